@@ -4,6 +4,7 @@
 
     python bench.py                       # N = 1, 100 steps after 20 warm-up steps
     python bench.py --gpus N              # starts its N ranks itself (one per GPU)
+    python bench.py --dump-outputs DIR    # + the last timed step's token ids as DIR/*.npy (float32), to compare builds
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -135,7 +136,14 @@ def main():
     ap.add_argument("--launch-probe", action="store_true",
                     help="rendezvous check only (CPU, gloo): every rank all-reduces its rank number, rank 0 prints "
                          "{n_gpus, ranks_seen}; exercises the self-launch path of `--gpus N` without a GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32; rank 0; --mode greedy): ids.npy = the (batch, seq) token ids of the timed region of "
+                         "`value`'s headline schedule (the pipeline, or the serial pass with --serial), ids_serial.npy = "
+                         "those of the serial pass.  Inputs are seeded: the same arguments give the same inputs every run")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.mode != "greedy":
+        ap.error("--dump-outputs is implemented for --mode greedy (the headline workload) only")
     args.pipelined = not args.serial
     args.coresident = not args.no_coresident
     args.group_flag = _lib.FLAG_DECODE_GROUP16 if args.decode_members == 16 else _lib.FLAG_DECODE_GROUP8
@@ -480,6 +488,9 @@ def main():
                                   "the timed region: after idle the GPU needs ~50 ms of load to reach its clocks "
                                   "(profiles/r03/ramp.txt); --settle-ms 0 turns it off") if settled["batches"] else "none"
 
+    if args.dump_outputs is not None and rank == 0:
+        result["dumped"] = dump_outputs(args.dump_outputs, {"ids": ids_host if args.serial else ids_pipe,
+                                                            "ids_serial": None if args.serial else ids_host})
     # ---- outside the timed region: the decode must not have timed out, and the ids must be the reference's
     _lib.check_ids(ids_host)
     result["ids_check"] = golden_ids_check(ids_host, B, T, rank)
@@ -544,6 +555,22 @@ def self_launch(n):
                                       stdout=None if r == 0 else subprocess.DEVNULL))
     codes = [p.wait() for p in procs]
     return max((abs(c) for c in codes), default=0)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every non-None tensor of `arrays` as out_dir/<name>.npy in float32 (token ids are exact in it);
+    returns {name: shape}.  Refuses to write more than DUMP_LIMIT_BYTES in all."""
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def golden_ids_check(ids_host, B, T, rank):

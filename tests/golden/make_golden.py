@@ -320,9 +320,26 @@ def run_init_parity():
     print("init parity ok", len(names))
 
 
+def run_encoder_fp64():
+    """G1 encoder output of every config with the reference evaluated in float64 (weights and images cast from the
+    same fp32 values): a target that does not depend on which CPU kernels summed the fp32 fixtures.  The fp32
+    Linear over K = 102 400 / 204 800 features of the wide configs differs by several 1e-6 between the AVX-512 and
+    AVX2 code paths of the CPU libraries, more than the fixtures' 1e-6 bound."""
+    out = {}
+    for name, (ckw, skw) in CONFIGS.items():
+        cfg = synth.model_config(**ckw)
+        ref = build_reference(cfg, synth.make_state_dict(cfg, **skw)).double()
+        imgs = torch.from_numpy(synth.make_images(4, cfg, seed=1234)).double()
+        with torch.no_grad():
+            out[name] = ref.encoder(imgs).numpy().copy()
+    np.savez_compressed(os.path.join(OUT, "encoder_fp64.npz"), **out)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     only = sys.argv[1:]
+    if not only or "encoder_fp64" in only:
+        run_encoder_fp64()
     for name, (ckw, skw) in CONFIGS.items():
         if only and name not in only:
             continue

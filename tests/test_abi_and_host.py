@@ -206,3 +206,30 @@ def test_bench_refuses_a_mismatched_world():
     if torch.cuda.device_count() < 2:
         r = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0"])
         assert r.returncode == 2 and "GPU(s) visible" in r.stderr and not r.stdout.strip()
+
+
+def test_bench_dump_outputs_refuses_other_modes(tmp_path):
+    """--dump-outputs covers the headline greedy workload; another mode refuses it before any work instead of
+    silently writing nothing."""
+    r = _run_bench(["--mode", "beam", "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr and not r.stdout.strip()
+    assert not (tmp_path / "out").exists()
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --steps K --dump-outputs DIR`: the line reports exactly K timed steps and ms_per_step, and DIR holds
+    the last timed step's ids of both timed passes as float32 (B, seq) arrays of whole token ids."""
+    out = tmp_path / "out"
+    r = _run_bench(["--steps", "3", "--warmup", "1", "--settle-ms", "0", "--no-cpu-baseline", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert d["dumped"] == {"ids": [256, 150], "ids_serial": [256, 150]}
+    for name in ("ids", "ids_serial"):
+        a = np.load(out / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (256, 150)
+        assert np.array_equal(a, np.round(a)) and a.min() >= 0 and a.max() < 512
+    assert sorted(os.listdir(out)) == ["ids.npy", "ids_serial.npy"]
