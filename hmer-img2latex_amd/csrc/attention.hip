@@ -10,13 +10,9 @@
 
 namespace {
 
-constexpr int NT = 256;
+#include "lstm_rows.inc.h"
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+constexpr int NT = 256;
 
 __global__ __launch_bounds__(NT) void attention_kernel(const float* __restrict__ hidden, const float* __restrict__ enc,
                                                        const float* __restrict__ w_attn, const float* __restrict__ b_attn,
@@ -45,7 +41,7 @@ __global__ __launch_bounds__(NT) void attention_kernel(const float* __restrict__
             for (int k = 0; k < E; ++k) a = fmaf(wr[k], eb[(size_t)s * E + k], a);
             part += v[j] * tanhf(a + b_attn[j]);
         }
-        part = wave_sum_f(part);
+        part = wave_sum(part);
         if (lane == 0) red[wave] = part;
         __syncthreads();
         if (tid == 0) {

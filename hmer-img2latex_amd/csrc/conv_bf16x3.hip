@@ -24,37 +24,9 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
+#include "bf16_split.inc.h"
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ bf16_t f2bf(float f) {
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (bf16_t)(u >> 16);
-}
-__device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ void split3(float x, bf16_t& s0, bf16_t& s1, bf16_t& s2) {
-    s0 = f2bf(x);
-    const float r1 = x - bf2f(s0);
-    s1 = f2bf(r1);
-    s2 = f2bf(r1 - bf2f(s1));
-}
-
-// two values at once: v_cvt_pk_bf16_f32 (round to nearest even, as f2bf) packs the pair into one dword
-typedef __bf16 bf16v2 __attribute__((ext_vector_type(2)));
-typedef float f32v2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& s0, unsigned& s1, unsigned& s2) {
-    f32v2 v = {x0, x1};
-    bf16v2 b0 = __builtin_convertvector(v, bf16v2);
-    v -= __builtin_convertvector(b0, f32v2);
-    bf16v2 b1 = __builtin_convertvector(v, bf16v2);
-    v -= __builtin_convertvector(b1, f32v2);
-    bf16v2 b2 = __builtin_convertvector(v, bf16v2);
-    s0 = *reinterpret_cast<unsigned*>(&b0);
-    s1 = *reinterpret_cast<unsigned*>(&b1);
-    s2 = *reinterpret_cast<unsigned*>(&b2);
-}
 
 constexpr int CH = 16;                        // input channels per chunk (= one MFMA k-step per tap)
 constexpr int CO_BLK = 64;
@@ -264,20 +236,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x3_kernel(
                 }
 #pragma unroll
                 for (int kx = 0; kx < 3; ++kx) {
-                    bf16x8 a[2][3], bw[NT][3];
+                    i16x8_t a[2][3], bw[NT][3];
 #pragma unroll
                     for (int m = 0; m < 2; ++m)
 #pragma unroll
                         for (int sp = 0; sp < 3; ++sp) {
                             const uint4 t = in_s[a_base + (sp * TL::IR + m * 2 + ky) * TL::ROW16 + kx];
-                            a[m][sp] = *reinterpret_cast<const bf16x8*>(&t);
+                            a[m][sp] = *reinterpret_cast<const i16x8_t*>(&t);
                         }
 #pragma unroll
                     for (int n = 0; n < NT; ++n)
 #pragma unroll
                         for (int sp = 0; sp < 3; ++sp) {
                             const uint4 t = w_s[b_base + ((kx * 3 + sp) * 2) * CO_BLK + n * 32];
-                            bw[n][sp] = *reinterpret_cast<const bf16x8*>(&t);
+                            bw[n][sp] = *reinterpret_cast<const i16x8_t*>(&t);
                         }
                     // smallest partial products first; consecutive MFMAs go to different accumulators
                     constexpr int TI[6] = {0, 1, 2, 0, 1, 0}, TJ[6] = {2, 1, 0, 1, 0, 0};
@@ -418,7 +390,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_smallk_bf16x3_kernel(
     const int y0 = blockIdx.y * 8;
 
     // B operand: k-step s, lane half h -> taps 4s + 2h, 4s + 2h + 1, channels 0..3 each
-    bf16x8 bw[3][3];
+    i16x8_t bw[3][3];
     {
         const int co = cb * 32 + i;
 #pragma unroll
@@ -435,7 +407,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_smallk_bf16x3_kernel(
 #pragma unroll
             for (int sp = 0; sp < 3; ++sp) {
                 const uint4 t = make_uint4(pk[sp][0], pk[sp][1], pk[sp][2], pk[sp][3]);
-                bw[s][sp] = *reinterpret_cast<const bf16x8*>(&t);
+                bw[s][sp] = *reinterpret_cast<const i16x8_t*>(&t);
             }
         }
     }
@@ -503,13 +475,13 @@ __global__ __launch_bounds__(256, 4) void conv3x3_smallk_bf16x3_kernel(
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
-                bf16x8 a[3];
+                i16x8_t a[3];
 #pragma unroll
                 for (int sp = 0; sp < 3; ++sp) {
                     const uint2 t0 = img[sp * PLANE + m * 2 * RS + aoff[s][0]];
                     const uint2 t1 = img[sp * PLANE + m * 2 * RS + aoff[s][1]];
                     const uint4 t = make_uint4(t0.x, t0.y, t1.x, t1.y);
-                    a[sp] = *reinterpret_cast<const bf16x8*>(&t);
+                    a[sp] = *reinterpret_cast<const i16x8_t*>(&t);
                 }
                 constexpr int TI[6] = {0, 1, 2, 0, 1, 0}, TJ[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll

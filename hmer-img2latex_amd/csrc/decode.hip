@@ -23,53 +23,14 @@
 
 namespace {
 
+#include "lstm_rows.inc.h"
+
 constexpr int MAXL = I2L_MAX_LSTM_LAYERS;
 constexpr int NT = 256;        // threads per workgroup
 constexpr int VCHUNK = 2 * NT;  // vocab columns per projection pass
 
-struct Layout {
-    size_t P, Genc, WhhT[MAXL], WihT[MAXL], biasP[MAXL], WoutT, boutP, wpack16, gemm_ws, xchg, xchg_bytes, total;
-    int Vp, n_groups;
-};
-
-// grouped decode (decode_group.inc.h): exchange granules [groups padded to 8][2][4][288] x 8 B + a status block
-constexpr size_t GROUP_XCHG_PER_GROUP = (size_t)2 * 4 * 288 * 8;
-constexpr size_t GROUP16_XCHG_BYTES = (size_t)2 * 16 * 288 * 8;   // decode_group16.inc.h: [2 parities][16 members][288 granules]
-constexpr size_t GROUP_STATUS_BYTES = 2048;
+constexpr size_t GROUP_STATUS_BYTES = 2048;   // status words in front of a grouped kernel's exchange granules
 inline bool group_shape_ok(int V, int H, int L) { return L == 1 && H == 256 && V <= 512; }
-
-Layout make_layout(int rows, int V, int E, int H, int L) {
-    Layout o{};
-    size_t off = 0;
-    auto take = [&](size_t floats) { size_t r = off; off += i2l_align(floats * sizeof(float)); return r; };
-    const size_t G = 4 * (size_t)H;
-    o.Vp = i2l_cdiv(V, VCHUNK) * VCHUNK;
-    o.P = take((size_t)V * G);
-    o.Genc = take((size_t)rows * G);
-    for (int l = 0; l < L; ++l) o.WhhT[l] = take((size_t)H * G);
-    for (int l = 1; l < L; ++l) o.WihT[l] = take((size_t)H * G);
-    for (int l = 1; l < L; ++l) o.biasP[l] = take(G);
-    o.WoutT = take((size_t)H * o.Vp);
-    o.boutP = take(o.Vp);
-    // decode_group16_kernel: the weights pre-split into bf16 pieces in the matrix cores' operand layout, [member 16][wave 4]
-    // [fragment 36][lane 64] x 16 bytes (weight-only: built with the other weight images under I2L_PREP_WEIGHTS)
-    if (group_shape_ok(V, H, L)) o.wpack16 = take((size_t)16 * 4 * 36 * 64 * 4);
-    size_t g1 = i2l_gemm_workspace_bytes(V, 4 * H, E), g2 = i2l_gemm_workspace_bytes(rows, 4 * H, E);
-    o.gemm_ws = off;
-    off += i2l_align(g1 > g2 ? g1 : g2);
-    if (group_shape_ok(V, H, L)) {
-        o.n_groups = i2l_cdiv(rows, 4);
-        o.xchg = off;
-        const size_t x4 = (size_t)i2l_cdiv(o.n_groups, 8) * 8 * GROUP_XCHG_PER_GROUP;
-        const size_t x8 = (size_t)i2l_cdiv(i2l_cdiv(rows, 8), 8) * 8 * (2 * GROUP_XCHG_PER_GROUP);   // 8 members x 8 rows (decode_group8)
-        const size_t x16 = (size_t)i2l_cdiv(i2l_cdiv(rows, 16), 8) * 8 * GROUP16_XCHG_BYTES;         // 16 x 16 (decode_group16)
-        const size_t x48 = x4 > x8 ? x4 : x8;
-        o.xchg_bytes = GROUP_STATUS_BYTES + (x48 > x16 ? x48 : x16);
-        off += i2l_align(o.xchg_bytes);
-    }
-    o.total = off;
-    return o;
-}
 
 // out[k][c] = W[n(c)][k] for c < Npad; n(c) = (c&3)*perm_h + (c>>2) when perm_h > 0 else c; rows n >= N read as 0.
 __global__ __launch_bounds__(256) void transpose_perm_kernel(const float* __restrict__ W, int N, int K,
@@ -132,132 +93,6 @@ struct DecodeParams {
     int top_k; float top_p; unsigned long long seed; float* probs;   // I2L_SELECT_SAMPLE only
 };
 
-// Gate functions of the search kernels (greedy, beam, row-per-workgroup): hardware exp2 / reciprocal (v_exp_f32,
-// v_rcp_f32: ~1 ulp each) instead of libm's expf / tanhf and an IEEE division -- the LSTM cell is a chain of five of
-// them on the critical path of every step (~150 dependent instructions -> ~30).  Absolute error <= ~2e-7 per call, the
-// class of the vectorised expf / tanhf ATen itself uses; saturation: exp -> inf gives 1/inf = 0, exp -> 0 gives -1 / 0+.
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * x) + 1.f); }
-
-// acc[r] += sum_k W[k][0..3] * x[r][k], k ascending (one fmaf chain per output).
-// The weight stream is software-pipelined: while the FMAs of one batch of PF rows run, the
-// loads of the next batch are already in flight (two register sets, counted vmcnt by the
-// compiler), so one wave per SIMD keeps ~PF 16-byte loads per lane outstanding.
-constexpr int PF = 8;
-
-template <int R, int NV>   // NV = 4 (float4: LSTM gates) or 2 (float2: vocabulary projection)
-struct WVec;
-template <int R>
-struct WVec<R, 4> { typedef float4 type; };
-template <int R>
-struct WVec<R, 2> { typedef float2 type; };
-
-template <int R>
-__device__ __forceinline__ void fma_rows(float4 (&acc)[R], const float4 (&w)[PF], const float* xs, int H, int k) {   // H = row stride of xs
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int i4 = 0; i4 < PF; i4 += 4) {
-            const float4 xa = *reinterpret_cast<const float4*>(xs + r * H + k + i4);
-            const float xv[4] = {xa.x, xa.y, xa.z, xa.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                acc[r].x = fmaf(w[i4 + i].x, xv[i], acc[r].x);
-                acc[r].y = fmaf(w[i4 + i].y, xv[i], acc[r].y);
-                acc[r].z = fmaf(w[i4 + i].z, xv[i], acc[r].z);
-                acc[r].w = fmaf(w[i4 + i].w, xv[i], acc[r].w);
-            }
-        }
-    }
-}
-
-template <typename VT>
-__device__ __forceinline__ void load_batch(VT (&w)[PF], const float* __restrict__ Wcol, size_t ldw) {
-#pragma unroll
-    for (int i = 0; i < PF; ++i) w[i] = *reinterpret_cast<const VT*>(Wcol + (size_t)i * ldw);
-}
-
-// matvec whose first batch (rows 0..PF-1) was loaded earlier by load_batch (prefetch across a barrier).
-template <int R, typename VT>
-__device__ __forceinline__ void matvec_pre(VT (&acc)[R], VT (&wa)[PF], const float* __restrict__ Wcol, size_t ldw,
-                                           const float* xs, int xstride, int H) {
-    VT wb[PF];
-    int k = 0;
-    for (; k + 2 * PF < H; k += 2 * PF) {
-#pragma unroll
-        for (int i = 0; i < PF; ++i) wb[i] = *reinterpret_cast<const VT*>(Wcol + (size_t)(k + PF + i) * ldw);
-        __builtin_amdgcn_sched_barrier(0);
-        fma_rows<R>(acc, wa, xs, xstride, k);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < PF; ++i) wa[i] = *reinterpret_cast<const VT*>(Wcol + (size_t)(k + 2 * PF + i) * ldw);
-        __builtin_amdgcn_sched_barrier(0);
-        fma_rows<R>(acc, wb, xs, xstride, k + PF);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int i = 0; i < PF; ++i) wb[i] = *reinterpret_cast<const VT*>(Wcol + (size_t)(k + PF + i) * ldw);
-    __builtin_amdgcn_sched_barrier(0);
-    fma_rows<R>(acc, wa, xs, xstride, k);
-    fma_rows<R>(acc, wb, xs, xstride, k + PF);
-}
-
-template <int R, typename VT>
-__device__ __forceinline__ void matvec(VT (&acc)[R], const float* __restrict__ Wcol, size_t ldw, const float* xs,
-                                       int xstride, int H) {   // H = number of k (multiple of 32), xstride = row stride of xs
-    VT wa[PF], wb[PF];
-    // No load sits under a condition: the compiler can then count outstanding loads exactly
-    // (s_waitcnt vmcnt(PF) before a batch is used) instead of draining to vmcnt(0) at a join.
-#pragma unroll
-    for (int i = 0; i < PF; ++i) wa[i] = *reinterpret_cast<const VT*>(Wcol + (size_t)i * ldw);
-    int k = 0;
-    for (; k + 2 * PF < H; k += 2 * PF) {                 // H % (2*PF) == 0
-#pragma unroll
-        for (int i = 0; i < PF; ++i) wb[i] = *reinterpret_cast<const VT*>(Wcol + (size_t)(k + PF + i) * ldw);
-        __builtin_amdgcn_sched_barrier(0);                // keep the batch of loads ahead of the FMAs
-        fma_rows<R>(acc, wa, xs, xstride, k);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < PF; ++i) wa[i] = *reinterpret_cast<const VT*>(Wcol + (size_t)(k + 2 * PF + i) * ldw);
-        __builtin_amdgcn_sched_barrier(0);
-        fma_rows<R>(acc, wb, xs, xstride, k + PF);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int i = 0; i < PF; ++i) wb[i] = *reinterpret_cast<const VT*>(Wcol + (size_t)(k + PF + i) * ldw);
-    __builtin_amdgcn_sched_barrier(0);
-    fma_rows<R>(acc, wa, xs, xstride, k);
-    fma_rows<R>(acc, wb, xs, xstride, k + PF);
-}
-
-template <int R>
-__device__ __forceinline__ void matvec4(float4 (&acc)[R], const float* __restrict__ Wcol, size_t ldw,
-                                        const float* xs, int H) {
-    matvec<R, float4>(acc, Wcol, ldw, xs, H, H);
-}
-
-// (value, index) max with "first index wins" over the 64 lanes of a wave.
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(v, off, 64);
-        const int oi = __shfl_xor(i, off, 64);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // All L layers of one LSTM time step for R rows of one workgroup (decoder.py:247/277 at seq len 1).
 // h is double-buffered in LDS: reads hs[par], writes hs[par^1]; c_in -> c_out (may alias: each
 // element is read and written by the same thread).  tok[r] selects the row of P, grow[r] the row of Genc.
@@ -283,9 +118,9 @@ __device__ __forceinline__ void lstm_layers(const StepWeights& w, const int (&to
                 const float4 bb = *reinterpret_cast<const float4*>(w.biasP[l] + 4 * j);
 #pragma unroll
                 for (int r = 0; r < R; ++r) acc[r] = bb;
-                matvec4<R>(acc, w.WihT[l] + 4 * j, G, hs + ((size_t)(par ^ 1) * L + (l - 1)) * R * H, H);
+                matvec<R, float4>(acc, w.WihT[l] + 4 * j, G, hs + ((size_t)(par ^ 1) * L + (l - 1)) * R * H, H, H);
             }
-            matvec4<R>(acc, w.WhhT[l] + 4 * j, G, h_old, H);
+            matvec<R, float4>(acc, w.WhhT[l] + 4 * j, G, h_old, H, H);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const size_t ci = ((size_t)l * R + r) * H + j;
@@ -894,6 +729,69 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamParams p) {
     }
 }
 
+// The grouped greedy kernels, in the order launch_decode tries them.  A group is `rows` workgroups (one per member and
+// row), the grid is padded to a multiple of 8 groups, and the exchange region is [groups padded to 8][xchg_per_group].
+// The 16- and 8-member kernels run only when their flag asks for them and take ids only (no logits output, no forced
+// tokens); the 4-member kernel takes every grouped greedy call.
+struct GroupVariant {
+    void (*kernel)(GroupParams);
+    int flag;                 // I2L_FLAG_DECODE_GROUP16 / GROUP8; 0: the 4-member kernel
+    int rows, threads;
+    size_t lds, xchg_per_group;
+};
+constexpr int GROUP_VARIANTS = 3;
+// (a table inside a function: the library keeps no data symbols beyond its attribute caches)
+constexpr GroupVariant group_variant(int i) {
+    constexpr GroupVariant table[GROUP_VARIANTS] = {
+        // sixteen members x sixteen rows, the per-step products on the matrix cores (decode_group16.inc.h)
+        {decode_group16_kernel, I2L_FLAG_DECODE_GROUP16, G16Q, G16NT, GRP16_LDS, GROUP16_XCHG_PER_GROUP},
+        // eight members x eight rows: one wave per SIMD and ~80 KB of LDS per CU, i.e. room for a conv workgroup beside it
+        {decode_group8_kernel, I2L_FLAG_DECODE_GROUP8, G8Q, G8NT, GRP8_LDS, GROUP8_XCHG_PER_GROUP},
+        // four members x four rows (decode_group.inc.h)
+        {decode_group_kernel, 0, GQ, GNT, GRP_LDS, GROUP_XCHG_PER_GROUP},
+    };
+    return table[i];
+}
+
+struct Layout {
+    size_t P, Genc, WhhT[MAXL], WihT[MAXL], biasP[MAXL], WoutT, boutP, wpack16, gemm_ws, xchg, xchg_bytes, total;
+    int Vp;
+};
+
+Layout make_layout(int rows, int V, int E, int H, int L) {
+    Layout o{};
+    size_t off = 0;
+    auto take = [&](size_t floats) { size_t r = off; off += i2l_align(floats * sizeof(float)); return r; };
+    const size_t G = 4 * (size_t)H;
+    o.Vp = i2l_cdiv(V, VCHUNK) * VCHUNK;
+    o.P = take((size_t)V * G);
+    o.Genc = take((size_t)rows * G);
+    for (int l = 0; l < L; ++l) o.WhhT[l] = take((size_t)H * G);
+    for (int l = 1; l < L; ++l) o.WihT[l] = take((size_t)H * G);
+    for (int l = 1; l < L; ++l) o.biasP[l] = take(G);
+    o.WoutT = take((size_t)H * o.Vp);
+    o.boutP = take(o.Vp);
+    // decode_group16_kernel: the weights pre-split into bf16 pieces in the matrix cores' operand layout, [member 16][wave 4]
+    // [fragment 36][lane 64] x 16 bytes (weight-only: built with the other weight images under I2L_PREP_WEIGHTS)
+    if (group_shape_ok(V, H, L)) o.wpack16 = take((size_t)16 * 4 * 36 * 64 * 4);
+    size_t g1 = i2l_gemm_workspace_bytes(V, 4 * H, E), g2 = i2l_gemm_workspace_bytes(rows, 4 * H, E);
+    o.gemm_ws = off;
+    off += i2l_align(g1 > g2 ? g1 : g2);
+    if (group_shape_ok(V, H, L)) {   // status block + the largest exchange region of the grouped greedy kernels
+        o.xchg = off;
+        size_t most = 0;
+        for (int i = 0; i < GROUP_VARIANTS; ++i) {
+            const GroupVariant g = group_variant(i);
+            const size_t x = (size_t)i2l_cdiv(i2l_cdiv(rows, g.rows), 8) * 8 * g.xchg_per_group;
+            most = x > most ? x : most;
+        }
+        o.xchg_bytes = GROUP_STATUS_BYTES + most;
+        off += i2l_align(o.xchg_bytes);
+    }
+    o.total = off;
+    return o;
+}
+
 int check_weights(const i2l_decoder_weights* w) {
     if (!w || !w->embedding || !w->w_ih || !w->w_hh || !w->b_ih || !w->b_hh || !w->w_out || !w->b_out)
         return I2L_ERR_ARG;
@@ -1067,58 +965,16 @@ int launch_decode(const i2l_decoder_weights* w, const void* workspace, int rows,
     p.select = select; p.stop = stop; p.end_id = end_id;
     p.top_k = top_k; p.top_p = top_p; p.seed = seed; p.probs = probs_out;
 
-    // grouped kernel: 4 workgroups share 4 rows, weights fully on chip (decode_group.inc.h)
-    // I2L_SELECT_SOFTMAX takes it too: softmax is monotone, so its arg max is the logits' arg max unless fp32 rounding
+    // grouped kernels (group_variant): the workgroups of a group share its rows, weights fully on chip
+    // I2L_SELECT_SOFTMAX takes them too: softmax is monotone, so its arg max is the logits' arg max unless fp32 rounding
     // makes two DIFFERENT scaled logits equal probabilities, which needs the two largest to be adjacent floats AND the
     // largest below 2 in magnitude (exp(x2 - x1) is then within 2 ulp of 1); the row-per-workgroup kernel evaluates
     // the probabilities literally and is one argument away (rows_per_workgroup != 0)
     if (rows_per_wg == 0 && lo.xchg_bytes && (select == I2L_SELECT_LOGITS || select == I2L_SELECT_SOFTMAX) && !h0 &&
         !h_out && !c_out &&
         steps >= 8 && steps <= 65000) {   // the candidate granule carries step + 1 in 16 bits
-        if ((flags & I2L_FLAG_DECODE_GROUP16) && !logits_out && !forced && ids_out) {
-            // sixteen members x sixteen rows, the per-step products on the matrix cores (decode_group16.inc.h)
-            static_assert(GROUP16_XCHG_PER_GROUP == GROUP16_XCHG_BYTES, "exchange region sizing");
-            GroupParams gp{};
-            gp.w = p.w; gp.B = rows; gp.T = steps; gp.n_groups = i2l_cdiv(rows, 16);
-            gp.tok0 = tok0; gp.forced = nullptr; gp.ids = ids_out; gp.logits = nullptr;
-            gp.temperature = temperature; gp.use_temp = p.use_temp; gp.stop = stop; gp.end_id = end_id;
-            char* xb = const_cast<char*>(base) + lo.xchg;
-            gp.status = reinterpret_cast<unsigned*>(xb);
-            gp.xchg = reinterpret_cast<u64_t*>(xb + GROUP_STATUS_BYTES);
-            gp.opts = group_opts(steps, flags);
-            gp.resident_flag = resident_flag; gp.resident_value = resident_value;
-            hipStream_t gs = i2l_s(stream);
-            static std::atomic<unsigned> attr16{0};
-            if (i2l_lds_attr(reinterpret_cast<const void*>(decode_group16_kernel), GRP16_LDS, attr16)) {
-                if (!(flags & I2L_FLAG_DECODE_REGION_CLEARED) && hipMemsetAsync(xb, 0, lo.xchg_bytes, gs) != hipSuccess) return I2L_ERR_LAUNCH;
-                hipLaunchKernelGGL(decode_group16_kernel, dim3(i2l_cdiv(gp.n_groups, 8) * 128), dim3(G16NT), GRP16_LDS, gs, gp);
-                I2L_CHECK_LAUNCH();
-                return I2L_OK;
-            }
-        }
-        if ((flags & I2L_FLAG_DECODE_GROUP8) && !logits_out && !forced && ids_out) {
-            // eight members x eight rows: one wave per SIMD and ~80 KB of LDS per CU, i.e. room for a conv workgroup beside it
-            static_assert(GROUP8_XCHG_PER_GROUP == 2 * GROUP_XCHG_PER_GROUP, "exchange region sizing");
-            GroupParams gp{};
-            gp.w = p.w; gp.B = rows; gp.T = steps; gp.n_groups = i2l_cdiv(rows, 8);
-            gp.tok0 = tok0; gp.forced = nullptr; gp.ids = ids_out; gp.logits = nullptr;
-            gp.temperature = temperature; gp.use_temp = p.use_temp; gp.stop = stop; gp.end_id = end_id;
-            char* xb = const_cast<char*>(base) + lo.xchg;
-            gp.status = reinterpret_cast<unsigned*>(xb);
-            gp.xchg = reinterpret_cast<u64_t*>(xb + GROUP_STATUS_BYTES);
-            gp.opts = group_opts(steps, flags);
-            gp.resident_flag = resident_flag; gp.resident_value = resident_value;
-            hipStream_t gs = i2l_s(stream);
-            static std::atomic<unsigned> attr8{0};               // per device
-            if (i2l_lds_attr(reinterpret_cast<const void*>(decode_group8_kernel), GRP8_LDS, attr8)) {
-                if (!(flags & I2L_FLAG_DECODE_REGION_CLEARED) && hipMemsetAsync(xb, 0, lo.xchg_bytes, gs) != hipSuccess) return I2L_ERR_LAUNCH;
-                hipLaunchKernelGGL(decode_group8_kernel, dim3(i2l_cdiv(gp.n_groups, 8) * 64), dim3(G8NT), GRP8_LDS, gs, gp);
-                I2L_CHECK_LAUNCH();
-                return I2L_OK;
-            }
-        }
         GroupParams gp{};
-        gp.w = p.w; gp.B = rows; gp.T = steps; gp.n_groups = lo.n_groups;
+        gp.w = p.w; gp.B = rows; gp.T = steps;
         gp.tok0 = tok0; gp.forced = forced; gp.ids = ids_out; gp.logits = logits_out;
         gp.temperature = temperature; gp.use_temp = p.use_temp; gp.stop = stop; gp.end_id = end_id;
         char* xb = const_cast<char*>(base) + lo.xchg;           // scratch region of the workspace
@@ -1127,10 +983,15 @@ int launch_decode(const i2l_decoder_weights* w, const void* workspace, int rows,
         gp.opts = group_opts(steps, flags);
         gp.resident_flag = resident_flag; gp.resident_value = resident_value;
         hipStream_t gs = i2l_s(stream);
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(decode_group_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRP_LDS) == hipSuccess) {
+        const bool ids_only = ids_out && !logits_out && !forced;
+        static std::atomic<unsigned> attr[GROUP_VARIANTS]{};   // per variant and device
+        for (int i = 0; i < GROUP_VARIANTS; ++i) {
+            const GroupVariant g = group_variant(i);
+            if (g.flag && !((flags & g.flag) && ids_only)) continue;
+            if (!i2l_lds_attr(reinterpret_cast<const void*>(g.kernel), g.lds, attr[i])) continue;   // try the next one
             if (!(flags & I2L_FLAG_DECODE_REGION_CLEARED) && hipMemsetAsync(xb, 0, lo.xchg_bytes, gs) != hipSuccess) return I2L_ERR_LAUNCH;
-            hipLaunchKernelGGL(decode_group_kernel, dim3(i2l_cdiv(lo.n_groups, 8) * 32), dim3(GNT), GRP_LDS, gs, gp);
+            gp.n_groups = i2l_cdiv(rows, g.rows);
+            hipLaunchKernelGGL(g.kernel, dim3(i2l_cdiv(gp.n_groups, 8) * 8 * g.rows), dim3(g.threads), g.lds, gs, gp);
             I2L_CHECK_LAUNCH();
             return I2L_OK;
         }
@@ -1209,9 +1070,8 @@ template <int K>
 int launch_beam_group(const BeamGroupParams& p, hipStream_t s) {
     constexpr size_t lds = bg_lds_bytes();
     static_assert(lds <= 160 * 1024, "beam_group_kernel LDS");
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_group_kernel<K>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return I2L_ERR_UNSUPPORTED;
+    static std::atomic<unsigned> attr{0};
+    if (!i2l_lds_attr(reinterpret_cast<const void*>(&beam_group_kernel<K>), lds, attr)) return I2L_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(beam_group_kernel<K>, dim3(i2l_cdiv(p.n_groups, 8) * 32), dim3(GNT), lds, s, p);
     I2L_CHECK_LAUNCH();
     return I2L_OK;

@@ -53,6 +53,7 @@ constexpr int GRAN = GRAN_H + 32;
 // LDS: W_out quarter | h [2 parities][256 k][4 rows] | per-thread image-side gate constants (Genc, read once per step: four
 // registers less across the recurrent product) | arg-max keys [2 parities][4 rows] | arrival counters [2] + flags
 constexpr size_t GRP_LDS = (size_t)(256 * 128 + 2 * 256 * 4 + GNT * 4) * sizeof(float) + (size_t)2 * 4 * 8 + 8 * sizeof(int);
+constexpr size_t GROUP_XCHG_PER_GROUP = (size_t)2 * GQ * GRAN * 8;
 
 struct GroupParams {
     StepWeights w;

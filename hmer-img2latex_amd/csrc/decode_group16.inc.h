@@ -32,7 +32,8 @@
 // Tags, two buffers by step parity, bounded polls, placement measurement, failure marking (ids -3), residency signal:
 // exactly as decode_group8_kernel.  Supported: ids out (both stop rules, temperature, arg max of logits / of softmax);
 // no logits output, no forced tokens, no initial / returned state.
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+#include "bf16_split.inc.h"
+
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
@@ -47,19 +48,6 @@ constexpr int G16_HP_PIECE = 32 * 16 * 8;  // bf16 elements of one piece image
 constexpr size_t GRP16_LDS = (size_t)2 * 3 * G16_HP_PIECE * 2 + (size_t)2 * 64 * 16 + (size_t)2 * 16 * 8 + 8 * sizeof(int);
 constexpr size_t GROUP16_XCHG_PER_GROUP = (size_t)2 * G16Q * G16GRAN * 8;
 
-__device__ __forceinline__ unsigned short f2bf_rne(float f) {
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-__device__ __forceinline__ float bf2f_(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-// x = p0 + p1 + p2 exactly (3 x 8 mantissa bits); every difference below is exact in fp32
-__device__ __forceinline__ void split3(float x, unsigned short& p0, unsigned short& p1, unsigned short& p2) {
-    p0 = f2bf_rne(x);
-    const float r1 = x - bf2f_(p0);
-    p1 = f2bf_rne(r1);
-    p2 = f2bf_rne(r1 - bf2f_(p1));
-}
 union Frag16 {
     bf16x8_t v;
     u32x4_t q;

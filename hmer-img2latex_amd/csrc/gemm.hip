@@ -20,6 +20,8 @@
 
 namespace {
 
+#include "bf16_split.inc.h"
+
 constexpr int BM = 64, BN = 64, BK = 64, LDP = BK + 1;
 constexpr int NLD = BM * BK / 4 / 256;      // float4 loads per thread per operand tile
 constexpr int KQ = BK / 4;                  // float4 chunks along k
@@ -254,29 +256,15 @@ void launch(const GemmArgs& g, float* ws, int kc, int ks, int slabs, bool vec, d
 // operand reads (32 lanes = 32 consecutive rows) are conflict-free.  Workgroups that share a K slice (same operand
 // bytes) get block ids that are equal mod 8: one XCD, one L2 (speed only).
 // ---------------------------------------------------------------------------------------------------------------
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16v2_t __attribute__((ext_vector_type(2)));
-typedef float f32v2_t __attribute__((ext_vector_type(2)));
 constexpr int LBN = 64, LBK = 32, LPW = LBN + 2;
 
-__device__ __forceinline__ void lsplit3_pair(float x0, float x1, unsigned& s0, unsigned& s1, unsigned& s2) {
-    f32v2_t v = {x0, x1};
-    bf16v2_t b0 = __builtin_convertvector(v, bf16v2_t);
-    v -= __builtin_convertvector(b0, f32v2_t);
-    bf16v2_t b1 = __builtin_convertvector(v, bf16v2_t);
-    v -= __builtin_convertvector(b1, f32v2_t);
-    bf16v2_t b2 = __builtin_convertvector(v, bf16v2_t);
-    s0 = *reinterpret_cast<unsigned*>(&b0);
-    s1 = *reinterpret_cast<unsigned*>(&b1);
-    s2 = *reinterpret_cast<unsigned*>(&b2);
-}
 // 8 consecutive k of one row -> one 16-byte piece per split
 __device__ __forceinline__ void lsplit_piece(const float4& lo, const float4& hi, uint4 (&out)[3]) {
     unsigned p[3][4];
-    lsplit3_pair(lo.x, lo.y, p[0][0], p[1][0], p[2][0]);
-    lsplit3_pair(lo.z, lo.w, p[0][1], p[1][1], p[2][1]);
-    lsplit3_pair(hi.x, hi.y, p[0][2], p[1][2], p[2][2]);
-    lsplit3_pair(hi.z, hi.w, p[0][3], p[1][3], p[2][3]);
+    split3_pair(lo.x, lo.y, p[0][0], p[1][0], p[2][0]);
+    split3_pair(lo.z, lo.w, p[0][1], p[1][1], p[2][1]);
+    split3_pair(hi.x, hi.y, p[0][2], p[1][2], p[2][2]);
+    split3_pair(hi.z, hi.w, p[0][3], p[1][3], p[2][3]);
 #pragma unroll
     for (int sp = 0; sp < 3; ++sp) out[sp] = make_uint4(p[sp][0], p[sp][1], p[sp][2], p[sp][3]);
 }
@@ -447,17 +435,17 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16x3_kernel(GemmArgs g, float* 
         if (k0 + 2 * LBK < kf_end) fetch(cur, k0 + 2 * LBK);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            bf16x8_t a[MT][3], b[3];
+            i16x8_t a[MT][3], b[3];
 #pragma unroll
             for (int sp = 0; sp < 3; ++sp) {
                 const int plane = sp * 4 + s * 2 + h;
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
                     const uint4 t = a_s[plane * LPA_ + wm * 32 * MT + m * 32 + i];
-                    a[m][sp] = *reinterpret_cast<const bf16x8_t*>(&t);
+                    a[m][sp] = *reinterpret_cast<const i16x8_t*>(&t);
                 }
                 const uint4 t = w_s[plane * LPW + wn * 32 + i];
-                b[sp] = *reinterpret_cast<const bf16x8_t*>(&t);
+                b[sp] = *reinterpret_cast<const i16x8_t*>(&t);
             }
             constexpr int TI[6] = {0, 1, 2, 0, 1, 0}, TJ[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll

@@ -13,16 +13,9 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "bf16_split.inc.h"
 
-__device__ __forceinline__ bf16_t f2bf(float f) {
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);          // round to nearest even (finite inputs)
-    return (bf16_t)(u >> 16);
-}
-__device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float((unsigned)h << 16); }
+typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ------------------------------------------------------------------ bf16 GEMM with fused epilogue
 // out[m][n] = act( acc[m][n] * scale[n] + bias[n] + res[m][n] ),  acc = sum_k A[m][k] * W[n][k]
@@ -122,13 +115,13 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(BfGemm g) {
         if (k0 + GK < g.K) fetch(k0 + GK);                 // next tile in flight during the MFMAs
 #pragma unroll
         for (int ks = 0; ks < GK; ks += 16) {
-            bf16x8 a[2], b[NTW];
+            i16x8_t a[2], b[NTW];
 #pragma unroll
             for (int t = 0; t < 2; ++t)
-                a[t] = *reinterpret_cast<const bf16x8*>(&As[(wm * 64 + t * 32 + li) * GLD + ks + 8 * lh]);
+                a[t] = *reinterpret_cast<const i16x8_t*>(&As[(wm * 64 + t * 32 + li) * GLD + ks + 8 * lh]);
 #pragma unroll
             for (int t = 0; t < NTW; ++t)
-                b[t] = *reinterpret_cast<const bf16x8*>(&Ws[(wn * 32 * NTW + t * 32 + li) * GLD + ks + 8 * lh]);
+                b[t] = *reinterpret_cast<const i16x8_t*>(&Ws[(wn * 32 * NTW + t * 32 + li) * GLD + ks + 8 * lh]);
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -340,15 +333,15 @@ __global__ __launch_bounds__(256, OCC) void gemm_bf16_ring_kernel(BfGemm g, int 
         else wait_vm<0>();
         __builtin_amdgcn_s_barrier();                      // stage kt landed for every wave; slot kt-1 is free
         const unsigned char* st = ring + slot * STAGE;
-        bf16x8 a[BK / 16][2], b[BK / 16][NTW];             // the whole tile's fragments, then the MFMAs
+        i16x8_t a[BK / 16][2], b[BK / 16][NTW];             // the whole tile's fragments, then the MFMAs
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks) {
 #pragma unroll
             for (int x = 0; x < 2; ++x)
-                a[ks][x] = *reinterpret_cast<const bf16x8*>(st + offA[x] + (((2 * ks) ^ qA[x]) << 4));
+                a[ks][x] = *reinterpret_cast<const i16x8_t*>(st + offA[x] + (((2 * ks) ^ qA[x]) << 4));
 #pragma unroll
             for (int x = 0; x < NTW; ++x)
-                b[ks][x] = *reinterpret_cast<const bf16x8*>(st + offB[x] + (((2 * ks) ^ qB[x]) << 4));
+                b[ks][x] = *reinterpret_cast<const i16x8_t*>(st + offB[x] + (((2 * ks) ^ qB[x]) << 4));
         }
         if (NS > 1 && kt + NS - 1 < KT) issue();
 #pragma unroll
@@ -487,12 +480,12 @@ __global__ __launch_bounds__(256) void stem_conv7_kernel(const float* __restrict
             const int q0 = 2 * ks + Q0, q1 = (2 * ks + 1 > 20) ? 20 : 2 * ks + 1;
             const int rq = lh ? ((q1 / 7) * ST_WR + q1 % 7) : ((q0 / 7) * ST_WR + q0 % 7);
             const unsigned* pw = reinterpret_cast<const unsigned*>(win + abase + rq * ST_WS);
-            union { unsigned u[4]; bf16x8 v; } a;
+            union { unsigned u[4]; i16x8_t v; } a;
 #pragma unroll
             for (int e = 0; e < 4; ++e) a.u[e] = pw[e];
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
-                const bf16x8 bb = *reinterpret_cast<const bf16x8*>(&wl[(nt * 32 + li) * ST_WLD + ks * 16 + lh * 8]);
+                const i16x8_t bb = *reinterpret_cast<const i16x8_t*>(&wl[(nt * 32 + li) * ST_WLD + ks * 16 + lh * 8]);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, bb, acc[nt], 0, 0, 0);
             }
         }

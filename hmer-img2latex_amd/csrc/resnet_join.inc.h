@@ -93,13 +93,13 @@ __global__ __launch_bounds__(256, 1) void bottleneck_join_kernel(JoinArgs g) {
                     for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                bf16x8 a[2], b[2];
+                i16x8_t a[2], b[2];
 #pragma unroll
                 for (int x = 0; x < 2; ++x) {
                     const int row = x * 32 + li;
-                    a[x] = *reinterpret_cast<const bf16x8*>(a1 + row * 128 + (((2 * ks + lh) ^ ring_swz<64>(row)) << 4));
+                    a[x] = *reinterpret_cast<const i16x8_t*>(a1 + row * 128 + (((2 * ks + lh) ^ ring_swz<64>(row)) << 4));
                     const int n = n1base + x * 32 + li;
-                    b[x] = *reinterpret_cast<const bf16x8*>(w1s + n * 128 + (((2 * ks + lh) ^ ring_swz<64>(n)) << 4));
+                    b[x] = *reinterpret_cast<const i16x8_t*>(w1s + n * 128 + (((2 * ks + lh) ^ ring_swz<64>(n)) << 4));
                 }
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt)
@@ -141,11 +141,11 @@ __global__ __launch_bounds__(256, 1) void bottleneck_join_kernel(JoinArgs g) {
         for (int kt = 0; kt < 4; ++kt) {
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                const bf16x8 a = *reinterpret_cast<const bf16x8*>(&inter[(r2base + li) * JN_ILD + kt * 64 + ks * 16 + lh * 8]);
+                const i16x8_t a = *reinterpret_cast<const i16x8_t*>(&inter[(r2base + li) * JN_ILD + kt * 64 + ks * 16 + lh * 8]);
 #pragma unroll
                 for (int nt = 0; nt < NT2; ++nt) {
                     const int n = c2base + nt * 32 + li;
-                    const bf16x8 b = *reinterpret_cast<const bf16x8*>(w2s + kt * (N2 * 128) + n * 128 + (((2 * ks + lh) ^ ring_swz<64>(n)) << 4));
+                    const i16x8_t b = *reinterpret_cast<const i16x8_t*>(w2s + kt * (N2 * 128) + n * 128 + (((2 * ks + lh) ^ ring_swz<64>(n)) << 4));
                     acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc2[nt], 0, 0, 0);
                 }
             }

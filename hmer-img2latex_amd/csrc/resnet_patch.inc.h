@@ -129,16 +129,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch_bf16_kernel(BfGemm g, in
             const unsigned wbase = slot * WST;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                bf16x8 a[MTW], b[NTW];
+                i16x8_t a[MTW], b[NTW];
 #pragma unroll
                 for (int mt = 0; mt < MTW; ++mt) {
                     const int q = q0[mt] + tq;
                     const unsigned ad = ((rowok[mt] >> ky) & 1u) ? pbase + q * 64 + (((2 * ks + lh) ^ ((q >> 2) & 3)) << 4) : zoff;
-                    a[mt] = *reinterpret_cast<const bf16x8*>(lds + ad);
+                    a[mt] = *reinterpret_cast<const i16x8_t*>(lds + ad);
                 }
 #pragma unroll
                 for (int nt = 0; nt < NTW; ++nt)
-                    b[nt] = *reinterpret_cast<const bf16x8*>(lds + wbase + rowB[nt] + (((2 * ks + lh) ^ swB[nt]) << 4));
+                    b[nt] = *reinterpret_cast<const i16x8_t*>(lds + wbase + rowB[nt] + (((2 * ks + lh) ^ swB[nt]) << 4));
 #pragma unroll
                 for (int mt = 0; mt < MTW; ++mt)
 #pragma unroll

@@ -22,8 +22,7 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-__device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float((unsigned)h << 16); }
+#include "bf16_split.inc.h"
 
 constexpr int SLAB_ROWS = 128;          // rows of the (M, C) matrix one workgroup reduces (M / 128 workgroups: 640+ at B = 64)
 

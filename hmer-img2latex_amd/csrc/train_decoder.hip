@@ -23,9 +23,10 @@
 
 namespace {
 
+#include "lstm_rows.inc.h"
+
 constexpr int MAXL = I2L_MAX_LSTM_LAYERS;
 constexpr int NT = 256;
-constexpr int PF = 8;
 constexpr int RES_KR = 96, RES_KL = 32;     // rows of W_hh kept in registers / LDS by the recurrence fast paths
 
 // ------------------------------------------------------------------ dropout mask
@@ -76,53 +77,6 @@ __global__ __launch_bounds__(256) void dropout_rows_kernel(const float* __restri
         out[i] = in[i] * keep_scale(seed, stream, i, p, inv_keep);
 }
 
-// ------------------------------------------------------------------ pipelined matvec (same scheme as decode.hip)
-template <int R>
-__device__ __forceinline__ void fma_rows(float4 (&acc)[R], const float4 (&w)[PF], const float* xs, int xstride, int k) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int i4 = 0; i4 < PF; i4 += 4) {
-            const float4 xa = *reinterpret_cast<const float4*>(xs + r * xstride + k + i4);
-            const float xv[4] = {xa.x, xa.y, xa.z, xa.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                acc[r].x = fmaf(w[i4 + i].x, xv[i], acc[r].x);
-                acc[r].y = fmaf(w[i4 + i].y, xv[i], acc[r].y);
-                acc[r].z = fmaf(w[i4 + i].z, xv[i], acc[r].z);
-                acc[r].w = fmaf(w[i4 + i].w, xv[i], acc[r].w);
-            }
-        }
-    }
-}
-
-// acc[r] += sum_{k<count} W[k][0..3] * xs[r*xstride + k];  count % (2*PF) == 0.
-template <int R>
-__device__ __forceinline__ void matvec(float4 (&acc)[R], const float* __restrict__ Wcol, size_t ldw, const float* xs,
-                                       int xstride, int count) {
-    float4 wa[PF], wb[PF];
-#pragma unroll
-    for (int i = 0; i < PF; ++i) wa[i] = *reinterpret_cast<const float4*>(Wcol + (size_t)i * ldw);
-    int k = 0;
-    for (; k + 2 * PF < count; k += 2 * PF) {
-#pragma unroll
-        for (int i = 0; i < PF; ++i) wb[i] = *reinterpret_cast<const float4*>(Wcol + (size_t)(k + PF + i) * ldw);
-        __builtin_amdgcn_sched_barrier(0);
-        fma_rows<R>(acc, wa, xs, xstride, k);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < PF; ++i) wa[i] = *reinterpret_cast<const float4*>(Wcol + (size_t)(k + 2 * PF + i) * ldw);
-        __builtin_amdgcn_sched_barrier(0);
-        fma_rows<R>(acc, wb, xs, xstride, k + PF);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int i = 0; i < PF; ++i) wb[i] = *reinterpret_cast<const float4*>(Wcol + (size_t)(k + PF + i) * ldw);
-    __builtin_amdgcn_sched_barrier(0);
-    fma_rows<R>(acc, wa, xs, xstride, k);
-    fma_rows<R>(acc, wb, xs, xstride, k + PF);
-}
-
 // One-row matvec whose first KR weight rows sit in this thread's registers and the next KL rows in LDS for the
 // whole kernel (loaded once); only the remaining rows are streamed from L2 each step.  Same k order as matvec.
 template <int KR, int KL>
@@ -154,13 +108,9 @@ __device__ __forceinline__ void matvec_res(float4& acc, const float4 (&wres)[KR 
         }
     }
     float4 a1[1] = {acc};
-    matvec<1>(a1, Wcol + (size_t)(KR + KL) * ldw, ldw, xs + KR + KL, 0, count - KR - KL);
+    matvec<1, float4>(a1, Wcol + (size_t)(KR + KL) * ldw, ldw, xs + KR + KL, 0, count - KR - KL);
     acc = a1[0];
 }
-
-// gate functions on the hardware exp2 / reciprocal (v_exp_f32, v_rcp_f32), as in decode.hip: <= ~2e-7 absolute per call
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * x) + 1.f); }
 
 #include "train_group.inc.h"
 
@@ -244,9 +194,9 @@ __global__ __launch_bounds__(NT) void lstm_train_fwd_kernel(TrainBuf p) {
                     const float4 bb = *reinterpret_cast<const float4*>(p.biasP[l] + 4 * j);
 #pragma unroll
                     for (int r = 0; r < R; ++r) acc[r] = bb;
-                    matvec<R>(acc, p.WihT[l] + 4 * j, G, hd + (size_t)(l - 1) * R * H, H, H);
+                    matvec<R, float4>(acc, p.WihT[l] + 4 * j, G, hd + (size_t)(l - 1) * R * H, H, H);
                 }
-                matvec<R>(acc, p.WhhT[l] + 4 * j, G, h_old, H, H);
+                matvec<R, float4>(acc, p.WhhT[l] + 4 * j, G, h_old, H, H);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const size_t ci = ((size_t)l * R + r) * H + j;
@@ -369,7 +319,7 @@ __global__ __launch_bounds__(NT) void lstm_train_bwd_kernel(BwdBuf p) {
                         matvec_res<KR, KL>(acc[0], wres, wl + ((size_t)ng * KL) * H + 4 * cg, H,
                                            W + (size_t)ng * rows_per * H + 4 * cg, (size_t)H, dgs + ng * rows_per, rows_per);
                     else
-                        matvec<R>(acc, W + (size_t)ng * rows_per * H + 4 * cg, (size_t)H, dgs + ng * rows_per, (int)G, rows_per);
+                        matvec<R, float4>(acc, W + (size_t)ng * rows_per * H + 4 * cg, (size_t)H, dgs + ng * rows_per, (int)G, rows_per);
 #pragma unroll
                     for (int r = 0; r < R; ++r)
                         *reinterpret_cast<float4*>(part + ((size_t)ng * R + r) * H + 4 * cg) = acc[r];
