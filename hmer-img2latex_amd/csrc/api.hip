@@ -81,7 +81,8 @@ extern "C" int i2l_lanes_join(i2l_lanes* l, i2l_stream_t stream) {
 // schedule that is 15 - 20 % slower (profiles/r03/ramp.txt).  r03 approximated the dependency with a 30 us delay kernel.
 // The wait is one wave polling with s_sleep; it is BOUNDED (timeout_us <= 100 ms): a signal that never comes -- a launch
 // that fell back to another kernel, a timed-out group -- costs time, never a hang.  Values compare as a wrapping
-// sequence: the wait ends when (int32)(*flag - value) >= 0.
+// sequence: the wait ends when (int32)(*flag - value) >= 0.  The publishers keep that order: they store a value only if it
+// is ahead of the word (a compare-and-swap maximum), so two launches sharing one word never move it backwards.
 namespace {
 __global__ void wait_value32_kernel(const unsigned* flag, unsigned value, long long ticks) {
     const long long t0 = (long long)wall_clock64();          // constant 100 MHz counter

@@ -937,10 +937,9 @@ extern "C" int i2l_sample_decode(const i2l_decoder_weights* w, const void* works
 
 namespace {
 // the residency signal of a launch that does NOT run a grouped kernel (other dimensions, row-per-workgroup request): its
-// workgroups need no partners, so "resident" is said at once -- a waiter never pays its time-out for a kernel choice
-__global__ void publish_value32_kernel(unsigned* flag, unsigned value) {
-    __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
+// workgroups need no partners, so "resident" is said at once -- a waiter never pays its time-out for a kernel choice;
+// like the grouped kernels it never moves the word backwards (publish_max32)
+__global__ void publish_value32_kernel(unsigned* flag, unsigned value) { publish_max32(flag, value); }
 
 int launch_decode(const i2l_decoder_weights* w, const void* workspace, int rows, int steps, const int32_t* tok0,
                   const int32_t* forced, const float* h0, const float* c0, float temperature, int select, int stop,

@@ -36,9 +36,18 @@ constexpr int GRP_STAT_FAILED = 0, GRP_STAT_GROUPS = 1, GRP_STAT_LOCAL = 2;
 // counts its group in status[GRP_STAT_GROUPS] once all members have answered the placement exchange, i.e. ARE RESIDENT; the
 // group that completes the count publishes resident_value at agent scope.  A stream that must not start before this
 // launch owns its CUs waits for the word (i2l_stream_wait_value32) -- a dependency, where r03 guessed with a 30 us delay.
+// The word is a wrapping sequence that several launches may share (decode streams > 1): publish_max32 only moves it FORWARD,
+// so a launch that assembles after a later one cannot take the word back and leave a waiter sitting out its time-out.
+__device__ __forceinline__ void publish_max32(unsigned* flag, unsigned value) {
+    unsigned old = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while ((int)(value - old) > 0 &&
+           !__hip_atomic_compare_exchange_strong(flag, &old, value, __ATOMIC_RELEASE, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT)) {
+    }
+}
 __device__ __forceinline__ void count_resident_group(unsigned* status, int n_groups, unsigned* flag, unsigned value) {
     const unsigned before = atomicAdd(status + GRP_STAT_GROUPS, 1u);
-    if (flag && before + 1u == (unsigned)n_groups) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    if (flag && before + 1u == (unsigned)n_groups) publish_max32(flag, value);
 }
 
 

@@ -175,7 +175,19 @@ class GreedyPipeline:
 
     def close(self) -> None:
         """Give the decoder workspaces of this pipeline's slots back (they live in the decoder's cache under this
-        pipeline's id); called by Predictor.predict_ids_stream when its stream ends, and on garbage collection."""
+        pipeline's id); called by Predictor.predict_ids_stream when its stream ends, and on garbage collection.
+        Batches still in flight are dropped (no fallback re-run) and waited for first: their decodes read and write the
+        slot workspaces and `_resident` on the decode stream, and the allocator must not hand those blocks out again
+        before they end.  Calling it again does nothing."""
+        inflight = getattr(self, "_inflight", None)
+        if inflight:
+            # the allocator records events of its own on these streams when a batch's tensors are freed (record_stream in
+            # submit), behind that batch's `done`: the streams themselves are synchronised, after the batches are dropped,
+            # so that close() leaves every one of them idle
+            inflight.clear()
+            for s in self.enc_streams + self.dec_streams + [self.copy_stream]:
+                if s is not None:
+                    s.synchronize()
         dec = getattr(getattr(self, "model", None), "decoder", None)
         if dec is not None and hasattr(dec, "release_slots"):
             dec.release_slots(id(self))
@@ -183,7 +195,7 @@ class GreedyPipeline:
     def __del__(self):
         try:
             self.close()
-        except Exception:
+        except Exception:                            # interpreter shutdown: torch or the HIP runtime may be gone already
             pass
 
     def _host_buffer(self, shape) -> torch.Tensor:

@@ -5,7 +5,9 @@ import os
 import numpy as np
 import torch
 
+from conftest import record
 from img2latex_amd import synth
+from img2latex_amd.model import Seq2SeqModel
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 START, END, PAD = synth.START, synth.END, synth.PAD
@@ -40,6 +42,51 @@ def torch_state_dict(name, device="cpu"):
 
 def images(cfg, batch=4, seed=1234, device="cpu"):
     return torch.from_numpy(synth.make_images(batch, cfg, seed=seed)).to(device)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# GPU parity checks shared by test_hip_parity.py and test_pipeline_headline.py
+# ---------------------------------------------------------------------------------------------------------------
+DEV = "cuda"
+
+
+def close(a, b, tol, what=None, absolute=False):
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    scale = 1.0 if absolute else max(1.0, float(np.abs(b).max()))
+    err = float(np.abs(a - b).max())
+    if what:
+        record(what + (" [abs]" if absolute else " [rel to max(1,|ref|)]"), err / scale)
+    assert err <= tol * scale, f"{what}: max err {err} > {tol} * {scale}"
+
+
+_MODELS = {}
+
+
+def model_for(name, sd_kw=None, cfg=None):
+    key = (name, repr(sd_kw))
+    if key not in _MODELS:
+        if cfg is None:
+            _, cfg, kw = load(name)
+            sd_kw = kw if sd_kw is None else sd_kw
+        m = Seq2SeqModel("cnn_lstm", cfg["vocab_size"], synth.encoder_params(cfg), synth.decoder_params(cfg))
+        m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in synth.make_state_dict(cfg, **sd_kw).items()})
+        _MODELS[key] = (m.to(DEV).eval(), cfg)
+    return _MODELS[key]
+
+
+def _margin_guard(got, ref_ids, margins, tol):
+    """ids must agree with the reference up to the first step whose reference top1-top2
+    margin is below tol (a fp32 near-tie, after which sequences legitimately diverge)."""
+    diverged = 0
+    for b in range(ref_ids.shape[0]):
+        ne = np.nonzero(got[b] != ref_ids[b, 1:1 + got.shape[1]])[0]
+        if ne.size:
+            t = int(ne[0])
+            assert margins[b, t] < tol, f"row {b} step {t}: ids differ at margin {margins[b, t]}"
+            diverged += 1
+    return diverged
 
 
 def padded_to_lists(arr, lens):

@@ -8,38 +8,13 @@ import torch
 
 import img2latex_oracle as O
 from conftest import record
-from helpers import ALL, BIG, END, SMALL, START, images, load, padded_to_lists, sample, torch_state_dict
+from helpers import (_MODELS, ALL, BIG, END, SMALL, START, _margin_guard, close, images, load, model_for, padded_to_lists,
+                     sample, torch_state_dict)
 from img2latex_amd import _lib, synth
 from img2latex_amd.model import Seq2SeqModel
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def close(a, b, tol, what=None, absolute=False):
-    a = np.asarray(a, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    scale = 1.0 if absolute else max(1.0, float(np.abs(b).max()))
-    err = float(np.abs(a - b).max())
-    if what:
-        record(what + (" [abs]" if absolute else " [rel to max(1,|ref|)]"), err / scale)
-    assert err <= tol * scale, f"{what}: max err {err} > {tol} * {scale}"
-
-
-_MODELS = {}
-
-
-def model_for(name, sd_kw=None, cfg=None):
-    key = (name, repr(sd_kw))
-    if key not in _MODELS:
-        if cfg is None:
-            _, cfg, kw = load(name)
-            sd_kw = kw if sd_kw is None else sd_kw
-        m = Seq2SeqModel("cnn_lstm", cfg["vocab_size"], synth.encoder_params(cfg), synth.decoder_params(cfg))
-        m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in synth.make_state_dict(cfg, **sd_kw).items()})
-        _MODELS[key] = (m.to(DEV).eval(), cfg)
-    return _MODELS[key]
 
 
 @pytest.mark.parametrize("name", ALL)
@@ -126,19 +101,6 @@ def test_sticky_stop_loop_vs_golden(name):
         r = [t for t in r if t >= 0]
         rows.append(r[: r.index(END)] if END in r else r)
     assert rows == padded_to_lists(d["g5_ids"], d["g5_len"])
-
-
-def _margin_guard(got, ref_ids, margins, tol):
-    """ids must agree with the reference up to the first step whose reference top1-top2
-    margin is below tol (a fp32 near-tie, after which sequences legitimately diverge)."""
-    diverged = 0
-    for b in range(ref_ids.shape[0]):
-        ne = np.nonzero(got[b] != ref_ids[b, 1:1 + got.shape[1]])[0]
-        if ne.size:
-            t = int(ne[0])
-            assert margins[b, t] < tol, f"row {b} step {t}: ids differ at margin {margins[b, t]}"
-            diverged += 1
-    return diverged
 
 
 @pytest.mark.parametrize("fname", ["primary_cfg2_clock", "primary_cfg2"])
@@ -665,11 +627,13 @@ def test_resnet_encoder_vs_oracle(model_name, hw):
     enc.eval()
 
 
+@pytest.mark.filterwarnings("error::RuntimeWarning")
 def test_predict_ids_stream_equals_predict_batch_ids():
     """Predictor.predict_ids_stream (GreedyPipeline with the Predictor's loop: argmax of softmax, sticky stop): batch by batch
     the lists predict_batch_ids returns -- on a tiny attention model (no grouped kernels: the pipeline's C call picks the
-    row-per-workgroup kernel) and at the primary dims (8-member co-resident decode; a row may leave the 4-member kernel's
-    ids only at an fp32 near-tie, judged by the reference fixture's margins); ragged last batch, order preserved."""
+    row-per-workgroup kernel) and at the primary dims (16-member co-resident decode; a row may leave the 4-member kernel's
+    ids only at an fp32 near-tie, judged by the reference fixture's margins); ragged last batch, order preserved; no grouped
+    decode times out (the pipeline's fallback warning is an error here)."""
     from img2latex_amd.training import Predictor, TokenTable
     for name, n_imgs, bs, T in (("tiny_l2_attn", 10, 4, 24), ("primary_cfg2_clock", 160, 64, 60)):
         d, cfg, sd_kw = load(name)
@@ -1093,11 +1057,13 @@ def test_group8_decode_ids_vs_reference(fname, members):
         assert bool((bad == -3).all())
 
 
+@pytest.mark.filterwarnings("error::RuntimeWarning")
 def test_coresident_pipeline_ids_vs_reference():
     """GreedyPipeline with the 8-member grouped decode (FLAG_DECODE_GROUP8) sharing every CU with the next batch's conv
     workgroups: six batches of BASELINE configs[1] (three distinct image sets, so that consecutive batches differ) through
     the two-stream pipeline -- every batch's ids against the reference's fixture (margin guard) for the fixture's images
-    and equal to the one-batch-at-a-time search for the others up to near-ties; nothing times out."""
+    and equal to the one-batch-at-a-time search for the others up to near-ties; nothing times out (the pipeline's fallback
+    warning is an error here)."""
     from img2latex_amd.pipeline import GreedyPipeline
     d, cfg, sd_kw = load("primary_cfg2")
     m, _ = model_for("primary_cfg2", sd_kw, cfg)
@@ -1198,8 +1164,8 @@ def test_pipeline_with_two_encoder_streams_cnn():
 def test_residency_signal_and_bounded_stream_wait():
     """i2l_greedy_decode_ex's residency signal + i2l_stream_wait_value32 (r04: GreedyPipeline's dependency between decode(i)
     and encoder(i + 1), where r03 had a 30 us delay kernel), through the C ABI:
-    the grouped kernels (4 and 8 members) publish the value once their groups are resident, an ungrouped launch publishes at
-    once, a launch with a silent member (forced time-out) never does; a wait on a published value returns at once, a wait
+    the grouped kernels (4, 8 and 16 members) publish the value once their groups are resident, an ungrouped launch publishes
+    at once, a launch with a silent member (forced time-out) never does; a wait on a published value returns at once, a wait
     on a value that never comes returns after its bound; and in a traced pipeline every encoder starts after the decode
     launch it was held for, with identical ids."""
     import ctypes
@@ -1213,23 +1179,25 @@ def test_residency_signal_and_bounded_stream_wait():
     with torch.no_grad():
         enc = m.encoder(x)
         base = m.greedy_ids(enc, START, END, 40)[0].cpu()
-        for n, (fl, rows_per_wg) in enumerate([(0, 0), (_lib.FLAG_DECODE_GROUP8, 0), (0, 1)], start=1):
+        for n, (fl, rows_per_wg) in enumerate([(0, 0), (_lib.FLAG_DECODE_GROUP8, 0), (0, 1), (_lib.FLAG_DECODE_GROUP16, 0)],
+                                              start=1):
             ids, _, _ = m.decoder.run_steps(enc, 40, torch.full((64,), START, dtype=torch.int32, device=DEV), flags=fl,
                                             rows_per_workgroup=rows_per_wg, resident=(flag, 100 + n))
             torch.cuda.synchronize()
             assert int(flag.item()) == 100 + n, (fl, rows_per_wg)
             assert int((ids.cpu() != base).any(dim=1).sum()) <= 2           # the signal does not touch the results
-        bad = _lib.FLAG_DECODE_GROUP8 | _lib.FLAG_TEST_DROP_MEMBER | _lib.FLAG_TEST_SHORT_TIMEOUT
-        ids, _, _ = m.decoder.run_steps(enc, 40, torch.full((64,), START, dtype=torch.int32, device=DEV), flags=bad,
-                                        resident=(flag, 999))
-        torch.cuda.synchronize()
-        assert bool((ids == -3).all()) and int(flag.item()) == 103           # a group that never assembled says nothing
-    # the wait: satisfied (wrapping compare: 103 - 50 >= 0), then a value that never comes
+        for group in (_lib.FLAG_DECODE_GROUP8, _lib.FLAG_DECODE_GROUP16):
+            bad = group | _lib.FLAG_TEST_DROP_MEMBER | _lib.FLAG_TEST_SHORT_TIMEOUT
+            ids, _, _ = m.decoder.run_steps(enc, 40, torch.full((64,), START, dtype=torch.int32, device=DEV), flags=bad,
+                                            resident=(flag, 999))
+            torch.cuda.synchronize()
+            assert bool((ids == -3).all()) and int(flag.item()) == 104, group    # a group that never assembled says nothing
+    # the wait: satisfied (wrapping compare: 104 - 50 >= 0), then a value that never comes
     s = torch.cuda.Stream()
     assert L.i2l_stream_wait_value32(flag.data_ptr(), 50, 5000.0, s.cuda_stream) == 0
     s.synchronize()
     t0 = time.perf_counter()
-    assert L.i2l_stream_wait_value32(flag.data_ptr(), 104, 3000.0, s.cuda_stream) == 0
+    assert L.i2l_stream_wait_value32(flag.data_ptr(), 105, 3000.0, s.cuda_stream) == 0
     s.synchronize()
     waited = time.perf_counter() - t0
     assert 2.5e-3 <= waited <= 0.5, waited
@@ -1259,18 +1227,20 @@ def test_residency_signal_and_bounded_stream_wait():
         pipe.close()
 
 
-def test_pipeline_falls_back_when_the_grouped_decode_times_out():
+@pytest.mark.parametrize("group", [_lib.FLAG_DECODE_GROUP8, _lib.FLAG_DECODE_GROUP16], ids=["group8", "group16"])
+def test_pipeline_falls_back_when_the_grouped_decode_times_out(group):
     """A batch whose grouped decode timed out (forced: silent member + 2 ms limits) is decoded again on the
-    row-per-workgroup kernel inside GreedyPipeline.collect(): same ids as the healthy pipeline, one warning per batch."""
+    row-per-workgroup kernel inside GreedyPipeline.collect(): same ids as the healthy pipeline, one warning per batch;
+    for the 8-member and the 16-member (bench.py's) grouped decode."""
     from img2latex_amd.pipeline import GreedyPipeline
     d, cfg, sd_kw = load("primary_cfg2_clock")
     m, _ = model_for("primary_cfg2_clock", sd_kw, cfg)
     x = torch.from_numpy(synth.make_images(64, cfg, seed=1234)).to(DEV)
-    good = GreedyPipeline(m, START, END, 60, rows_per_workgroup=0, decode_flags=_lib.FLAG_DECODE_GROUP8)
+    good = GreedyPipeline(m, START, END, 60, rows_per_workgroup=0, decode_flags=group)
     good.submit(x)
     want = good.collect().clone()
     bad = GreedyPipeline(m, START, END, 60, rows_per_workgroup=0,
-                         decode_flags=_lib.FLAG_DECODE_GROUP8 | _lib.FLAG_TEST_DROP_MEMBER | _lib.FLAG_TEST_SHORT_TIMEOUT)
+                         decode_flags=group | _lib.FLAG_TEST_DROP_MEMBER | _lib.FLAG_TEST_SHORT_TIMEOUT)
     bad.submit(x)
     bad.submit(x)
     with pytest.warns(RuntimeWarning):
