@@ -21,7 +21,8 @@
 //   E  logits of this member's 128 columns for the 12 slots
 //   F  per slot: local (max, sum exp) and top K -> published with tag step + 1
 // All four members hold the same per-image state and take the same decisions from the same data; member (image & 3)
-// writes the history and the result.  Exchange, placement check, progress argument and timeouts: decode_group.inc.h.
+// writes the history and the result.  Exchange: decode_group.inc.h; seating, placement check, progress argument and
+// time-outs: group_common.inc.h.
 // A timed-out poll ends the group with len_out = -3 (i2l_beam_decode is then re-run with I2L_FLAG_NO_GROUP).
 
 constexpr int BG_NP = 3;                         // passes of 4 row slots
@@ -131,8 +132,8 @@ __global__ __launch_bounds__(GNT) void beam_group_kernel(BeamGroupParams p) {
 
     const StepWeights& w = p.w;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int within = blockIdx.x & 31;
-    const int group = (blockIdx.x >> 5) * 8 + (within & 7), m = within >> 3;
+    const GroupSeat seat = group_seat<GQ>();
+    const int group = seat.group, m = seat.m;
     if (group >= p.n_groups) return;
     const int T = p.T, V = w.V;
     const int img0 = group * IPG;
@@ -169,31 +170,10 @@ __global__ __launch_bounds__(GNT) void beam_group_kernel(BeamGroupParams p) {
     if (tid == 0) { flg[0] = 0; flg[2] = 0; }
     u64_t* xg = p.xchg + (size_t)group * 2 * GQ * BG_GRAN;
 
-    // placement (see decode_group_kernel)
+    // placement (group_common.inc.h); beam search keeps no placement statistics
     if (wave == 0) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 0xFu;
-        if (lane == 0 && !(p.opts.drop_member && m == 3))      // test hook: member 3 stays silent, its peers time out
-            store_granule(xg + (size_t)m * BG_GRAN + BG_GRAN_X, granule(0xC0DEu, __uint_as_float(xcc)), false);
-        const int pq = (lane & 3) + ((lane & 3) >= m ? 1 : 0);
-        u64_t pv = 0;
-        bool bad = false;
-        long long t_start = 0;
-        unsigned spins = 0;
-        for (;;) {
-            bool ok = true;
-            if (lane < 3) { pv = load_granule(xg + (size_t)pq * BG_GRAN + BG_GRAN_X); ok = (unsigned)(pv >> 32) == 0xC0DEu; }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 255u) == 0) {
-                const long long now = (long long)wall_clock64();
-                if (t_start == 0) t_start = now;
-                else if (now - t_start > p.opts.limit_first) { bad = true; break; }
-            }
-        }
-        const bool all_same = __all(lane >= 3 || (unsigned)pv == xcc);
-        if (lane == 0) { flg[1] = (all_same && !bad) ? 1 : 0; if (bad) flg[0] = 1; }
+        const Placement pl = group_placement<GQ>(xg, BG_GRAN, BG_GRAN_X, m, p.opts);
+        if (lane == 0) { flg[1] = (pl.one_xcd && !pl.timed_out) ? 1 : 0; if (pl.timed_out) flg[0] = 1; }
     }
     __syncthreads();
     const bool local = flg[1] != 0 && !p.opts.agent_scope;
@@ -203,13 +183,7 @@ __global__ __launch_bounds__(GNT) void beam_group_kernel(BeamGroupParams p) {
     for (int pp = 0; pp < BG_NP; ++pp) c_new[pp] = 0.f;
     bool failed = false;
     int t = 0;
-#ifdef I2L_GROUP_STAMPS
-    long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long st_last = (long long)wall_clock64();
-#define I2L_STAMP(i) do { const long long n_ = (long long)wall_clock64(); st_acc[i] += n_ - st_last; st_last = n_; } while (0)
-#else
-#define I2L_STAMP(i) do { } while (0)
-#endif
+    I2L_STAMPS_BEGIN;
     for (;; ++t) {
         // candidates of step t-1 (wave w merges slots w and w + 8): requested now, in flight during A
         //   lanes 0..4K-1: candidate j of member qm; lanes 32..35: local max of member lane-32; 36..39: local sum
@@ -281,17 +255,12 @@ __global__ __launch_bounds__(GNT) void beam_group_kernel(BeamGroupParams p) {
                 if (slot >= BG_S) break;
                 u64_t gv = b_gv[half];
                 bool bad = false;
-                long long t_start = 0;
-                unsigned spins = 0;
+                PollClock clk;
                 for (;;) {
                     const bool ok = !b_act || (unsigned)(gv >> 48) == epoch;
                     if (__all(ok)) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++spins & 255u) == 0) {
-                        const long long now = (long long)wall_clock64();
-                        if (t_start == 0) t_start = now;
-                        else if (now - t_start > p.opts.limit_step) { bad = true; break; }
-                    }
+                    bad = clk.expired(p.opts.limit_step);
+                    if (bad) break;
                     if (b_act) {
                         gv = load_granule(b_src + slot * BG_CW);
                         if (half == 0 && wave + 8 < BG_S) b_gv[1] = load_granule(b_src + (wave + 8) * BG_CW);
@@ -444,19 +413,13 @@ __global__ __launch_bounds__(GNT) void beam_group_kernel(BeamGroupParams p) {
                 const int pi = idx / BG_GRAN_H, gi = idx - pi * BG_GRAN_H;
                 return xslot + (size_t)(pi + (pi >= m ? 1 : 0)) * BG_GRAN + gi;
             };
-            long long t_start = 0;
-            unsigned spins = 0;
+            PollClock clk;
             for (;;) {
                 bool ok = true;
 #pragma unroll
                 for (int i = 0; i < PER; ++i) { gr[i] = load_granule(gsrc(i)); ok = ok && (unsigned)(gr[i] >> 32) == epoch; }
                 if (ok) break;
-                __builtin_amdgcn_s_sleep(1);
-                if ((++spins & 255u) == 0) {
-                    const long long now = (long long)wall_clock64();
-                    if (t_start == 0) t_start = now;
-                    else if (now - t_start > p.opts.limit_step) { failed = true; break; }
-                }
+                if (clk.expired(p.opts.limit_step)) { failed = true; break; }
             }
             I2L_STAMP(4);
             // h_s was last read in A of this step, before the barriers of B (t > 0) or the start-up barrier (t = 0)
@@ -591,11 +554,10 @@ __global__ __launch_bounds__(GNT) void beam_group_kernel(BeamGroupParams p) {
     }
 #ifdef I2L_GROUP_STAMPS
     if (tid == 0 && blockIdx.x < 32) {
-        for (int i = 0; i < 8; ++i) p.status[8 + blockIdx.x * 8 + i] = (unsigned)st_acc[i];
+        for (int i = 0; i < 8; ++i) p.status[8 + blockIdx.x * 8 + i] = (unsigned)st_.acc[i];
         if (blockIdx.x == 0) p.status[4] = (unsigned)t;
     }
 #endif
-#undef I2L_STAMP
     if (failed) {
         if (tid == 0) atomicOr(p.status, 1u);
         if (tid < IPG && img0 + tid < p.images && m == ((img0 + tid) & 3)) p.len_out[img0 + tid] = -3;

@@ -782,7 +782,7 @@ Layout make_layout(int rows, int V, int E, int H, int L) {
         size_t most = 0;
         for (int i = 0; i < GROUP_VARIANTS; ++i) {
             const GroupVariant g = group_variant(i);
-            const size_t x = (size_t)i2l_cdiv(i2l_cdiv(rows, g.rows), 8) * 8 * g.xchg_per_group;
+            const size_t x = group_xchg_bytes(i2l_cdiv(rows, g.rows), g.xchg_per_group);
             most = x > most ? x : most;
         }
         o.xchg_bytes = GROUP_STATUS_BYTES + most;
@@ -990,7 +990,7 @@ int launch_decode(const i2l_decoder_weights* w, const void* workspace, int rows,
             if (!i2l_lds_attr(reinterpret_cast<const void*>(g.kernel), g.lds, attr[i])) continue;   // try the next one
             if (!(flags & I2L_FLAG_DECODE_REGION_CLEARED) && hipMemsetAsync(xb, 0, lo.xchg_bytes, gs) != hipSuccess) return I2L_ERR_LAUNCH;
             gp.n_groups = i2l_cdiv(rows, g.rows);
-            hipLaunchKernelGGL(g.kernel, dim3(i2l_cdiv(gp.n_groups, 8) * 8 * g.rows), dim3(g.threads), g.lds, gs, gp);
+            hipLaunchKernelGGL(g.kernel, dim3(group_grid(gp.n_groups, g.rows)), dim3(g.threads), g.lds, gs, gp);
             I2L_CHECK_LAUNCH();
             return I2L_OK;
         }
@@ -1071,7 +1071,7 @@ int launch_beam_group(const BeamGroupParams& p, hipStream_t s) {
     static_assert(lds <= 160 * 1024, "beam_group_kernel LDS");
     static std::atomic<unsigned> attr{0};
     if (!i2l_lds_attr(reinterpret_cast<const void*>(&beam_group_kernel<K>), lds, attr)) return I2L_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(beam_group_kernel<K>, dim3(i2l_cdiv(p.n_groups, 8) * 32), dim3(GNT), lds, s, p);
+    hipLaunchKernelGGL(beam_group_kernel<K>, dim3(group_grid(p.n_groups, GQ)), dim3(GNT), lds, s, p);
     I2L_CHECK_LAUNCH();
     return I2L_OK;
 }
@@ -1081,7 +1081,7 @@ extern "C" size_t i2l_beam_workspace_bytes(int images, int beam, int hidden, int
     if (images <= 0 || beam <= 0 || beam > I2L_MAX_BEAM || steps <= 0) return 0;
     size_t b = beam_hist_bytes(images, beam, steps);
     if (beam_group_ok(beam, hidden, layers))
-        b += GROUP_STATUS_BYTES + (size_t)i2l_cdiv(beam_groups(images, beam), 8) * 8 * BEAM_XCHG_PER_GROUP;
+        b += GROUP_STATUS_BYTES + group_xchg_bytes(beam_groups(images, beam), BEAM_XCHG_PER_GROUP);
     return b;
 }
 
@@ -1112,7 +1112,7 @@ extern "C" int i2l_beam_decode(const i2l_decoder_weights* w, const void* workspa
         gp.parhist = gp.tokhist + (size_t)images * steps * beam;
         gp.seq_out = seq_out; gp.len_out = len_out; gp.score_out = score_out;
         char* xb = static_cast<char*>(beam_workspace) + beam_hist_bytes(images, beam, steps);
-        const size_t xbytes = GROUP_STATUS_BYTES + (size_t)i2l_cdiv(gp.n_groups, 8) * 8 * BEAM_XCHG_PER_GROUP;
+        const size_t xbytes = GROUP_STATUS_BYTES + group_xchg_bytes(gp.n_groups, BEAM_XCHG_PER_GROUP);
         gp.status = reinterpret_cast<unsigned*>(xb);
         gp.xchg = reinterpret_cast<u64_t*>(xb + GROUP_STATUS_BYTES);
         gp.opts = group_opts(steps, flags);

@@ -29,14 +29,8 @@
 // a member overwrites a slot two steps later, after it has consumed from every peer data that the peer published
 // after reading that slot.  The granule block is zeroed by a memset node before every launch.
 //
-// Progress: the members of a group are workgroups 32a + x + 8k (k = 0..3) -- one XCD under round-robin placement
-// (speed only) -- and workgroups are dispatched in index order, so on a GPU with at least the 32 CUs of one grid
-// slice free some complete group is resident and runs to its end, freeing its CUs for the next.  That is an
-// assumption about the dispatcher and about what else runs on the device, not something HIP promises (the launch
-// is not cooperative): with fewer CUs free every resident workgroup may be waiting for a member that is not, so
-// EVERY poll is bounded by a wall-clock limit: on expiry the workgroup raises status[0], fills its ids with -3 (and
-// its logits with NaN) and exits, its peers follow by their own limits, and the host wrapper reports the failure
-// and re-runs on the row-per-workgroup kernel; the GPU is never left spinning.
+// Seating, progress argument, bounded polls (PollClock), placement exchange: group_common.inc.h.  On a time-out the
+// workgroup fills its ids with -3 (and its logits with NaN).
 // Memory model: the granule stores are relaxed atomics at AGENT scope (sc1, write-through) and the polls agent-scope
 // loads -- conformant HSA.  When the four members measure themselves on one XCD the stores drop to WORKGROUP scope
 // (a plain store that gfx950's write-through L1 forwards to the XCD's L2, where the peers' L1-bypassing polls find
@@ -84,8 +78,8 @@ __global__ __launch_bounds__(GNT) void decode_group_kernel(GroupParams p) {
 
     const StepWeights& w = p.w;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int within = blockIdx.x & 31;
-    const int group = (blockIdx.x >> 5) * 8 + (within & 7), m = within >> 3;
+    const GroupSeat seat = group_seat<GQ>();
+    const int group = seat.group, m = seat.m;
     if (group >= p.n_groups) return;
     const int B = p.B, T = p.T, V = w.V;
     const int row0 = group * GQ;
@@ -122,40 +116,15 @@ __global__ __launch_bounds__(GNT) void decode_group_kernel(GroupParams p) {
     const bool own_row = row0 + m < B;                      // this member writes the ids of row m
     int32_t* ids_row = (p.ids && own_row) ? p.ids + (size_t)(row0 + m) * T : nullptr;
     float* lrow = (p.logits && row0 + l_row < B && l_v < V) ? p.logits + (size_t)(row0 + l_row) * T * V + l_v : nullptr;
-    // Placement: are the four members on one XCD?  Each publishes its XCC id (sc1, seen from anywhere); equal ids
-    // switch the granule stores to the L2-local flavour.  Measured, never assumed: correctness does not depend on it
-    // (if a member times out here it fails the launch like any other poll).
+    // placement: are the four members on one XCD?  (equal ids switch the granule stores to the L2-local flavour)
     __syncthreads();                                        // the LDS initialisation above
     if (wave == 0) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 0xFu;
-        if (lane == 0 && !(p.opts.drop_member && m == 3))      // test hook: member 3 stays silent, its peers time out
-            store_granule(xg + (size_t)m * GRAN + GRAN_X, granule(0xC0DEu, __uint_as_float(xcc)), false);
-        const int pq = (lane & 3) + ((lane & 3) >= m ? 1 : 0);
-        u64_t pv = 0;
-        bool bad = false;
-        long long t_start = 0;
-        unsigned spins = 0;
-        for (;;) {
-            bool ok = true;
-            if (lane < 3) { pv = load_granule(xg + (size_t)pq * GRAN + GRAN_X); ok = (unsigned)(pv >> 32) == 0xC0DEu; }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 255u) == 0) {
-                const long long now = (long long)wall_clock64();
-                if (t_start == 0) t_start = now;
-                else if (now - t_start > p.opts.limit_first) { bad = true; break; }
-            }
-        }
-        const bool all_same = __all(lane >= 3 || (unsigned)pv == xcc);
+        const Placement pl = group_placement<GQ>(xg, GRAN, GRAN_X, m, p.opts);
         if (lane == 0) {
-            cnt_s[3] = (all_same && !bad) ? 1 : 0;
-            if (bad) cnt_s[2] = 1;
-            if (m == 0 && !bad) {                            // placement statistics of the launch (read by the host on request)
-                count_resident_group(p.status, p.n_groups, p.resident_flag, p.resident_value);
-                if (all_same && !p.opts.agent_scope) atomicAdd(p.status + GRP_STAT_LOCAL, 1u);
-            }
+            cnt_s[3] = (pl.one_xcd && !pl.timed_out) ? 1 : 0;
+            if (pl.timed_out) cnt_s[2] = 1;
+            if (m == 0 && !pl.timed_out)
+                report_group(p.status, p.n_groups, p.resident_flag, p.resident_value, pl.one_xcd && !p.opts.agent_scope);
         }
     }
     __syncthreads();
@@ -169,13 +138,7 @@ __global__ __launch_bounds__(GNT) void decode_group_kernel(GroupParams p) {
 
     int t = 0;
     bool failed = cnt_s[2] != 0;
-#ifdef I2L_GROUP_STAMPS
-    long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long st_last = (long long)wall_clock64();
-#define I2L_STAMP(i) do { const long long n_ = (long long)wall_clock64(); st_acc[i] += n_ - st_last; st_last = n_; } while (0)
-#else
-#define I2L_STAMP(i) do { } while (0)
-#endif
+    I2L_STAMPS_BEGIN;
     for (; !failed; ++t) {
         // ---- A. token-independent part of the gates of step t: sum_k h(t-1)[k] Whh[k][.]; on the way, the tokens chosen
         //         at step t-1: every wave polls the 16 candidate granules {member q, row r} = lane 4q + r itself
@@ -242,18 +205,12 @@ __global__ __launch_bounds__(GNT) void decode_group_kernel(GroupParams p) {
         //         which every wave leaves together (uniform barrier use on the failure path too)
         bool bail = false;
         if (!have) {
-            long long t_start = 0;
-            unsigned spins = 0;
+            PollClock clk;
             for (;;) {
                 issue();
                 check();
                 if (have) break;
-                __builtin_amdgcn_s_sleep(1);
-                if ((++spins & 255u) == 0) {
-                    const long long now = (long long)wall_clock64();
-                    if (t_start == 0) t_start = now;
-                    else if (now - t_start > p.opts.limit_step) { bail = true; break; }
-                }
+                if (clk.expired(p.opts.limit_step)) { bail = true; break; }
             }
             if (bail) cnt_s[2] = 1;
         }
@@ -309,18 +266,12 @@ __global__ __launch_bounds__(GNT) void decode_group_kernel(GroupParams p) {
             const int qa = tid < 256 ? 0 : 2;
             const u64_t* pa_ = slot + (size_t)(qa + (qa >= m ? 1 : 0)) * GRAN + gi;
             const u64_t* pb_ = slot + (size_t)(1 + (1 >= m ? 1 : 0)) * GRAN + gi;
-            long long t_start = 0;
-            unsigned spins = 0;
+            PollClock clk;
             for (;;) {
                 gr[0] = load_granule(pa_);
                 gr[1] = tid < 256 ? load_granule(pb_) : gr[0];
                 if ((unsigned)(gr[0] >> 32) == epoch && (unsigned)(gr[1] >> 32) == epoch) break;
-                __builtin_amdgcn_s_sleep(1);
-                if ((++spins & 255u) == 0) {
-                    const long long now = (long long)wall_clock64();
-                    if (t_start == 0) t_start = now;
-                    else if (now - t_start > p.opts.limit_step) { cnt_s[2] = 1; break; }
-                }
+                if (clk.expired(p.opts.limit_step)) { cnt_s[2] = 1; break; }
             }
             I2L_STAMP(3);
             hcur[(qa + (qa >= m ? 1 : 0)) * 256 + gi] = __uint_as_float((unsigned)gr[0]);
@@ -398,16 +349,9 @@ __global__ __launch_bounds__(GNT) void decode_group_kernel(GroupParams p) {
         I2L_STAMP(6);
     }
 #ifdef I2L_GROUP_STAMPS
-    if (tid == 0 && blockIdx.x < 32) for (int i = 0; i < 8; ++i) p.status[8 + blockIdx.x * 8 + i] = (unsigned)st_acc[i];
+    if (tid == 0 && blockIdx.x < 32) for (int i = 0; i < 8; ++i) p.status[8 + blockIdx.x * 8 + i] = (unsigned)st_.acc[i];
 #endif
-    if (failed) {
-        // loud failure: ids -3 (checked by the host wrappers) and NaN logits (a caller that asked for logits only --
-        // the validation forward -- gets a NaN loss instead of a partly written tensor)
-        if (lane == 0) atomicOr(p.status, 1u);
-        if (ids_row) for (int tt = tid; tt < T; tt += GNT) ids_row[tt] = -3;
-        if (lrow) for (int tt = 0; tt < T; ++tt) lrow[(size_t)tt * V] = __builtin_nanf("");
-        return;
-    }
-    if (ids_row) for (int tt = t + tid; tt < T; tt += GNT) ids_row[tt] = -1;   // steps never executed (sticky stop)
+    // loud failure: NaN logits too (a caller that asked for logits only -- the validation forward -- gets a NaN loss
+    // instead of a partly written tensor)
+    greedy_finish<GNT>(ids_row, failed, t, T, p.status, lrow, V);
 }
-#undef I2L_STAMP

@@ -34,8 +34,8 @@ __global__ __launch_bounds__(G8NT) void decode_group8_kernel(GroupParams p) {
 
     const StepWeights& w = p.w;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int within = blockIdx.x & 63;
-    const int group = (blockIdx.x >> 6) * 8 + (within & 7), m = within >> 3;
+    const GroupSeat seat = group_seat<G8Q>();
+    const int group = seat.group, m = seat.m;
     if (group >= p.n_groups) return;
     const int B = p.B, T = p.T, V = w.V;
     const int row0 = group * G8Q;
@@ -72,35 +72,12 @@ __global__ __launch_bounds__(G8NT) void decode_group8_kernel(GroupParams p) {
 
     __syncthreads();
     if (wave == 0) {                                        // placement: are the eight members on one XCD?
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 0xFu;
-        if (lane == 0 && !(p.opts.drop_member && m == 3))
-            store_granule(xg + (size_t)m * G8GRAN + G8GRAN_X, granule(0xC0DEu, __uint_as_float(xcc)), false);
-        const int pq = (lane & 7) + ((lane & 7) >= m ? 1 : 0);
-        u64_t pv = 0;
-        bool bad = false;
-        long long t_start = 0;
-        unsigned spins = 0;
-        for (;;) {
-            bool ok = true;
-            if (lane < 7) { pv = load_granule(xg + (size_t)pq * G8GRAN + G8GRAN_X); ok = (unsigned)(pv >> 32) == 0xC0DEu; }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 255u) == 0) {
-                const long long now = (long long)wall_clock64();
-                if (t_start == 0) t_start = now;
-                else if (now - t_start > p.opts.limit_first) { bad = true; break; }
-            }
-        }
-        const bool all_same = __all(lane >= 7 || (unsigned)pv == xcc);
+        const Placement pl = group_placement<G8Q>(xg, G8GRAN, G8GRAN_X, m, p.opts);
         if (lane == 0) {
-            cnt_s[3] = (all_same && !bad) ? 1 : 0;
-            if (bad) cnt_s[2] = 1;
-            if (m == 0 && !bad) {
-                count_resident_group(p.status, p.n_groups, p.resident_flag, p.resident_value);
-                if (all_same && !p.opts.agent_scope) atomicAdd(p.status + GRP_STAT_LOCAL, 1u);
-            }
+            cnt_s[3] = (pl.one_xcd && !pl.timed_out) ? 1 : 0;
+            if (pl.timed_out) cnt_s[2] = 1;
+            if (m == 0 && !pl.timed_out)
+                report_group(p.status, p.n_groups, p.resident_flag, p.resident_value, pl.one_xcd && !p.opts.agent_scope);
         }
     }
     __syncthreads();
@@ -174,18 +151,12 @@ __global__ __launch_bounds__(G8NT) void decode_group8_kernel(GroupParams p) {
         // ---- B. wait for the tokens if they are not there yet (uniform exit on a time-out: see decode_group_kernel)
         bool bail = false;
         if (!have) {
-            long long t_start = 0;
-            unsigned spins = 0;
+            PollClock clk;
             for (;;) {
                 issue();
                 check();
                 if (have) break;
-                __builtin_amdgcn_s_sleep(1);
-                if ((++spins & 255u) == 0) {
-                    const long long now = (long long)wall_clock64();
-                    if (t_start == 0) t_start = now;
-                    else if (now - t_start > p.opts.limit_step) { bail = true; break; }
-                }
+                if (clk.expired(p.opts.limit_step)) { bail = true; break; }
             }
             if (bail) cnt_s[2] = 1;
         }
@@ -235,8 +206,7 @@ __global__ __launch_bounds__(G8NT) void decode_group8_kernel(GroupParams p) {
             const u64_t* src[7];
 #pragma unroll
             for (int q = 0; q < 7; ++q) src[q] = slot + (size_t)(q + (q >= m ? 1 : 0)) * G8GRAN + tid;
-            long long t_start = 0;
-            unsigned spins = 0;
+            PollClock clk;
             for (;;) {
                 bool ok = true;
 #pragma unroll
@@ -244,12 +214,7 @@ __global__ __launch_bounds__(G8NT) void decode_group8_kernel(GroupParams p) {
 #pragma unroll
                 for (int q = 0; q < 7; ++q) ok = ok && (unsigned)(gr[q] >> 32) == epoch;
                 if (ok) break;
-                __builtin_amdgcn_s_sleep(1);
-                if ((++spins & 255u) == 0) {
-                    const long long now = (long long)wall_clock64();
-                    if (t_start == 0) t_start = now;
-                    else if (now - t_start > p.opts.limit_step) { cnt_s[2] = 1; break; }
-                }
+                if (clk.expired(p.opts.limit_step)) { cnt_s[2] = 1; break; }
             }
 #pragma unroll
             for (int q = 0; q < 7; ++q) hcur[(q + (q >= m ? 1 : 0)) * 256 + tid] = __uint_as_float((unsigned)gr[q]);
@@ -321,10 +286,5 @@ __global__ __launch_bounds__(G8NT) void decode_group8_kernel(GroupParams p) {
             if (lane == 0) cnt_s[par ^ 1] = 0;
         }
     }
-    if (failed) {
-        if (lane == 0) atomicOr(p.status, 1u);
-        if (ids_row) for (int tt = tid; tt < T; tt += G8NT) ids_row[tt] = -3;
-        return;
-    }
-    if (ids_row) for (int tt = t + tid; tt < T; tt += G8NT) ids_row[tt] = -1;
+    greedy_finish<G8NT>(ids_row, failed, t, T, p.status);
 }

@@ -1,5 +1,6 @@
-// Helpers shared by the grouped persistent kernels (decode_group.inc.h, train_group.inc.h): tagged-granule
-// exchange between the workgroups of a group, DPP reduce-scatter, packed-FMA tiles, arg-max keys.
+// Helpers shared by the grouped persistent kernels (decode_group*.inc.h, beam_group.inc.h, train_group.inc.h): seating,
+// bounded polls, placement exchange, tagged-granule exchange between the workgroups of a group, greedy ids epilogue,
+// phase stamps, DPP reduce-scatter, packed-FMA tiles, arg-max keys.
 // Included inside each translation unit's anonymous namespace.
 #pragma once
 typedef unsigned long long u64_t;
@@ -51,6 +52,43 @@ __device__ __forceinline__ void count_resident_group(unsigned* status, int n_gro
 }
 
 
+// Seating of a grouped launch with Q members per group: the grid is cut into slices of 8 Q workgroups, and slice a holds
+// groups 8a .. 8a + 7; member m of group 8a + x is workgroup 8Qa + x + 8m.
+// Progress: a group's members are 8 block ids apart -- one XCD under round-robin placement (speed only) -- and workgroups
+// are dispatched in index order, so on a GPU with at least the 8Q CUs of one grid slice free some complete group is
+// resident and runs to its end, freeing its CUs for the next.  That is an assumption about the dispatcher and about what
+// else runs on the device, not something HIP promises (the launch is not cooperative): with fewer CUs free every resident
+// workgroup may be waiting for a member that is not, so EVERY poll is bounded by a wall-clock limit (PollClock): on expiry
+// the workgroup raises status[0], marks its outputs as failed and exits, its peers follow by their own limits, and the
+// host wrapper reports the failure and re-runs on the row-per-workgroup kernel; the GPU is never left spinning.
+struct GroupSeat {
+    int group, m;
+};
+template <int Q>
+__device__ __forceinline__ GroupSeat group_seat() {
+    static_assert(Q == 4 || Q == 8 || Q == 16, "members per group");
+    const int within = blockIdx.x & (8 * Q - 1);
+    return {(int)(blockIdx.x / (8 * Q)) * 8 + (within & 7), within >> 3};
+}
+// workgroups of a launch of n_groups groups with q members (whole slices; the surplus workgroups return at once)
+__host__ __device__ constexpr int group_grid(int n_groups, int q) { return (n_groups + 7) / 8 * 8 * q; }
+// exchange bytes of such a launch: one region per group of the grid
+constexpr size_t group_xchg_bytes(int n_groups, size_t per_group) { return (size_t)group_grid(n_groups, 1) * per_group; }
+
+// Wall clock of one bounded poll: every call sleeps once; every 256th call reads the 100 MHz clock, the first reading
+// starts the limit and expired() reports true once `limit` ticks have passed since then.
+struct PollClock {
+    long long t_start = 0;
+    unsigned spins = 0;
+    __device__ __forceinline__ bool expired(long long limit) {
+        __builtin_amdgcn_s_sleep(1);
+        if ((++spins & 255u) != 0) return false;
+        const long long now = (long long)wall_clock64();
+        if (t_start == 0) { t_start = now; return false; }
+        return now - t_start > limit;
+    }
+};
+
 // local == false: sc1 store (write-through to memory, seen from every XCD).  local == true (all four members were
 // found on ONE XCD): sc0 store, the line stays in that XCD's L2 where the peers' sc1 loads (L1 bypassed) find it --
 // an L2 round trip instead of a memory one.
@@ -67,6 +105,77 @@ __device__ __forceinline__ u64_t granule(unsigned tag, float v) { return ((u64_t
 __device__ __forceinline__ u64_t load_granule(const u64_t* g) {
     return __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// Placement exchange, run by the 64 lanes of wave 0: are the Q members on one XCD?  Each publishes its XCC id in the
+// granule at xg[m * gran + xslot] (sc1, seen from anywhere) and polls its Q - 1 peers' under limit_first.  Measured,
+// never assumed: equal ids let the caller switch the granule stores to the L2-local flavour, and correctness does not
+// depend on it (a member that times out here fails the launch like any other poll).  drop_member (test hook): member 3
+// stays silent, its peers time out.  No LDS, no barrier: the caller's other waves may work meanwhile.
+struct Placement {
+    bool timed_out, one_xcd;
+};
+template <int Q>
+__device__ __forceinline__ Placement group_placement(u64_t* xg, int gran, int xslot, int m, const GroupOpts& o) {
+    const int lane = threadIdx.x & 63;
+    unsigned xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    xcc &= 0xFu;
+    if (lane == 0 && !(o.drop_member && m == 3))
+        store_granule(xg + (size_t)m * gran + xslot, granule(0xC0DEu, __uint_as_float(xcc)), false);
+    const int pq = (lane & (Q - 1)) + ((lane & (Q - 1)) >= m ? 1 : 0);
+    u64_t pv = 0;
+    bool bad = false;
+    PollClock clk;
+    for (;;) {
+        bool ok = true;
+        if (lane < Q - 1) { pv = load_granule(xg + (size_t)pq * gran + xslot); ok = (unsigned)(pv >> 32) == 0xC0DEu; }
+        if (__all(ok)) break;
+        if (clk.expired(o.limit_first)) { bad = true; break; }
+    }
+    return {bad, __all(lane >= Q - 1 || (unsigned)pv == xcc) != 0};
+}
+// Placement statistics of a greedy decode launch, reported by member 0 once its peers answered: the group counts as
+// resident (residency signal) and, when its members share one XCD and the stores are L2-local, in GRP_STAT_LOCAL.
+// Beam search and training do not count.
+__device__ __forceinline__ void report_group(unsigned* status, int n_groups, unsigned* flag, unsigned value, bool local) {
+    count_resident_group(status, n_groups, flag, value);
+    if (local) atomicAdd(status + GRP_STAT_LOCAL, 1u);
+}
+
+// Greedy decode epilogue of a workgroup of NT threads: after a failure status[0] is raised, the row's ids are -3
+// (checked by the host wrappers) and the lane's logits, if any (lrow[t * lstride]), NaN; otherwise the steps from t on,
+// never executed (sticky stop), get -1.
+template <int NT>
+__device__ __forceinline__ void greedy_finish(int32_t* ids_row, bool failed, int t, int T, unsigned* status,
+                                              float* lrow = nullptr, int lstride = 0) {
+    const int tid = threadIdx.x;
+    if (failed) {
+        if ((tid & 63) == 0) atomicOr(status, 1u);
+        if (ids_row) for (int tt = tid; tt < T; tt += NT) ids_row[tt] = -3;
+        if (lrow) for (int tt = 0; tt < T; ++tt) lrow[(size_t)tt * lstride] = __builtin_nanf("");
+    } else if (ids_row) {
+        for (int tt = t + tid; tt < T; tt += NT) ids_row[tt] = -1;
+    }
+}
+
+// Phase stamps (profiling build, -DI2L_GROUP_STAMPS): I2L_STAMP(i) adds the wall-clock ticks since the previous stamp
+// to st_.acc[i]; each kernel reads st_.acc out into status[8 + ...] in its own layout (profiles/*stamps*).
+#ifdef I2L_GROUP_STAMPS
+struct StampAcc {
+    long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    long long last = (long long)wall_clock64();
+    __device__ __forceinline__ void operator()(int i) {
+        const long long n = (long long)wall_clock64();
+        acc[i] += n - last;
+        last = n;
+    }
+};
+#define I2L_STAMPS_BEGIN StampAcc st_
+#define I2L_STAMP(i) st_(i)
+#else
+#define I2L_STAMPS_BEGIN do { } while (0)
+#define I2L_STAMP(i) do { } while (0)
+#endif
+
 // DPP controls: quad_perm [1,0,3,2] (lane ^ 1), quad_perm [2,3,0,1] (lane ^ 2), row_half_mirror (lane -> 7 - lane
 // within 8), row_ror:n (rotate within 16), row_shl:n (lane reads lane + n)
 constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HMIRROR = 0x141, DPP_ROR4 = 0x124, DPP_ROR8 = 0x128,

@@ -524,6 +524,14 @@ struct TLayout {
     int n_groups;
 };
 
+// status block (2048 bytes) + exchange granules of the grouped recurrences (train_group.inc.h), whose rows per group
+// follow B: 1 up to 64 rows, 2 up to 128, 4 above
+size_t train_xchg_bytes(int B, int n_groups, bool backward) {
+    const int gran = backward ? (B <= 64 ? TGB1_GRAN : (B <= 128 ? TGB2_GRAN : TGB_GRAN))
+                              : (B <= 64 ? TGF1_GRAN : (B <= 128 ? TGF2_GRAN : TGF_GRAN));
+    return 2048 + group_xchg_bytes(n_groups, (size_t)2 * 4 * gran * sizeof(u64_t));
+}
+
 TLayout make_tlayout(int B, int T, int V, int E, int H, int L) {
     TLayout o{};
     size_t off = 0;
@@ -563,8 +571,7 @@ TLayout make_tlayout(int B, int T, int V, int E, int H, int L) {
         // rows per group: 1 up to 64 rows (all 256 CUs on a 64-row shard), 2 up to 128 rows, 4 above
         o.n_groups = B <= 64 ? B : (B <= 128 ? i2l_cdiv(B, 2) : i2l_cdiv(B, 4));
         o.xchg = off;
-        o.xchg_bytes = 2048 + (size_t)i2l_cdiv(o.n_groups, 8) * 8 * 2 * 4 *
-                                  (B <= 64 ? TGB1_GRAN : (B <= 128 ? TGB2_GRAN : TGB_GRAN)) * sizeof(u64_t);
+        o.xchg_bytes = train_xchg_bytes(B, o.n_groups, true);       // the backward's granules are the larger
         off += i2l_align(o.xchg_bytes);
     }
     o.total = off;
@@ -673,15 +680,13 @@ extern "C" int i2l_decoder_train_fwd(const i2l_decoder_weights* w, const float* 
             gp.status = reinterpret_cast<unsigned*>(base + lo.xchg);
             gp.xchg = reinterpret_cast<u64_t*>(base + lo.xchg + 2048);
             gp.opts = group_opts(T, flags);
-            const size_t used = 2048 + (size_t)i2l_cdiv(lo.n_groups, 8) * 8 * 2 * 4 *
-                                       (B <= 64 ? TGF1_GRAN : (B <= 128 ? TGF2_GRAN : TGF_GRAN)) * sizeof(u64_t);
-            if (hipMemsetAsync(base + lo.xchg, 0, used, s) != hipSuccess) return I2L_ERR_LAUNCH;
+            if (hipMemsetAsync(base + lo.xchg, 0, train_xchg_bytes(B, lo.n_groups, false), s) != hipSuccess) return I2L_ERR_LAUNCH;
             if (B <= 64)
-                hipLaunchKernelGGL(lstm_train_fwd_group1_kernel, dim3(i2l_cdiv(lo.n_groups, 8) * 32), dim3(TGT), 0, s, gp);
+                hipLaunchKernelGGL(lstm_train_fwd_group1_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
             else if (B <= 128)
-                hipLaunchKernelGGL(lstm_train_fwd_group2_kernel, dim3(i2l_cdiv(lo.n_groups, 8) * 32), dim3(TGT), 0, s, gp);
+                hipLaunchKernelGGL(lstm_train_fwd_group2_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
             else
-                hipLaunchKernelGGL(lstm_train_fwd_group_kernel, dim3(i2l_cdiv(lo.n_groups, 8) * 32), dim3(TGT), 0, s, gp);
+                hipLaunchKernelGGL(lstm_train_fwd_group_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
             done = true;
         }
         if (!done && R == 1 && L == 1 && H == NT && T >= 8) {        // part of W_hh resident on chip
@@ -822,11 +827,11 @@ extern "C" int i2l_decoder_train_bwd(const i2l_decoder_weights* w, const int32_t
             gp.opts = group_opts(T, flags);
             if (hipMemsetAsync(base + lo.xchg, 0, lo.xchg_bytes, s) != hipSuccess) return I2L_ERR_LAUNCH;
             if (B <= 64)
-                hipLaunchKernelGGL(lstm_train_bwd_group1_kernel, dim3(i2l_cdiv(lo.n_groups, 8) * 32), dim3(TGT), 0, s, gp);
+                hipLaunchKernelGGL(lstm_train_bwd_group1_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
             else if (B <= 128)
-                hipLaunchKernelGGL(lstm_train_bwd_group2_kernel, dim3(i2l_cdiv(lo.n_groups, 8) * 32), dim3(TGT), 0, s, gp);
+                hipLaunchKernelGGL(lstm_train_bwd_group2_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
             else
-                hipLaunchKernelGGL(lstm_train_bwd_group_kernel, dim3(i2l_cdiv(lo.n_groups, 8) * 32), dim3(TGT), 0, s, gp);
+                hipLaunchKernelGGL(lstm_train_bwd_group_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
             done = true;
         }
         if (!done && R == 1 && L == 1 && H == NT && T >= 8) {

@@ -7,6 +7,9 @@
 //   backward: member m owns the same units: gate gradients from (dh, dc) for its units, stores DG, publishes its
 //             256 x 4 gate gradients; dh_{t-1}[own units] = sum over ALL 1024 gate rows n of Whh[n][unit] dG[n].
 // A timed-out wait raises status[0] and fills the outputs of the affected rows with NaN (the loss turns NaN).
+// Seating and the per-step polls are written out in these six kernels rather than taken from group_seat / PollClock
+// (group_common.inc.h; same mapping, same cadence): through the helpers the compiler allocates these kernels' registers
+// differently (SGPRs of all six, VGPRs of two), and their resource use is held fixed.
 #include "group_common.inc.h"
 
 constexpr int TGT = 512;                       // threads per workgroup
@@ -32,33 +35,12 @@ struct TrainGroupBwd {
     GroupOpts opts;       // poll limits, exchange flavour (group_common.inc.h)
 };
 
-// Are the four members on one XCD?  (decode_group.inc.h: measured, never assumed.)  Returns via LDS word flag[1];
-// flag[0] is set when the wait itself timed out.  Called by every thread; contains a barrier.
-__device__ __forceinline__ bool group_placement_local(u64_t* xg, int gran, int xslot, int m, int* flag, long long limit, bool silent) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (wave == 0) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 0xFu;
-        if (lane == 0 && !silent) store_granule(xg + (size_t)m * gran + xslot, granule(0xC0DEu, __uint_as_float(xcc)), false);
-        const int pq = (lane & 3) + ((lane & 3) >= m ? 1 : 0);
-        u64_t pv = 0;
-        bool bad = false;
-        long long t_start = 0;
-        unsigned spins = 0;
-        for (;;) {
-            bool ok = true;
-            if (lane < 3) { pv = load_granule(xg + (size_t)pq * gran + xslot); ok = (unsigned)(pv >> 32) == 0xC0DEu; }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 255u) == 0) {
-                const long long now = (long long)wall_clock64();
-                if (t_start == 0) t_start = now;
-                else if (now - t_start > limit) { bad = true; break; }
-            }
-        }
-        const bool all_same = __all(lane >= 3 || (unsigned)pv == xcc);
-        if (lane == 0) { flag[1] = (all_same && !bad) ? 1 : 0; flag[0] = bad ? 1 : 0; }
+// Are the four members on one XCD?  (group_placement, group_common.inc.h.)  Returns via LDS word flag[1]; flag[0] is
+// set when the wait itself timed out.  Called by every thread; contains a barrier.  No placement statistics.
+__device__ __forceinline__ bool group_placement_local(u64_t* xg, int gran, int xslot, int m, int* flag, const GroupOpts& o) {
+    if (threadIdx.x < 64) {
+        const Placement pl = group_placement<4>(xg, gran, xslot, m, o);
+        if (threadIdx.x == 0) { flag[1] = (pl.one_xcd && !pl.timed_out) ? 1 : 0; flag[0] = pl.timed_out ? 1 : 0; }
     }
     __syncthreads();
     return flag[1] != 0;
@@ -85,7 +67,7 @@ __global__ __launch_bounds__(TGT) void lstm_train_fwd_group_kernel(TrainGroupFwd
     }
     for (int idx = tid; idx < 2 * 1024; idx += TGT) (&h_s[0][0])[idx] = 0.f;
     u64_t* xg = p.xchg + (size_t)group * 2 * 4 * TGF_GRAN;
-    const bool local = group_placement_local(xg, TGF_GRAN, 272, m, flag, p.opts.limit_first, p.opts.drop_member && m == 3) && !p.opts.agent_scope;      // barrier inside: h_s zeroed
+    const bool local = group_placement_local(xg, TGF_GRAN, 272, m, flag, p.opts) && !p.opts.agent_scope;      // barrier inside: h_s zeroed
     const int row = min(row0 + kr, B - 1);
     const bool live = ke < 4 && row0 + kr < B;                                  // this lane owns (unit, row kr)
     float c_own = 0.f, h_own = 0.f;
@@ -206,7 +188,7 @@ __global__ __launch_bounds__(TGT) void lstm_train_bwd_group_kernel(TrainGroupBwd
     const int row = min(row0 + o_row, B - 1);
     const bool owner = ns < 16, live = owner && row0 + o_row < B;
     u64_t* xg = p.xchg + (size_t)group * 2 * 4 * TGB_GRAN;
-    const bool local = group_placement_local(xg, TGB_GRAN, 1024, m, flag, p.opts.limit_first, p.opts.drop_member && m == 3) && !p.opts.agent_scope;
+    const bool local = group_placement_local(xg, TGB_GRAN, 1024, m, flag, p.opts) && !p.opts.agent_scope;
     float dh_rec = 0.f, dc_next = 0.f;
     bool failed = false;
     float4 a_nx = make_float4(0.f, 0.f, 0.f, 0.f);                             // step t-1's reads, requested during step t
@@ -366,7 +348,7 @@ __global__ __launch_bounds__(TGT) void lstm_train_fwd_group2_kernel(TrainGroupFw
     }
     for (int idx = tid; idx < 2 * 512; idx += TGT) (&h_s[0][0])[idx] = 0.f;
     u64_t* xg = p.xchg + (size_t)group * 2 * 4 * TGF2_GRAN;
-    const bool local = group_placement_local(xg, TGF2_GRAN, 144, m, flag, p.opts.limit_first, p.opts.drop_member && m == 3) && !p.opts.agent_scope;   // barrier inside: h_s zeroed
+    const bool local = group_placement_local(xg, TGF2_GRAN, 144, m, flag, p.opts) && !p.opts.agent_scope;   // barrier inside: h_s zeroed
     const int row = min(row0 + kr, B - 1);
     const bool live = ke < 2 && row0 + kr < B;                                  // this lane owns (unit, row kr)
     float c_own = 0.f, h_own = 0.f;
@@ -482,7 +464,7 @@ __global__ __launch_bounds__(TGT) void lstm_train_bwd_group2_kernel(TrainGroupBw
     const int row = min(row0 + o_row, B - 1);
     const bool owner = ns < 8, live = owner && row0 + o_row < B;
     u64_t* xg = p.xchg + (size_t)group * 2 * 4 * TGB2_GRAN;
-    const bool local = group_placement_local(xg, TGB2_GRAN, 512, m, flag, p.opts.limit_first, p.opts.drop_member && m == 3) && !p.opts.agent_scope;
+    const bool local = group_placement_local(xg, TGB2_GRAN, 512, m, flag, p.opts) && !p.opts.agent_scope;
     float dh_rec = 0.f, dc_next = 0.f;
     bool failed = false;
     float4 a_nx = make_float4(0.f, 0.f, 0.f, 0.f);                             // step t-1's reads, requested during step t
@@ -633,7 +615,7 @@ __global__ __launch_bounds__(TGT) void lstm_train_fwd_group1_kernel(TrainGroupFw
     }
     for (int idx = tid; idx < 2 * 256; idx += TGT) (&h_s[0][0])[idx] = 0.f;
     u64_t* xg = p.xchg + (size_t)group * 2 * 4 * TGF1_GRAN;
-    const bool local = group_placement_local(xg, TGF1_GRAN, 80, m, flag, p.opts.limit_first, p.opts.drop_member && m == 3) && !p.opts.agent_scope;   // barrier inside: h_s zeroed
+    const bool local = group_placement_local(xg, TGF1_GRAN, 80, m, flag, p.opts) && !p.opts.agent_scope;   // barrier inside: h_s zeroed
     const bool live = ke == 0;                                                  // this lane owns the cell of `unit`
     auto hpos = [](int k) { return (((k >> 4) * 8 + (k & 7)) << 1) + ((k >> 3) & 1); };
     float c_own = 0.f, h_own = 0.f;
@@ -752,7 +734,7 @@ __global__ __launch_bounds__(TGT) void lstm_train_bwd_group1_kernel(TrainGroupBw
     const bool owner = (ns & ~5) == 0;
     auto dpos = [](int n) { return (((n >> 6) * 32 + (n & 31)) << 1) + ((n >> 5) & 1); };
     u64_t* xg = p.xchg + (size_t)group * 2 * 4 * TGB1_GRAN;
-    const bool local = group_placement_local(xg, TGB1_GRAN, 256, m, flag, p.opts.limit_first, p.opts.drop_member && m == 3) && !p.opts.agent_scope;
+    const bool local = group_placement_local(xg, TGB1_GRAN, 256, m, flag, p.opts) && !p.opts.agent_scope;
     float dh_rec = 0.f, dc_next = 0.f;
     bool failed = false;
     // what the cell backward of step t-1 reads (activations, cell states, dh from above) is requested during step t

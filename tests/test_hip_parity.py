@@ -987,6 +987,17 @@ def test_grouped_kernels_forced_timeout_fails_loudly_and_falls_back():
     mm.decoder.kernel_flags = 0
     out = ts.step(xs, forms)
     assert float(out["skipped"]) == 0.0 and np.isfinite(float(out["loss"]))
+    # the same forced time-out on the 2-row (65 <= B <= 128) and 4-row (B > 128) training recurrences
+    for b in (96, 160):
+        xs = torch.from_numpy(synth.make_images(b, cfg3, seed=5)).to(DEV)
+        forms = torch.from_numpy(synth.make_formulas(b, 40, cfg3["vocab_size"], seed=6)).to(DEV)
+        before = ts.flat_params.clone()
+        mm.decoder.kernel_flags = bad
+        try:
+            out = ts.step(xs, forms)
+        finally:
+            mm.decoder.kernel_flags = 0
+        assert float(out["skipped"]) == 1.0 and torch.equal(ts.flat_params, before), b
 
 
 def test_encoder_reuses_packed_filters_until_a_weight_changes():
