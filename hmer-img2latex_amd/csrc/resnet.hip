@@ -758,8 +758,8 @@ extern "C" int i2l_conv_bn_bf16_pack(const float* w, const float* bn_weight, con
 extern "C" size_t i2l_conv_bf16_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride,
                                                 int pad, int flags) {
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return 0;
+    if (H + 2 * pad < kh || W + 2 * pad < kw) return 0;   // else the truncating division below gives Ho = 1, not 0
     const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return 0;
     const int Kp = i2l_cdiv(kh * kw * Cin, 8) * 8;
     const bool direct = kh == 1 && kw == 1 && stride == 1 && pad == 0 && Cin % 8 == 0;
     const bool implicit = Cin % 64 == 0;                   // NHWC input gathered inside the GEMM (no im2col image)

@@ -391,6 +391,7 @@ struct ConvGeom {
 inline bool conv_geom(int x_kind, int B, int H, int W, int Cin, int kh, int kw, int stride, int pad, ConvGeom* g) {
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return false;
     if (x_kind != 1 && x_kind != 2) return false;
+    if (H + 2 * pad < kh || W + 2 * pad < kw) return false;   // else the truncating division below gives Ho = 1, not 0
     g->Ho = (H + 2 * pad - kh) / stride + 1;
     g->Wo = (W + 2 * pad - kw) / stride + 1;
     if (g->Ho <= 0 || g->Wo <= 0) return false;
@@ -566,16 +567,16 @@ extern "C" int i2l_bn_train_bwd_f32(const float* dy, const float* y_relu, const 
 extern "C" int i2l_im2col_f32(const void* x, int x_kind, int B, int H, int W, int C, int kh, int kw, int stride, int pad,
                               float* col, i2l_stream_t stream) {
     if (!x || !col || B <= 0 || H <= 0 || W <= 0 || C <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return I2L_ERR_ARG;
+    if (H + 2 * pad < kh || W + 2 * pad < kw) return I2L_ERR_ARG;
     const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return I2L_ERR_ARG;
     return launch_im2col(x, x_kind, B, H, W, C, kh, kw, stride, pad, Ho, Wo, col, i2l_s(stream));
 }
 
 extern "C" int i2l_col2im_f32(const float* dcol, int B, int H, int W, int C, int kh, int kw, int stride, int pad, float* dx,
                               int accumulate, i2l_stream_t stream) {
     if (!dcol || !dx || B <= 0 || H <= 0 || W <= 0 || C <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return I2L_ERR_ARG;
+    if (H + 2 * pad < kh || W + 2 * pad < kw) return I2L_ERR_ARG;
     const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return I2L_ERR_ARG;
     hipLaunchKernelGGL(col2im_kernel, dim3(grid_for((long)B * H * W * C)), dim3(256), 0, i2l_s(stream), dcol, B, H, W, C, kh, kw,
                        stride, pad, Ho, Wo, dx, accumulate ? 1 : 0);
     I2L_CHECK_LAUNCH();

@@ -189,7 +189,8 @@ int i2l_conv_bn_act_bf16_fwd(const void* x, int x_is_nchw_f32, const void* packe
                              void* y, int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride,
                              int pad, int relu, void* workspace, size_t workspace_bytes, int flags,
                              i2l_stream_t stream);
-/* nn.MaxPool2d(3, stride 2, padding 1) on NHWC bf16: (B,H,W,C) -> (B,(H-1)/2+1,(W-1)/2+1,C). */
+/* nn.MaxPool2d(3, stride 2, padding 1) on NHWC bf16: (B,H,W,C) -> (B,(H-1)/2+1,(W-1)/2+1,C), C % 8 == 0 (else
+ * I2L_ERR_UNSUPPORTED).  i2l_global_avgpool_bf16_fwd below accepts any C (8 channels per thread when C % 8 == 0). */
 /* Bottleneck tail + the next block's head in ONE launch (r04; encoder.py:185-249, torchvision Bottleneck.forward's
  * `out = relu(bn3(conv3(out)) + identity)` followed by the next block's `relu(bn1(conv1(x)))`):
  *   y[p][256] = relu(bn3(conv3(o2[p][64])) + identity[p][256]),  z[p][n2] = relu(bn1'(conv1'(y[p])))      NHWC bf16
@@ -249,8 +250,9 @@ int i2l_im2col_f32(const void* x, int x_kind, int B, int H, int W, int C, int kh
                    float* col, i2l_stream_t stream);
 int i2l_col2im_f32(const float* dcol, int B, int H, int W, int C, int kh, int kw, int stride, int pad, float* dx,
                    int accumulate, i2l_stream_t stream);
-/* nn.MaxPool2d(3, 2, 1) on NHWC fp32 (C % 4 == 0) and its backward (x = the forward input; the first maximum of a
- * window takes its gradient, as ATen); nn.AdaptiveAvgPool2d(1) + Flatten (B,H,W,C) -> (B,C) and its backward. */
+/* nn.MaxPool2d(3, 2, 1) on NHWC fp32 and its backward (x = the forward input; the first maximum of a window takes its
+ * gradient, as ATen); nn.AdaptiveAvgPool2d(1) + Flatten (B,H,W,C) -> (B,C) and its backward.  The two forward passes
+ * need C % 4 == 0 (else I2L_ERR_UNSUPPORTED); the two backward passes accept any C. */
 int i2l_maxpool3x3s2_f32_fwd(const float* x, float* y, int B, int H, int W, int C, i2l_stream_t stream);
 int i2l_maxpool3x3s2_f32_bwd(const float* x, const float* dy, float* dx, int B, int H, int W, int C, i2l_stream_t stream);
 int i2l_global_avgpool_f32_fwd(const float* x, float* y, int B, int H, int W, int C, i2l_stream_t stream);

@@ -149,6 +149,33 @@ def check_decisions(sd, cfg, x, decisions, tol=2e-6):
     return n_off, n_all
 
 
+# Operands that break a split-bf16 product scheme which only LOOKS fp32-grade on randn data (test_hip_parity.py,
+# test_train_primitives.py)
+ADVERSARIAL = ["cancellation", "range_2^+-60", "tiny_2^-100", "huge_2^+100"]
+
+
+def _adversarial(kind, x, w, chan_dim_x, chan_dim_w, g):
+    """Rewrites (x, w) along their reduction (input-channel / K) axis; returns the operands."""
+    n = x.shape[chan_dim_x]
+    if kind == "cancellation":          # consecutive reduction slots cancel to ~2^-12 of their size
+        xe, xo = x.narrow(chan_dim_x, 0, n // 2 * 2).unfold(chan_dim_x, 2, 2).unbind(-1)
+        we, wo = w.narrow(chan_dim_w, 0, n // 2 * 2).unfold(chan_dim_w, 2, 2).unbind(-1)
+        xo.copy_(-xe * (1.0 + 2.0 ** -12))
+        wo.copy_(we)
+        x, w = x * 64.0, w * 64.0
+    elif kind == "range_2^+-60":        # slot c scaled by 2^e_c in x and 2^-e_c in w: products stay O(1)
+        e = torch.randint(-60, 61, (n,), generator=g).double()
+        shape_x = [1] * x.dim(); shape_x[chan_dim_x] = n
+        shape_w = [1] * w.dim(); shape_w[chan_dim_w] = n
+        x = (x.double() * (2.0 ** e).reshape(shape_x)).float()
+        w = (w.double() * (2.0 ** -e).reshape(shape_w)).float()
+    elif kind == "tiny_2^-100":         # low split pieces at 2^-116: still normal bf16 numbers
+        x = x * 2.0 ** -100
+    elif kind == "huge_2^+100":
+        x, w = x * 2.0 ** 100, w * 2.0 ** -20
+    return x.contiguous(), w.contiguous()
+
+
 def adam_first_step_allowance(g_a, g_b, p0, coef_a=1.0, coef_b=1.0, coef_unc=0.0, lr=1e-3, wd=1e-4, eps=1e-8, base=3e-6):
     """How far one parameter may move between two runs of the FIRST Adam step whose gradients are g_a and g_b and whose
     clip coefficients are coef_a and coef_b (each known to a relative `coef_unc`: the total norm is a sum over 11.6 M

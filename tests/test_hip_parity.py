@@ -8,8 +8,8 @@ import torch
 
 import img2latex_oracle as O
 from conftest import record
-from helpers import (_MODELS, ALL, BIG, END, SMALL, START, _margin_guard, close, images, load, model_for, padded_to_lists,
-                     sample, torch_state_dict)
+from helpers import (_MODELS, ADVERSARIAL, ALL, BIG, END, SMALL, START, _adversarial, _margin_guard, close, images, load,
+                     model_for, padded_to_lists, sample, torch_state_dict)
 from img2latex_amd import _lib, synth
 from img2latex_amd.model import Seq2SeqModel
 
@@ -206,31 +206,6 @@ def _conv_truth(x, w, b):
     pre = torch.nn.functional.conv2d(xd, wd, bd, padding=1)
     mag = torch.nn.functional.conv2d(xd.abs(), wd.abs(), bd.abs(), padding=1)
     return torch.nn.functional.max_pool2d(torch.relu(pre), 2), torch.nn.functional.max_pool2d(mag, 2)
-
-
-ADVERSARIAL = ["cancellation", "range_2^+-60", "tiny_2^-100", "huge_2^+100"]
-
-
-def _adversarial(kind, x, w, chan_dim_x, chan_dim_w, g):
-    """Rewrites (x, w) along their reduction (input-channel / K) axis; returns the operands."""
-    n = x.shape[chan_dim_x]
-    if kind == "cancellation":          # consecutive reduction slots cancel to ~2^-12 of their size
-        xe, xo = x.narrow(chan_dim_x, 0, n // 2 * 2).unfold(chan_dim_x, 2, 2).unbind(-1)
-        we, wo = w.narrow(chan_dim_w, 0, n // 2 * 2).unfold(chan_dim_w, 2, 2).unbind(-1)
-        xo.copy_(-xe * (1.0 + 2.0 ** -12))
-        wo.copy_(we)
-        x, w = x * 64.0, w * 64.0
-    elif kind == "range_2^+-60":        # slot c scaled by 2^e_c in x and 2^-e_c in w: products stay O(1)
-        e = torch.randint(-60, 61, (n,), generator=g).double()
-        shape_x = [1] * x.dim(); shape_x[chan_dim_x] = n
-        shape_w = [1] * w.dim(); shape_w[chan_dim_w] = n
-        x = (x.double() * (2.0 ** e).reshape(shape_x)).float()
-        w = (w.double() * (2.0 ** -e).reshape(shape_w)).float()
-    elif kind == "tiny_2^-100":         # low split pieces at 2^-116: still normal bf16 numbers
-        x = x * 2.0 ** -100
-    elif kind == "huge_2^+100":
-        x, w = x * 2.0 ** 100, w * 2.0 ** -20
-    return x.contiguous(), w.contiguous()
 
 
 @pytest.mark.parametrize("kind", ADVERSARIAL)
