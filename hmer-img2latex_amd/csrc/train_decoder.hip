@@ -524,11 +524,10 @@ struct TLayout {
     int n_groups;
 };
 
-// status block (2048 bytes) + exchange granules of the grouped recurrences (train_group.inc.h), whose rows per group
-// follow B: 1 up to 64 rows, 2 up to 128, 4 above
+// status block (2048 bytes) + exchange granules of the grouped recurrences (train_group.inc.h)
 size_t train_xchg_bytes(int B, int n_groups, bool backward) {
-    const int gran = backward ? (B <= 64 ? TGB1_GRAN : (B <= 128 ? TGB2_GRAN : TGB_GRAN))
-                              : (B <= 64 ? TGF1_GRAN : (B <= 128 ? TGF2_GRAN : TGF_GRAN));
+    const int rows = train_group_rows(B);
+    const int gran = backward ? tgb_gran(rows) : tgf_gran(rows);
     return 2048 + group_xchg_bytes(n_groups, (size_t)2 * 4 * gran * sizeof(u64_t));
 }
 
@@ -568,8 +567,7 @@ TLayout make_tlayout(int B, int T, int V, int E, int H, int L) {
     o.gemm_ws2 = off;                                                // the side stream's
     off += o.gemm_ws_bytes;
     if (L == 1 && H == 256) {           // grouped recurrences (train_group.inc.h): status block + exchange granules
-        // rows per group: 1 up to 64 rows (all 256 CUs on a 64-row shard), 2 up to 128 rows, 4 above
-        o.n_groups = B <= 64 ? B : (B <= 128 ? i2l_cdiv(B, 2) : i2l_cdiv(B, 4));
+        o.n_groups = i2l_cdiv(B, train_group_rows(B));
         o.xchg = off;
         o.xchg_bytes = train_xchg_bytes(B, o.n_groups, true);       // the backward's granules are the larger
         off += i2l_align(o.xchg_bytes);
@@ -673,7 +671,7 @@ extern "C" int i2l_decoder_train_fwd(const i2l_decoder_weights* w, const float* 
         if (lds > 64 * 1024) return I2L_ERR_UNSUPPORTED;
         dim3 grid(i2l_cdiv(B, R));
         bool done = false;
-        if (lo.xchg_bytes && T >= 8 && group_on) {  // 4 workgroups share 4 rows, W_hh in registers
+        if (lo.xchg_bytes && T >= 8 && group_on) {  // 4 workgroups share 1, 2 or 4 rows, W_hh in registers
             TrainGroupFwd gp{};
             gp.B = B; gp.T = T; gp.n_groups = lo.n_groups; gp.GX = p.GX; gp.WhhT = p.WhhT[0];
             gp.ACT = p.ACT[0]; gp.C = p.C[0]; gp.Hout = p.Hout[0]; gp.Hprev = p.Hprev[0];
@@ -681,12 +679,10 @@ extern "C" int i2l_decoder_train_fwd(const i2l_decoder_weights* w, const float* 
             gp.xchg = reinterpret_cast<u64_t*>(base + lo.xchg + 2048);
             gp.opts = group_opts(T, flags);
             if (hipMemsetAsync(base + lo.xchg, 0, train_xchg_bytes(B, lo.n_groups, false), s) != hipSuccess) return I2L_ERR_LAUNCH;
-            if (B <= 64)
-                hipLaunchKernelGGL(lstm_train_fwd_group1_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
-            else if (B <= 128)
-                hipLaunchKernelGGL(lstm_train_fwd_group2_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
-            else
-                hipLaunchKernelGGL(lstm_train_fwd_group_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
+            const int rows = train_group_rows(B);
+            void (*kern)(TrainGroupFwd) = rows == 1 ? lstm_train_fwd_group_kernel<1>
+                                           : rows == 2 ? lstm_train_fwd_group_kernel<2> : lstm_train_fwd_group_kernel<4>;
+            hipLaunchKernelGGL(kern, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
             done = true;
         }
         if (!done && R == 1 && L == 1 && H == NT && T >= 8) {        // part of W_hh resident on chip
@@ -826,12 +822,10 @@ extern "C" int i2l_decoder_train_bwd(const i2l_decoder_weights* w, const int32_t
             gp.xchg = reinterpret_cast<u64_t*>(base + lo.xchg + 2048);
             gp.opts = group_opts(T, flags);
             if (hipMemsetAsync(base + lo.xchg, 0, lo.xchg_bytes, s) != hipSuccess) return I2L_ERR_LAUNCH;
-            if (B <= 64)
-                hipLaunchKernelGGL(lstm_train_bwd_group1_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
-            else if (B <= 128)
-                hipLaunchKernelGGL(lstm_train_bwd_group2_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
-            else
-                hipLaunchKernelGGL(lstm_train_bwd_group_kernel, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
+            const int rows = train_group_rows(B);
+            void (*kern)(TrainGroupBwd) = rows == 1 ? lstm_train_bwd_group_kernel<1>
+                                           : rows == 2 ? lstm_train_bwd_group_kernel<2> : lstm_train_bwd_group_kernel<4>;
+            hipLaunchKernelGGL(kern, dim3(group_grid(lo.n_groups, 4)), dim3(TGT), 0, s, gp);
             done = true;
         }
         if (!done && R == 1 && L == 1 && H == NT && T >= 8) {
