@@ -295,6 +295,204 @@ __global__ __launch_bounds__(MT) void compact_ids_kernel(const int32_t* __restri
     if (lane == 0) out_len[row] = n;
 }
 
+// ------------------------------------------------------------------ teacher-forced evaluation (trainer.py:510-559)
+// One wave per (b,t) row, TFE_WAVES rows per workgroup; the row is read ONCE.  Per row: the label-smoothed CE term of
+// ce_rows_kernel (lse - (1-eps) x_t - eps mean_v x_v; 0 for a pad target) and torch.argmax's first-index arg max.  Rows of
+// vocab <= 2048 stay in registers (4 NK floats per lane, NK = 1, 2, 4, 8: the smallest tile that holds the row, so a
+// short row computes no masked-off exponentials) and take max, then sum exp, then sum x from there -- the exact
+// two-pass form; longer rows merge per-lane (max, sum) pairs online.  expf / logf, not the
+// fast intrinsics.  tfe_finish_kernel then turns the per-row values into the ordered sums and the lengths.
+constexpr int TFE_WAVES = 4;
+constexpr int TFE_REG_V = 2048;         // 64 lanes x 32 floats
+constexpr int TFE_FIN = 1024;           // threads of the finishing workgroup
+
+// torch.argmax order: NaN above everything, then the larger value, then the smaller index
+__device__ __forceinline__ bool tfe_better(float x, int i, float bv, int bi) {
+    const bool xn = x != x, bn = bv != bv;
+    if (xn || bn) return xn && (!bn || i < bi);
+    return x > bv || (x == bv && i < bi);
+}
+
+__device__ __forceinline__ void tfe_wave_argmax(float& bv, int& bi) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        if (tfe_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+}
+
+__device__ __forceinline__ float tfe_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ float tfe_wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// (max, sum of exp(x - max)) merge of the online path; an empty side (max = -inf) contributes nothing
+__device__ __forceinline__ void tfe_merge(float& m, float& s, float om, float os) {
+    if (om == -INFINITY) return;
+    if (m == -INFINITY) { m = om; s = os; return; }
+    const float nm = fmaxf(m, om);
+    s = s * expf(m - nm) + os * expf(om - nm);
+    m = nm;
+}
+
+__device__ __forceinline__ void tfe_online(float x, float& m, float& s) {
+    if (x > m) { s = (m == -INFINITY ? 0.f : s * expf(m - x)) + 1.f; m = x; }
+    else if (x != -INFINITY) s += expf(x - m);             // a NaN lands here and poisons the sum, as in torch
+}
+
+// NK: groups of 4 values per lane in registers (vocab <= 256 NK), 0 = the online path
+template <bool VEC, int NK>
+__global__ __launch_bounds__(64 * TFE_WAVES) void tfe_rows_kernel(const float* __restrict__ logits,
+                                                                const int32_t* __restrict__ targets, long rows, int V,
+                                                                int pad_id, float eps, float* __restrict__ row_loss,
+                                                                int32_t* __restrict__ row_arg) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * TFE_WAVES + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* x = logits + (size_t)row * V;
+    float m = -INFINITY, s = 0.f, sx = 0.f, bv = -INFINITY;
+    int bi = 0x7fffffff;
+    if (NK > 0) {
+        constexpr int NE = 4 * (NK > 0 ? NK : 1);
+        float r[NE];
+        if (VEC) {
+#pragma unroll
+            for (int k = 0; k < NE / 4; ++k) {
+                const int v = 4 * (lane + 64 * k);
+                float4 q = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+                if (v < V) q = *reinterpret_cast<const float4*>(x + v);
+                r[4 * k] = q.x; r[4 * k + 1] = q.y; r[4 * k + 2] = q.z; r[4 * k + 3] = q.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NE; ++k) {
+                const int v = lane + 64 * k;
+                r[k] = v < V ? x[v] : -INFINITY;
+            }
+        }
+        // element k of this lane is vocabulary index idx(k), increasing in k: the first better one wins a tie
+#define TFE_IDX(k) (VEC ? 4 * (lane + 64 * ((k) >> 2)) + ((k) & 3) : lane + 64 * (k))
+#pragma unroll
+        for (int k = 0; k < NE; ++k)
+            if (TFE_IDX(k) < V && tfe_better(r[k], TFE_IDX(k), bv, bi)) { bv = r[k]; bi = TFE_IDX(k); }
+#pragma unroll
+        for (int k = 0; k < NE; ++k) m = fmaxf(m, r[k]);
+        m = tfe_wave_max(m);
+#pragma unroll
+        for (int k = 0; k < NE; ++k)
+            if (TFE_IDX(k) < V) { s += expf(r[k] - m); sx += r[k]; }
+#undef TFE_IDX
+        s = tfe_wave_sum(s);
+    } else {
+        if (VEC) {
+            for (int v = 4 * lane; v < V; v += 256) {
+                const float4 q = *reinterpret_cast<const float4*>(x + v);
+                const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (tfe_better(e[j], v + j, bv, bi)) { bv = e[j]; bi = v + j; }
+                    tfe_online(e[j], m, s);
+                    sx += e[j];
+                }
+            }
+        } else {
+            for (int v = lane; v < V; v += 64) {
+                const float e = x[v];
+                if (tfe_better(e, v, bv, bi)) { bv = e; bi = v; }
+                tfe_online(e, m, s);
+                sx += e;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float om = __shfl_xor(m, off, 64), os = __shfl_xor(s, off, 64);
+            tfe_merge(m, s, om, os);
+        }
+    }
+    sx = tfe_wave_sum(sx);
+    tfe_wave_argmax(bv, bi);
+    if (lane == 0) {
+        const int tgt = targets[row];
+        const bool keep = tgt != pad_id;
+        const int tg = min(max(tgt, 0), V - 1);             // ce_rows_kernel's clamp of an out-of-range target
+        const float lse = m + logf(s);
+        const float nll = lse - x[tg];
+        const float smooth = lse - sx / (float)V;
+        row_loss[row] = keep ? (1.f - eps) * nll + eps * smooth : 0.f;
+        row_arg[row] = bi;
+    }
+}
+
+// One workgroup: [loss_sum, count] as ordered_sum2_kernel forms them (thread i adds rows i, i + TFE_FIN, ... in double,
+// then a fixed tree; written as float), the exact integer [correct, total], and per sequence the first pad position of
+// the arg max ids and of the targets (a wave per sequence, 64 positions per ballot).  Deterministic: no atomics.
+__global__ __launch_bounds__(TFE_FIN) void tfe_finish_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ row_arg,
+                                                             const int32_t* __restrict__ targets, int batch, int steps,
+                                                             int pad_id, int32_t* __restrict__ pred_len,
+                                                             int32_t* __restrict__ target_len, float* __restrict__ loss_out,
+                                                             int64_t* __restrict__ correct_out) {
+    __shared__ double rl[TFE_FIN];
+    __shared__ long long rc[TFE_FIN], rt[TFE_FIN];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long rows = (long)batch * steps;
+    double sl = 0.0;
+    long long cor = 0, tot = 0;
+    long i = tid;
+    for (; i + 3 * TFE_FIN < rows; i += 4 * TFE_FIN) {      // four rows in flight, added in the same order
+        int t[4], a[4];
+        float l[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { t[j] = targets[i + j * TFE_FIN]; a[j] = row_arg[i + j * TFE_FIN]; l[j] = row_loss[i + j * TFE_FIN]; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            sl += l[j];
+            if (t[j] != pad_id) { ++tot; cor += a[j] == t[j] ? 1 : 0; }
+        }
+    }
+    for (; i < rows; i += TFE_FIN) {
+        const int t = targets[i];
+        sl += row_loss[i];
+        if (t != pad_id) { ++tot; cor += row_arg[i] == t ? 1 : 0; }
+    }
+    rl[tid] = sl; rc[tid] = cor; rt[tid] = tot;
+    __syncthreads();
+    for (int off = TFE_FIN / 2; off > 0; off >>= 1) {
+        if (tid < off) { rl[tid] += rl[tid + off]; rc[tid] += rc[tid + off]; rt[tid] += rt[tid + off]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        loss_out[0] = (float)rl[0];
+        loss_out[1] = (float)rt[0];
+        correct_out[0] = rc[0];
+        correct_out[1] = rt[0];
+    }
+    if (!pred_len && !target_len) return;
+    for (int b = wave; b < batch; b += TFE_FIN / 64) {
+        const int32_t* a = row_arg + (size_t)b * steps;
+        const int32_t* t = targets + (size_t)b * steps;
+        int pl = steps, tl = steps;
+        for (int base = 0; base < steps; base += 64) {
+            const int pos = base + lane;
+            const unsigned long long pm = __ballot(pos < steps && a[pos] == pad_id);
+            const unsigned long long tm = __ballot(pos < steps && t[pos] == pad_id);
+            if (pl == steps && pm) pl = base + __ffsll((long long)pm) - 1;
+            if (tl == steps && tm) tl = base + __ffsll((long long)tm) - 1;
+        }
+        if (lane == 0) {
+            if (pred_len) pred_len[b] = pl;
+            if (target_len) target_len[b] = tl;
+        }
+    }
+}
+
 size_t metrics_lds(int max_len) { return ((size_t)2 * max_len + 3 * ((size_t)max_len + 1) + 8) * sizeof(int); }
 
 }  // namespace
@@ -386,6 +584,48 @@ extern "C" int i2l_compact_ids(const int32_t* ids, int rows, int width, int stri
         return I2L_ERR_ARG;
     hipLaunchKernelGGL(compact_ids_kernel, dim3(i2l_cdiv(rows, MT / 64)), dim3(MT), 0, i2l_s(stream), ids, rows, width,
                        stride, end_id, drop_ids, n_drop, out_ids, out_stride, out_len);
+    I2L_CHECK_LAUNCH();
+    return I2L_OK;
+}
+
+extern "C" size_t i2l_teacher_forced_eval_workspace_bytes(int batch, int steps) {
+    if (batch < 0 || steps < 0) return 0;
+    const size_t rows = (size_t)batch * (size_t)steps;
+    return 2 * i2l_align((rows > 0 ? rows : 1) * sizeof(float));
+}
+
+extern "C" int i2l_teacher_forced_eval(const float* logits, const int32_t* targets, int batch, int steps, int vocab,
+                                       int pad_id, float label_smoothing, void* workspace, size_t workspace_bytes,
+                                       int32_t* argmax_out, int32_t* pred_len_out, int32_t* target_len_out,
+                                       float* loss_sum_count_out, int64_t* correct_total_out, i2l_stream_t stream) {
+    if (batch < 0 || steps < 0 || vocab < 1 || !loss_sum_count_out || !correct_total_out ||
+        !(label_smoothing >= 0.f && label_smoothing < 1.f))
+        return I2L_ERR_ARG;
+    const long rows = (long)batch * steps;
+    if (rows > 0 && (!logits || !targets)) return I2L_ERR_ARG;
+    const size_t need = i2l_teacher_forced_eval_workspace_bytes(batch, steps);
+    if (!workspace || workspace_bytes < need) return I2L_ERR_WORKSPACE;
+    float* row_loss = static_cast<float*>(workspace);
+    int32_t* row_arg = argmax_out ? argmax_out
+                                  : reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + need / 2);
+    hipStream_t s = i2l_s(stream);
+    if (rows > 0) {
+        const bool vec = vocab % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
+        const dim3 grid((unsigned)((rows + TFE_WAVES - 1) / TFE_WAVES)), block(64 * TFE_WAVES);
+        // the smallest register tile that holds the row (4 NK values per lane); longer rows: the online path
+        const int nk = vocab <= 256 ? 1 : vocab <= 512 ? 2 : vocab <= 1024 ? 4 : vocab <= TFE_REG_V ? 8 : 0;
+#define I2L_TFE(VEC_, NK_) hipLaunchKernelGGL((tfe_rows_kernel<VEC_, NK_>), grid, block, 0, s, logits, targets, rows, vocab, \
+                                              pad_id, label_smoothing, row_loss, row_arg)
+#define I2L_TFE_NK(VEC_) if (nk == 1) I2L_TFE(VEC_, 1); else if (nk == 2) I2L_TFE(VEC_, 2); \
+                         else if (nk == 4) I2L_TFE(VEC_, 4); else if (nk == 8) I2L_TFE(VEC_, 8); else I2L_TFE(VEC_, 0)
+        if (vec) { I2L_TFE_NK(true); } else { I2L_TFE_NK(false); }
+#undef I2L_TFE_NK
+#undef I2L_TFE
+        I2L_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(tfe_finish_kernel, dim3(1), dim3(TFE_FIN), 0, s, (const float*)row_loss, (const int32_t*)row_arg,
+                       targets, batch, steps, pad_id, pred_len_out, target_len_out, loss_sum_count_out,
+                       correct_total_out);
     I2L_CHECK_LAUNCH();
     return I2L_OK;
 }

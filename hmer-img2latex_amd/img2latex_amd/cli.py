@@ -4,7 +4,7 @@
     python -m img2latex_amd predict CHECKPOINT IMAGE [--beam-size N] [--max-length N] [--temperature T]
                                                      [--top-k K] [--top-p P] [--device cuda]
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
-                                  [--device cuda] [--seed N]
+                                  [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
 
 ``predict`` is the reference's chain end to end on the device: Predictor.from_checkpoint (predictor.py:61-137) ->
 Predictor.predict(image_path) (:139-203) -> load_image (data/utils.py:18-90) -> encoder -> greedy search -> string.
@@ -14,8 +14,14 @@ checkpoint (trainer.py:235-269) and drives ``TrainStep`` (the optimisation step 
 kernels) over the batches of the data loaders.  Dataset classes, file decoding and vocabulary fitting are outside this
 package's scope: the batches come from the reference's own ``create_data_loaders`` /
 ``LaTeXTokenizer`` when the ``img2latex`` package is importable beside this one, or -- ``--synthetic-steps N`` -- from
-the deterministic generator the benchmarks use.  Experiment registry, logging setup, rich console output, validation
-metrics and early stopping are the reference's host-side orchestration and are not rebuilt here.
+the deterministic generator the benchmarks use.  After every epoch it validates as Trainer.train does
+(trainer.py:667-766): ``training.validate`` on the validation batches, ReduceLROnPlateau on val_loss, a best checkpoint
+(``best_checkpoint_epoch_E_step_S.pt`` + ``best_checkpoint.pt``) or a plain one, early stopping after
+``training.early_stopping_patience`` epochs without improvement, and ``metrics/metrics.json`` when
+``evaluation.save_basic_metrics`` is set.  A synthetic run validates only with ``--synthetic-val-steps N`` (N synthetic
+batches from a seed disjoint from the training batches; it then runs ``training.epochs`` epochs over the same training
+batches); without it, it makes one pass and writes one plain checkpoint, as before.  Experiment registry, logging setup
+and rich console output are the reference's host-side orchestration and are not rebuilt here.
 
 The device is a ROCm GPU; ``--device cpu`` is refused (there is no CPU fallback in this package).
 """
@@ -79,12 +85,17 @@ def _synthetic_batches(config: Dict, steps: int, vocab_size: int, seed: int):
 
 def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: str = "img2latex_v1",
           checkpoint_path: Optional[str] = None, data_dir: Optional[str] = None, device: Optional[str] = None,
-          seed: int = 42, synthetic_steps: int = 0, synthetic_vocab: int = 512, output_dir: str = "outputs") -> Dict:
+          seed: int = 42, synthetic_steps: int = 0, synthetic_vocab: int = 512, output_dir: str = "outputs",
+          synthetic_val_steps: int = 0) -> Dict:
     """cli.py:104-250 reduced to the hot path: model from the config, optional resume, TrainStep over the batches, a
-    checkpoint in the reference's layout (trainer.py:209-224) per epoch.  Returns {"loss", "steps", "checkpoint"}."""
+    checkpoint in the reference's layout (trainer.py:209-224) per epoch, and -- with validation batches -- the epoch-end
+    validation / LR schedule / best checkpoint / early stop of trainer.py:713-766.  Returns {"loss", "steps",
+    "global_step", "checkpoint"}, plus {"best_val_loss", "val_metrics"} when validation ran."""
+    import random
     from . import data as D
-    from .training import TokenTable, TrainStep, save_checkpoint
-    torch.manual_seed(seed)                                                 # mps_utils.set_seed
+    from .training import EarlyStopping, PlateauSchedule, TokenTable, TrainStep, save_checkpoint, validate
+    random.seed(seed)                                                       # mps_utils.set_seed
+    torch.manual_seed(seed)
     config = load_config(config_path)
     if data_dir:
         config.setdefault("data", {})["data_dir"] = data_dir
@@ -100,7 +111,9 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
             vocab = {"<PAD>": 0, "<START>": 1, "<END>": 2, "<UNK>": 3}
             vocab.update({f"t{i}": i for i in range(4, synthetic_vocab)})
             tokenizer = TokenTable(vocab, max_sequence_length=int(config.get("data", {}).get("max_seq_length", 150)))
-        max_epochs, loaders = None, None                                    # one pass over the synthetic batches
+        max_epochs, loaders = None, None                                    # one pass over the synthetic batches ...
+        if synthetic_val_steps > 0:                                         # ... unless there is something to validate on
+            max_epochs = int(tcfg.get("epochs", 50))
     else:
         try:
             from img2latex.data.dataset import create_data_loaders          # the reference's own dataset + tokenizer
@@ -133,6 +146,16 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
     os.makedirs(ck_dir, exist_ok=True)
     last, path = None, None
     is_resnet = config["model"]["name"] == "resnet_lstm"
+    if loaders is not None:
+        val_batches = loaders["val"]
+    elif synthetic_val_steps > 0:                                           # seeds after the training batches' ones
+        val_batches = list(_synthetic_batches(config, synthetic_val_steps, tokenizer.vocab_size, seed + synthetic_steps))
+    else:
+        val_batches = None
+    ecfg = config.get("evaluation", {}) or {}
+    scheduler = PlateauSchedule(ts, mode="min", factor=0.5, patience=2)    # trainer.py:94-98
+    stopper = EarlyStopping.from_checkpoint(int(tcfg.get("early_stopping_patience", 10)), resume)   # :120-122,257-262
+    val_metrics = None
     accum = max(1, int(tcfg.get("accumulation_steps", 1)))                  # trainer.py:86-88 (the shipped config: 4)
     for epoch in range(start_epoch + 1, max_epochs + 1):                    # `epoch` = trainer.py's current_epoch + 1
         batches = _synthetic_batches(config, synthetic_steps, tokenizer.vocab_size, seed) if loaders is None else loaders["train"]
@@ -148,12 +171,52 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
             step += 1                                                       # the reference's global_step counts batches (:399)
             batch, batch_idx = nxt, batch_idx + 1
         loss = float(last["loss"]) if last is not None else float("nan")
-        path = os.path.join(ck_dir, f"checkpoint_epoch_{epoch}_step_{step}.pt")
-        save_checkpoint(path, model, tokenizer, config, epoch=epoch, step=step, metrics={"loss": loss},
+        if val_batches is None:
+            path = os.path.join(ck_dir, f"checkpoint_epoch_{epoch}_step_{step}.pt")
+            save_checkpoint(path, model, tokenizer, config, epoch=epoch, step=step, metrics={"loss": loss},
+                            optimizer_state_dict=ts.optimizer_state_dict())
+            print(f"epoch {epoch}: {step} steps, loss {loss:.4f}, checkpoint {path}")
+            continue
+        # trainer.py:716-766: validate, step the LR schedule on val_loss, best or plain checkpoint, early stop
+        val_metrics = validate(model, val_batches, tokenizer.pad_token_id, int(ecfg.get("bleu_batches", 10)),
+                               label_smoothing=0.1, epoch=epoch - 1, step=step)
+        scheduler.step(val_metrics.get("val_loss", float("inf")))
+        is_best, stop = stopper.update(val_metrics)
+        name = f"checkpoint_epoch_{epoch}_step_{step}.pt"
+        path = os.path.join(ck_dir, "best_" + name if is_best else name)
+        save_checkpoint(path, model, tokenizer, config, epoch=epoch, step=step, metrics=val_metrics,
                         optimizer_state_dict=ts.optimizer_state_dict())
-        print(f"epoch {epoch}: {step} steps, loss {loss:.4f}, checkpoint {path}")
-    return {"loss": float(last["loss"]) if last is not None else None, "steps": step - step0, "global_step": step,
-            "checkpoint": path}
+        if is_best:
+            save_checkpoint(os.path.join(ck_dir, "best_checkpoint.pt"), model, tokenizer, config, epoch=epoch, step=step,
+                            metrics=val_metrics, optimizer_state_dict=ts.optimizer_state_dict())
+        if ecfg.get("save_basic_metrics", False):                           # trainer.py:645-661
+            _save_basic_metrics(os.path.join(output_dir, experiment_name, "metrics"), epoch, val_metrics)
+        extra = "".join(f", {k} {val_metrics[k]:.4f}" for k in ("bleu", "levenshtein") if k in val_metrics)
+        print(f"epoch {epoch}: {step} steps, loss {loss:.4f}, val_loss {val_metrics['val_loss']:.4f}, "
+              f"val_acc {val_metrics['val_acc']:.4f}{extra}, lr {ts.lr:g}, checkpoint {path}")
+        if stop:
+            print(f"early stopping after {epoch} epochs ({stopper.patience_counter} epochs without improvement)")
+            break
+    out = {"loss": float(last["loss"]) if last is not None else None, "steps": step - step0, "global_step": step,
+           "checkpoint": path}
+    if val_metrics is not None:
+        out.update(best_val_loss=stopper.best_val_loss, val_metrics=val_metrics)
+    return out
+
+
+def _save_basic_metrics(metrics_dir: str, epoch: int, val_metrics: Dict) -> None:
+    """trainer.py:645-661: metrics.json keyed by the 1-based epoch, merged into what the file already holds."""
+    import json
+    os.makedirs(metrics_dir, exist_ok=True)
+    metrics_path = os.path.join(metrics_dir, "metrics.json")
+    try:
+        with open(metrics_path, "r") as f:
+            basic_metrics = json.load(f)
+    except Exception:
+        basic_metrics = {}
+    basic_metrics[str(epoch)] = val_metrics
+    with open(metrics_path, "w") as f:
+        json.dump(basic_metrics, f, indent=2)
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -179,6 +242,9 @@ def main(argv: Optional[List[str]] = None) -> int:
                    help="(this package) train N steps on synthetic batches instead of the reference's data loaders")
     t.add_argument("--synthetic-vocab", type=int, default=512, help="(this package) vocabulary size of the synthetic batches")
     t.add_argument("--output-dir", default="outputs", help="(this package) root of <experiment>/checkpoints")
+    t.add_argument("--synthetic-val-steps", type=int, default=0,
+                   help="(this package) with --synthetic-steps: validate every epoch on N synthetic batches and run "
+                        "training.epochs epochs with LR scheduling and early stopping")
     args = ap.parse_args(argv)
     if args.command == "predict":
         latex = predict(args.checkpoint_path, args.image_path, args.beam_size, args.max_length, args.temperature,
@@ -188,7 +254,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,
-              args.synthetic_steps, args.synthetic_vocab, args.output_dir)
+              args.synthetic_steps, args.synthetic_vocab, args.output_dir, args.synthetic_val_steps)
     except SystemExit:
         raise
     except Exception as exc:                                                # cli.py:247-250: failure -> exit code 1

@@ -484,6 +484,29 @@ int i2l_compact_ids(const int32_t* ids, int rows, int width, int stride, int end
 int i2l_masked_accuracy(const float* logits, const int64_t* targets, int64_t rows, int vocab, int64_t pad_id,
                         uint64_t* correct_total_out, i2l_stream_t stream);
 
+/* The per-batch statistics of Trainer.validate (trainer.py:510-559) from the teacher-forced logits in ONE read of them:
+ * logits (batch, steps, vocab) fp32 contiguous, targets (batch, steps) int32 = formulas[:, 1:].  Per (b,t) row the
+ * label-smoothed CE term of nn.CrossEntropyLoss(ignore_index=pad, label_smoothing) (:111-115,521-523; the formula of
+ * i2l_ce_label_smooth_fwd_bwd, 0 where target == pad) and torch.argmax's first-index arg max (:541; NaN counts as the
+ * largest value); a non-pad target outside [0, vocab) is clamped into it for the loss, as i2l_ce_label_smooth_fwd_bwd
+ * does.  Written, not accumulated (so a caller can aim them at slot i of a per-epoch record):
+ *   loss_sum_count_out[2]   fp32 [SUM over non-pad rows of the row loss, number of non-pad rows] -- the convention of
+ *                           i2l_ce_label_smooth_fwd_bwd: the batch's loss.item() is [0] / [1]; fixed-order double sum
+ *   correct_total_out[2]    int64 [#(argmax == target != pad), #(target != pad)]: masked_accuracy, :524-526
+ *   argmax_out (batch, steps) int32 or NULL
+ *   pred_len_out (batch)    first t with argmax == pad, else steps (:547-553); NULL = not wanted
+ *   target_len_out (batch)  first t with target == pad, else steps (:555-559); NULL = not wanted
+ * Two launches (a wave per row; one finishing workgroup), no atomics: bit-identical results run to run.  Rows of
+ * vocab <= 2048 are held in registers (exact two-pass max / sum exp / sum x); 16-byte loads when vocab % 4 == 0 and
+ * logits is 16-byte aligned.  The workspace (i2l_teacher_forced_eval_workspace_bytes) is the caller's.  I2L_ERR_ARG for
+ * batch or steps < 0, vocab < 1, label_smoothing outside [0, 1) or a missing pointer; I2L_ERR_WORKSPACE when it is too
+ * small.  batch * steps == 0 writes zero counts. */
+size_t i2l_teacher_forced_eval_workspace_bytes(int batch, int steps);
+int i2l_teacher_forced_eval(const float* logits, const int32_t* targets, int batch, int steps, int vocab, int pad_id,
+                            float label_smoothing, void* workspace, size_t workspace_bytes, int32_t* argmax_out,
+                            int32_t* pred_len_out, int32_t* target_len_out, float* loss_sum_count_out,
+                            int64_t* correct_total_out, i2l_stream_t stream);
+
 /* Where the grouped greedy kernel's status words live inside the decoder workspace (0: these dimensions have no
  * grouped path): uint32 [0] != 0 -> a poll timed out (the ids are -3), [1] groups that completed the placement
  * exchange in the last launch, [2] of those, the groups whose four workgroups measured themselves on ONE XCD and
