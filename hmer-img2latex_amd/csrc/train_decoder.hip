@@ -240,15 +240,35 @@ struct BwdBuf {
     unsigned long long seed;
 };
 
+// Row groups of the backward's 4H-row reduction dG @ W: one per H/4-thread slice of the workgroup, at most G/32 of
+// them, and G/NG rows each, which matvec consumes in batches of 16 -- the largest such count with G % (16 NG) == 0
+// (H = 192: 4, H = 320: 2; every other multiple of 64 up to 1024 keeps min(NT / (H/4), G/32)).  0: no valid split.
+constexpr __host__ __device__ int bwd_row_groups(int H) {
+    const int G = 4 * H;
+    int n = H >= 4 ? NT / (H / 4) : 0;
+    if (n > G / 32) n = G / 32;
+    while (n > 0 && G % (16 * n) != 0) --n;
+    return n;
+}
+constexpr bool bwd_split_kept_elsewhere() {      // every accepted H but 192 and 320 keeps the split it always had
+    for (int H = 64; H <= 1024; H += 64) {
+        int n = NT / (H / 4);
+        if (n > H / 8) n = H / 8;
+        if (H != 192 && H != 320 && bwd_row_groups(H) != n) return false;
+    }
+    return true;
+}
+static_assert(bwd_split_kept_elsewhere() && bwd_row_groups(192) == 4 && bwd_row_groups(320) == 2,
+              "backward row-group split");
+
 template <int R, int KR, int KL>
 __global__ __launch_bounds__(NT) void lstm_train_bwd_kernel(BwdBuf p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, L = p.L, B = p.B, T = p.T;
     const size_t G = 4 * (size_t)H;
     const int CG = H / 4;                                   // column groups (float4 each)
-    int NG = NT / CG;                                       // row groups of the 4H reduction
-    if (NG > (int)(G / 32)) NG = (int)(G / 32);
-    const int rows_per = (int)(G / NG);                     // multiple of 32
+    const int NG = bwd_row_groups(H);                       // row groups of the 4H reduction
+    const int rows_per = (int)(G / NG);                     // multiple of 16
     float* dh_rec = smem;                    // [L][R][H]  dL/dh_{t} arriving from step t+1
     float* dc_next = dh_rec + L * R * H;     // [L][R][H]
     float* dh_low = dc_next + L * R * H;     // [R][H]     gradient handed to the layer below
@@ -805,9 +825,8 @@ extern "C" int i2l_decoder_train_bwd(const i2l_decoder_weights* w, const int32_t
         p.Whh[l] = w->w_hh[l]; p.Wih[l] = l ? w->w_ih[l] : nullptr;
     }
     {
-        const int CG = H / 4;
-        int NG = NT / CG;
-        if (NG > G / 32) NG = G / 32;
+        const int NG = bwd_row_groups(H);
+        if (NG <= 0) return I2L_ERR_UNSUPPORTED;
         const size_t per_row = ((size_t)2 * L * H + H + G + (size_t)NG * H) * sizeof(float);
         const int R = rows_per_wg(B, per_row, 0);
         const size_t lds = R * per_row;

@@ -54,6 +54,9 @@ class LSTMDecoder(nn.Module):
     ``context == encoder_output`` bit-for-bit (decoder.py:338-341; golden fixture G7).
     The step kernels therefore consume ``encoder_output`` directly for both
     ``attention=True`` and ``attention=False``; results are identical to the reference's.
+
+    The kernels take L <= 4, E % 4 == 0 and H % 64 == 0 (H <= 2048 to decode, <= 1024 to train), with
+    vocabulary and beam limits set by LDS: DESIGN.md, "Accepted decoder dimensions".  Other dimensions raise.
     """
 
     def __init__(self, vocab_size: int, embedding_dim: int = None, hidden_dim: int = None,

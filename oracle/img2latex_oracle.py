@@ -114,8 +114,9 @@ def lstm_step(sd: SD, cfg: Dict, x: torch.Tensor, h: torch.Tensor, c: torch.Tens
     return inp, (torch.stack(hs), torch.stack(cs))
 
 
-def zero_hidden(cfg: Dict, batch: int) -> Hidden:
-    z = torch.zeros(cfg["lstm_layers"], batch, cfg["hidden_dim"])
+def zero_hidden(cfg: Dict, batch: int, dtype: torch.dtype = torch.float32, device=None) -> Hidden:
+    """The zero (h, c) of decoder.py:231-244, in the dtype and on the device of the encoder output it goes with."""
+    z = torch.zeros(cfg["lstm_layers"], batch, cfg["hidden_dim"], dtype=dtype, device=device)
     return z, z.clone()
 
 
@@ -129,7 +130,7 @@ def decode_step(sd: SD, cfg: Dict, enc: torch.Tensor, tok: torch.Tensor,
     B = tok.shape[0]
     emb = F.embedding(tok, sd["decoder.embedding.weight"])              # :214 (B,1,E)
     if hidden is None:                                                  # :231-244 / :253-266
-        hidden = zero_hidden(cfg, B)
+        hidden = zero_hidden(cfg, B, enc.dtype, enc.device)
     h, c = hidden
     if cfg["attention"]:
         ctx = attention_context(sd, h[-1].unsqueeze(1), enc.unsqueeze(1))   # :271
@@ -151,7 +152,7 @@ def decoder_forward(sd: SD, cfg: Dict, enc: torch.Tensor, target: torch.Tensor,
     """
     B, T = target.shape
     emb = F.embedding(target, sd["decoder.embedding.weight"])
-    h, c = zero_hidden(cfg, B)
+    h, c = zero_hidden(cfg, B, enc.dtype, enc.device)
     outs = []
     if cfg["attention"]:
         emb = F.dropout(emb, dropout_p, training)                       # :162
@@ -220,7 +221,7 @@ def greedy_search(sd: SD, cfg: Dict, enc: torch.Tensor, start_id: int, end_id: i
 
 
 def beam_search(sd: SD, cfg: Dict, enc: torch.Tensor, start_id: int, end_id: int,
-                max_length: int, beam_size: int, return_score: bool = False):
+                max_length: int, beam_size: int, return_score: bool = False, stats: Optional[Dict] = None):
     """Seq2SeqModel._beam_search (seq2seq.py:234-298); B must be 1 else greedy (:244-247).
 
     Per live beam: decode_step at B=1 -> log_softmax (fp32) -> topk(k) -> candidates
@@ -228,6 +229,8 @@ def beam_search(sd: SD, cfg: Dict, enc: torch.Tensor, start_id: int, end_id: int
     move to ``completed`` on the NEXT iteration (:258-260); stable sort desc, keep k
     (:279-280); early exit when all k ended (:282-284); best = max(completed) (first
     on ties) else beams[0] (:286-290); strip START / cut at END (:291-297).
+    ``stats`` (a dict), if given, receives "gap": the smallest score difference between neighbours among the
+    k + 1 best candidates of any step -- the decisions another summation order of the logits could flip.
     """
     if enc.shape[0] != 1:
         return greedy_search(sd, cfg, enc, start_id, end_id, max_length, 1.0)
@@ -240,7 +243,7 @@ def beam_search(sd: SD, cfg: Dict, enc: torch.Tensor, start_id: int, end_id: int
             if last == end_id:
                 completed.append(bm)
                 continue
-            out, hid = decode_step(sd, cfg, enc, torch.tensor([[last]], dtype=torch.long), bm["hidden"])
+            out, hid = decode_step(sd, cfg, enc, torch.tensor([[last]], dtype=torch.long, device=enc.device), bm["hidden"])
             logp = torch.log_softmax(out.squeeze(1), dim=-1).squeeze(0)
             tv, ti = torch.topk(logp, beam_size)
             for lp, ix in zip(tv.tolist(), ti.tolist()):
@@ -248,6 +251,9 @@ def beam_search(sd: SD, cfg: Dict, enc: torch.Tensor, start_id: int, end_id: int
         if not cands:
             break
         cands = sorted(cands, key=lambda b: b["score"], reverse=True)
+        if stats is not None:
+            sc = [c["score"] for c in cands[:beam_size + 1]]
+            stats["gap"] = min([stats.get("gap", float("inf"))] + [a - b for a, b in zip(sc[:-1], sc[1:])])
         beams = cands[:beam_size]
         if all(b["tokens"][-1] == end_id for b in beams):
             completed.extend(beams)

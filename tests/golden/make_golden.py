@@ -72,8 +72,16 @@ CONFIGS = {
     "shipped_128x800": (dict(channels=1, img_height=128, img_width=800, embedding_dim=512, hidden_dim=512,
                              lstm_layers=2, attention=True),
                         dict(seed=45, out_scale=12.0, enc_scale=16.0, end_clock=(0.05, 12.0, 6.0))),
+    # past the fixture-sized vocabularies: primary's decoder with V = 1000 (two 512-column passes of the output layer,
+    # padded to 1024) -- no grouped inference or beam kernel takes it
+    "wide_vocab": (dict(vocab_size=1000, attention=True),
+                   dict(seed=52, out_scale=12.0, enc_scale=16.0, end_clock=(0.05, 12.0, 6.0))),
+    # odd everything: V = 777 (247 padding columns of Vp = 1024), E = 36, H = 320 (the backward's 2-group split), L = 3
+    "odd_hidden": (dict(vocab_size=777, embedding_dim=36, hidden_dim=320, lstm_layers=3, attention=True,
+                        channels=1, img_height=16, img_width=32, conv_filters=(4, 8, 16)),
+                   dict(seed=47, out_scale=12.0, enc_scale=16.0, end_clock=(0.05, 12.0, 6.0))),
 }
-BIG = ("primary", "secondary", "ref_test_64x800", "shipped_128x800")
+BIG = ("primary", "secondary", "ref_test_64x800", "shipped_128x800", "wide_vocab")
 
 
 def build_reference(cfg, np_sd):
@@ -121,6 +129,8 @@ def run_config(name, cfg_kw, sd_kw, big):
                 blk += 1
         enc = ref.encoder(imgs)
         out["g1_enc"] = enc.numpy().copy()
+        # the same encoder in float64 (what encoder_fp64.npz holds for the configs that predate this key)
+        out["g1_enc_fp64"] = build_reference(cfg, np_sd).double().encoder(imgs.double()).numpy().copy()
 
         # ---- G2 three consecutive decode_step calls (decoder.py:197-284)
         tok = torch.full((B, 1), START, dtype=torch.long)
@@ -185,7 +195,8 @@ def run_config(name, cfg_kw, sd_kw, big):
     loss = crit(outputs.transpose(1, 2), forms[:, 1:])
     loss.backward()
     names = [n for n, _ in ref.named_parameters()]
-    out["g6_logits" if not big else "g6_logits_sample"] = (outputs.detach().numpy().copy() if not big else sample(outputs))
+    full = not big and outputs.numel() <= 16384          # a sample where the whole tensor would outgrow the fixture
+    out["g6_logits" if full else "g6_logits_sample"] = (outputs.detach().numpy().copy() if full else sample(outputs))
     out["g6_logits_checksum"] = np.array(synth.checksum(outputs.detach().numpy()))
     out["g6_loss"] = np.array(float(loss))
     out["g6_param_names"] = np.array(json.dumps(names))

@@ -11,9 +11,9 @@ from img2latex_amd.model import Seq2SeqModel
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 START, END, PAD = synth.START, synth.END, synth.PAD
-SMALL = ["tiny_l1", "tiny_l2_attn", "odd_dims"]
+SMALL = ["tiny_l1", "tiny_l2_attn", "odd_dims", "odd_hidden"]   # odd_hidden: V 777, E 36, H 320, L 3
 WIDE = ["ref_test_64x800", "shipped_128x800"]      # the reference's own shapes (tests/test_encoder.py:11-42, configs/config.yaml:30-50)
-BIG = ["primary", "secondary"] + WIDE               # fixtures that hold samples instead of whole tensors, T = 24
+BIG = ["primary", "secondary"] + WIDE + ["wide_vocab"]   # fixtures that hold samples instead of whole tensors, T = 24
 ALL = SMALL + BIG
 
 
@@ -87,6 +87,65 @@ def _margin_guard(got, ref_ids, margins, tol):
             assert margins[b, t] < tol, f"row {b} step {t}: ids differ at margin {margins[b, t]}"
             diverged += 1
     return diverged
+
+
+def uniform01(seed, row, step):
+    """Python twin of decode.hip::uniform01 (splitmix64 finaliser of (seed, row, step), 24 bits)."""
+    M = (1 << 64) - 1
+    z = (seed + (((row << 32) | step) * 0x9E3779B97F4A7C15)) & M
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
+    z = z ^ (z >> 31)
+    return np.float32(z >> 40) * np.float32(1.0 / 16777216.0)
+
+
+def check_sampling(decoder, enc, oracle_step, top_k, top_p, temp, seed, steps=6, what=None):
+    """predictor.py:295-331 through i2l_sample_decode: the masked / renormalised distribution equals the one rebuilt
+    from ``oracle_step(tok (B,1) int64 on the host, hidden) -> (logits (B,1,V), hidden)`` replayed along the HIP-sampled
+    tokens; every draw is the inverse-CDF of that distribution at the kernel's documented uniform (draws within 1e-5
+    of a CDF step are not judged); same seed -> same ids."""
+    from img2latex_amd import _lib
+    rows = enc.shape[0]
+    tok0 = torch.full((rows,), START, dtype=torch.int32, device=enc.device)
+    ids, probs = decoder.sample_steps(enc, steps, tok0, temp, top_k, top_p, seed, stop=_lib.STOP_NONE, want_probs=True)
+    ids2, _ = decoder.sample_steps(enc, steps, tok0, temp, top_k, top_p, seed, stop=_lib.STOP_NONE)
+    ids3, _ = decoder.sample_steps(enc, steps, tok0, temp, top_k, top_p, seed + 1, stop=_lib.STOP_NONE)
+    assert torch.equal(ids, ids2)
+    ids_h, probs_h = ids.cpu().numpy(), probs.cpu().numpy()
+    tok = torch.full((rows, 1), START, dtype=torch.long)
+    hidden = None
+    for t in range(steps):
+        with torch.no_grad():
+            out, hidden = oracle_step(tok, hidden)
+        p = torch.softmax(out.squeeze(1) / temp, dim=-1)
+        if top_k > 0:
+            kth = torch.topk(p, min(top_k, p.size(-1)), dim=-1).values[:, -1, None]
+            p = torch.where(p < kth, torch.zeros_like(p), p)
+            p = p / p.sum(-1, keepdim=True)
+        if top_p > 0:
+            sp, si = torch.sort(p, descending=True, stable=True)
+            cum = torch.cumsum(sp, -1)
+            rm = cum > top_p
+            rm[:, 1:] = rm[:, :-1].clone()
+            rm[:, 0] = False
+            p = torch.where(rm.scatter(-1, si, rm), torch.zeros_like(p), p)
+            p = p / p.sum(-1, keepdim=True)
+        want = p.cpu().numpy()
+        close(probs_h[:, t, :], want, 1e-5, what)
+        for b in range(rows):
+            pr = probs_h[b, t].astype(np.float32)
+            assert pr[ids_h[b, t]] > 0
+            u = uniform01(seed, b, t)
+            cdf = np.cumsum(pr.astype(np.float64))
+            j = int(np.searchsorted(cdf, float(u) * cdf[-1], side="right"))
+            lo = cdf[j - 1] if j > 0 else 0.0
+            if min(abs(float(u) * cdf[-1] - lo), abs(cdf[min(j, len(cdf) - 1)] - float(u) * cdf[-1])) > 1e-5:
+                assert j == ids_h[b, t], (b, t, j, ids_h[b, t])
+        tok = torch.from_numpy(ids_h[:, t:t + 1].astype(np.int64))
+    if top_k != 1:
+        assert not torch.equal(ids, ids3)        # a different seed draws different tokens
+    else:
+        assert torch.equal(ids, ids3)            # top-1 sampling is greedy
 
 
 def padded_to_lists(arr, lens):

@@ -83,7 +83,7 @@ def test_decoder_backward_vs_oracle(name, batch):
 def test_ce_kernel_vs_torch():
     torch.manual_seed(0)
     L = _lib.lib()
-    for rows, V in [(7, 37), (48, 512), (301, 50)]:
+    for rows, V in [(7, 37), (48, 512), (301, 50), (33, 513), (9, 1000), (5, 5000)]:     # V > 512: several columns per thread
         logits = torch.randn(rows, V) * 3
         tgt = torch.randint(0, V, (rows,))
         tgt[::5] = PAD
