@@ -143,15 +143,7 @@ __global__ __launch_bounds__(GNT) void beam_group_kernel(BeamGroupParams p) {
     const int l_v = 128 * m + 4 * cq + ((ks >> 2) & 1) * 2 + (ks >> 3);   // the column whose bias this lane adds in E
 
     f32x2 wreg[32][2];
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const float4 t4 = *reinterpret_cast<const float4*>(w.WhhT[0] + (size_t)(8 * j + ke) * G + 4 * unit);
-        wreg[j][0] = f32x2{t4.x, t4.y};
-        wreg[j][1] = f32x2{t4.z, t4.w};
-    }
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        wout_s4[j * GNT + tid] = *reinterpret_cast<const float4*>(w.WoutT + (size_t)(16 * j + ks) * 512 + 128 * m + 4 * cq);
+    load_weight_image<GNT>(wreg, wout_s4, w, unit, ke, 128 * m + 4 * cq, ks, tid);
     for (int idx = tid; idx < BG_NP * 256 * 4; idx += GNT) h_s[idx] = 0.f;
     for (int idx = tid; idx < BG_S * 64; idx += GNT) cs[idx] = 0.f;
     const float l_bias = w.boutP[l_v];
@@ -210,34 +202,8 @@ __global__ __launch_bounds__(GNT) void beam_group_kernel(BeamGroupParams p) {
                 f32x2 acc[4][2];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) { acc[g][0] = splat2(0.f); acc[g][1] = splat2(0.f); }
-                const float4* hq4 = reinterpret_cast<const float4*>(h_s) + pp * 256 + ke;
-                float4 hb[2][4];                            // h is read 4 k ahead of its use (two register sets)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) hb[0][i] = hq4[8 * i];
-#pragma unroll
-                for (int b = 0; b < 8; ++b) {
-                    if (b + 1 < 8) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) hb[(b + 1) & 1][i] = hq4[8 * ((b + 1) * 4 + i)];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) fma_4x4(acc, wreg[b * 4 + i][0], wreg[b * 4 + i][1], hb[b & 1][i]);
-                }
-                const bool b0 = ke & 1, b1 = ke & 2, b2 = ke & 4;
-                float z[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    float wv[2];
-#pragma unroll
-                    for (int rp = 0; rp < 2; ++rp) {
-                        const float ux = rs_level<DPP_HMIRROR>(acc[e][rp].x, acc[2 + e][rp].x, b2);
-                        const float uy = rs_level<DPP_HMIRROR>(acc[e][rp].y, acc[2 + e][rp].y, b2);
-                        wv[rp] = rs_level<DPP_XOR1>(ux, uy, b0);
-                    }
-                    z[e] = rs_level<DPP_XOR2>(wv[0], wv[1], b1);
-                }
-                zr[pp][0] = z[0]; zr[pp][1] = z[1];
+                rec_product4(acc, wreg, reinterpret_cast<const float4*>(h_s) + pp * 256 + ke, [](int) {});
+                fold_gates4(acc, ke, zr[pp]);
                 __builtin_amdgcn_sched_barrier(0);
                 if (pp == 1) b_fetch();
                 __builtin_amdgcn_sched_barrier(0);
@@ -445,42 +411,8 @@ __global__ __launch_bounds__(GNT) void beam_group_kernel(BeamGroupParams p) {
 #pragma unroll
         for (int pp = 0; pp < BG_NP; ++pp) {
             f32x2 pa[4][2];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { pa[c][0] = splat2(0.f); pa[c][1] = splat2(0.f); }
-            const float4* hq4 = reinterpret_cast<const float4*>(h_s) + pp * 256 + ks;
-            float4 wb[2][2], hb[2][2];
-            auto fetch = [&](int set, int b) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    wb[set][i] = wout_s4[(b * 2 + i) * GNT + te];
-                    hb[set][i] = hq4[16 * (b * 2 + i)];
-                }
-            };
-            fetch(0, 0);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                if (b + 1 < 8) fetch((b + 1) & 1, b + 1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const float4 w4 = wb[b & 1][i];
-                    fma_4x4(pa, f32x2{w4.x, w4.y}, f32x2{w4.z, w4.w}, hb[b & 1][i]);
-                }
-            }
-            const bool b0 = ks & 1, b1 = ks & 2, b2 = ks & 4, b3 = ks & 8;
-            float z[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                float wv[2];
-#pragma unroll
-                for (int rp = 0; rp < 2; ++rp) {
-                    const float ux = rs_level<DPP_HMIRROR>(pa[e][rp].x, pa[2 + e][rp].x, b2);
-                    const float uy = rs_level<DPP_HMIRROR>(pa[e][rp].y, pa[2 + e][rp].y, b2);
-                    wv[rp] = rs_level<DPP_XOR1>(ux, uy, b0);
-                }
-                z[e] = rs_level<DPP_XOR2>(wv[0], wv[1], b1);
-            }
-            const float lv = rs_level<DPP_ROR8>(z[0], z[1], b3) + l_bias;
+            logits_product4<GNT>(pa, wout_s4, reinterpret_cast<const float4*>(h_s) + pp * 256 + ks, te);
+            const float lv = fold_logits4(pa, ks) + l_bias;
             lg[(4 * pp + l_row) * 128 + 4 * cq + l_col] = lv;
             __builtin_amdgcn_sched_barrier(0);
         }

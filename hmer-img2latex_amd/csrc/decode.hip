@@ -239,7 +239,6 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned row
 }
 
 #include "decode_group.inc.h"
-#include "decode_group8.inc.h"
 #include "decode_group16.inc.h"
 #include "beam_group.inc.h"
 
@@ -740,15 +739,20 @@ struct GroupVariant {
     size_t lds, xchg_per_group;
 };
 constexpr int GROUP_VARIANTS = 3;
+template <int M>   // decode_group_kernel<M> (decode_group.inc.h)
+constexpr GroupVariant grouped_variant(int flag) {
+    using S = GroupShape<M>;
+    return {decode_group_kernel<M>, flag, M, S::NT, S::LDS, S::XCHG_PER_GROUP};
+}
 // (a table inside a function: the library keeps no data symbols beyond its attribute caches)
 constexpr GroupVariant group_variant(int i) {
     constexpr GroupVariant table[GROUP_VARIANTS] = {
         // sixteen members x sixteen rows, the per-step products on the matrix cores (decode_group16.inc.h)
         {decode_group16_kernel, I2L_FLAG_DECODE_GROUP16, G16Q, G16NT, GRP16_LDS, GROUP16_XCHG_PER_GROUP},
         // eight members x eight rows: one wave per SIMD and ~80 KB of LDS per CU, i.e. room for a conv workgroup beside it
-        {decode_group8_kernel, I2L_FLAG_DECODE_GROUP8, G8Q, G8NT, GRP8_LDS, GROUP8_XCHG_PER_GROUP},
+        grouped_variant<8>(I2L_FLAG_DECODE_GROUP8),
         // four members x four rows (decode_group.inc.h)
-        {decode_group_kernel, 0, GQ, GNT, GRP_LDS, GROUP_XCHG_PER_GROUP},
+        grouped_variant<4>(0),
     };
     return table[i];
 }

@@ -1,5 +1,5 @@
 // Grouped greedy decode on the MATRIX CORES: SIXTEEN members x SIXTEEN rows per group (included by decode.hip inside its
-// anonymous namespace, after decode_group8.inc.h).  r04; reference decoder.py:247-250,277-280 (LSTM gates, Linear(H -> V)),
+// anonymous namespace, after decode_group.inc.h).  r04; reference decoder.py:247-250,277-280 (LSTM gates, Linear(H -> V)),
 // seq2seq.py:210-221 (arg max loop).
 //
 // Why: in the co-resident pipeline (decode(i) beside the conv workgroups of encoder(i + 1) on every CU) the 8-member
@@ -30,7 +30,7 @@
 //      take the arg max over the 16 lanes of a row, LDS atomic max across the two waves, and the later one publishes the
 //      member's 16 candidates (exchange 2); waves 2, 3 are already in A of step t + 1.
 // Tags, two buffers by step parity, bounded polls, placement measurement, failure marking (ids -3), residency signal:
-// exactly as decode_group8_kernel.  Supported: ids out (both stop rules, temperature, arg max of logits / of softmax);
+// exactly as decode_group_kernel<8>.  Supported: ids out (both stop rules, temperature, arg max of logits / of softmax);
 // no logits output, no forced tokens, no initial / returned state.
 #include "bf16_split.inc.h"
 

@@ -953,7 +953,7 @@ def test_encoder_reuses_packed_filters_until_a_weight_changes():
 @pytest.mark.parametrize("members", [8, 16])
 @pytest.mark.parametrize("fname", ["primary_cfg2_clock", "primary_cfg2"])
 def test_group8_decode_ids_vs_reference(fname, members):
-    """decode_group8_kernel (8 members x 8 rows per group: one wave per SIMD, ~80 KB of LDS, the footprint that shares a
+    """decode_group_kernel<8> (8 members x 8 rows per group: one wave per SIMD, ~80 KB of LDS, the footprint that shares a
     CU with a conv workgroup) and decode_group16_kernel (r04: 16 members x 16 rows, the per-step products on the matrix
     cores as split-bf16 MFMA bursts) on BASELINE configs[1] at full size: ids against the reference's fixture with the
     margin guard, both stop rules, temperature, ragged batch sizes (last group partly empty), the forced time-out path."""
