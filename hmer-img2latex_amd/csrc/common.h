@@ -30,6 +30,7 @@ static inline size_t i2l_align(size_t x, size_t a = 256) { return (x + a - 1) / 
 
 // ---- generic fp32 MFMA GEMM (gemm.hip):
 //   C[m][n] (+)= alpha * act(sum_z sum_k A_z(m,k) * W_z(n,k) + bias[n] + bias2[n])
+//   with scale / residual (the eval-mode conv + BatchNorm unit): act(fmaf(sum, scale[n], bias[n]) + bias2[n] + residual[m][n])
 //   a_kc != 0: A(m,k) = A[m*lda + k] (K-contiguous) else A[k*lda + m];  same for W with n.
 //   perm_h > 0: output column n = g*perm_h + j is stored at column 4*j + g (LSTM gate interleave).
 struct GemmArgs {
@@ -52,6 +53,8 @@ struct GemmArgs {
     //   A(m, k = y*conv_w + x) = (pool_y > 0 && pool_am == 2*(y&1) + (x&1)) ? A_pooled[m][y/2][x/2] : 0      (conv_w % 8 == 0)
     const float* pool_y;
     const unsigned char* pool_am;
+    const float* scale;       // may be null; per output column, multiplies the complete K sum: v = fmaf(sum, scale[n], bias[n])
+    const float* residual;    // may be null; addressed as C is (row-major, ldc, perm_h), added after scale / bias, before the ReLU
 };
 static inline GemmArgs gemm_args() {
     GemmArgs g{};

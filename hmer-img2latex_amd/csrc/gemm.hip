@@ -1,5 +1,7 @@
 // fp32 GEMM on the gfx950 matrix cores:
 //     C[m][n] (+)= alpha * act( sum_z sum_k A_z(m,k) * W_z(n,k)  + bias[n] )
+// or, with a per-column scale and a residual matrix (eval-mode conv + BatchNorm + shortcut in one launch),
+//     C[m][n] (+)= alpha * act( fmaf(sum, scale[n], bias[n]) + residual[m][n] )
 //
 // Operands may be K-contiguous (A(m,k) = A[m*lda + k], how PyTorch stores nn.Linear / nn.LSTM
 // weights and activations: y = x @ W^T needs no transpose) or M/N-contiguous
@@ -42,12 +44,20 @@ __device__ __forceinline__ int perm_col(int n, int perm_h) {
     return 4 * j + g;
 }
 
+// v is the COMPLETE K sum (the direct epilogue's accumulator or the slab sum), so a result does not depend on whether K
+// was split.  Without scale / residual this is the arithmetic it always was (bias added, not fused).  FUSED = false
+// compiles the two out: the gathered-operand instantiations of the split-bf16 kernel sit at the scalar register limit and
+// never see them (run_bf16x3 refuses the combination).
+template <bool FUSED = true>
 __device__ __forceinline__ void epilogue_store(const GemmArgs& g, int m, int n, float v) {
-    if (g.bias) v += g.bias[n];
+    const size_t o = (size_t)m * g.ldc + perm_col(n, g.perm_h);
+    if (FUSED && g.scale) v = fmaf(v, g.scale[n], g.bias ? g.bias[n] : 0.f);
+    else if (g.bias) v += g.bias[n];
     if (g.bias2) v += g.bias2[n];
+    if (FUSED && g.residual) v += g.residual[o];
     if (g.relu) v = fmaxf(v, 0.f);
     v *= g.alpha;
-    float* c = g.C + (size_t)m * g.ldc + perm_col(n, g.perm_h);
+    float* c = g.C + o;
     *c = g.accumulate ? *c + v : v;
 }
 
@@ -470,7 +480,7 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16x3_kernel(GemmArgs g, float* 
             const int row = m0 + wm * 32 * MT + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
             if (row < g.M && n < g.N) {
                 if (S > 1) partial[(size_t)slice * slab_stride(g.M, g.N) + (size_t)row * g.N + n] = acc[m][r];
-                else epilogue_store(g, row, n, acc[m][r]);
+                else epilogue_store<PLAIN>(g, row, n, acc[m][r]);
             }
         }
 }
@@ -517,6 +527,7 @@ int run_bf16x3(const GemmArgs& g, void* ws, size_t ws_bytes, hipStream_t s) {
     dim3 grid((unsigned)blocks);
     float* wsf = static_cast<float*>(ws);
     const bool plain = g.nz == 1 && !g.pool_y && g.conv_h <= 0;
+    if (!plain && (g.scale || g.residual)) return I2L_ERR_UNSUPPORTED;   // the gathered-operand kernels' epilogue has neither
 #define I2L_LAUNCH_BF16X3(AK, WK)                                                                                          \
     do {                                                                                                                \
         if (mt == 2 && plain) hipLaunchKernelGGL((gemm_bf16x3_kernel<AK, WK, 2, true>), grid, dim3(256), 0, s, g, wsf, kc, S, tiles_n, tiles); \

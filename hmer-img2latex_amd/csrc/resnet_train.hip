@@ -16,6 +16,8 @@
 //              running statistics (momentum, unbiased variance), y = act(gamma * (z - mean) * invstd + beta + residual)
 //   backward   dy (fp32) -> ReLU mask from y, per-channel sums, dz = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat)),
 //              dgamma, dbeta, the masked gradient for the residual branch
+//   eval       the same units under model.eval() (ResNetEncoder.eval_precision = "fp32"): conv + folded running-statistics
+//              BatchNorm + residual + ReLU as ONE GEMM launch, the three in its epilogue (i2l_conv_bn_act_f32_fwd)
 //   pooling    max-pool 3x3/2 forward / backward (first maximum of the window wins, as ATen), global average pool both ways.
 // HBM-bound elementwise / reduction kernels: 16-byte accesses, one pass per tensor.
 #include "common.h"
@@ -429,14 +431,11 @@ extern "C" size_t i2l_conv_f32_workspace_bytes(int x_kind, int B, int H, int W, 
     return col + dcol + gemm + 256;
 }
 
-extern "C" int i2l_conv_f32_fwd(const float* x, int x_kind, const float* w, float* z, int B, int H, int W, int Cin, int Cout,
-                                int kh, int kw, int stride, int pad, void* workspace, size_t workspace_bytes, int flags,
-                                i2l_stream_t stream) {
-    ConvGeom c;
-    if (!x || !w || !z || Cout <= 0 || !conv_geom(x_kind, B, H, W, Cin, kh, kw, stride, pad, &c)) return I2L_ERR_ARG;
-    if (!workspace || workspace_bytes < i2l_conv_f32_workspace_bytes(x_kind, B, H, W, Cin, Cout, kh, kw, stride, pad, 0))
-        return I2L_ERR_WORKSPACE;
-    hipStream_t s = i2l_s(stream);
+namespace {
+// the forward convolution as one GEMM; scale / shift / residual / relu (all optional) go into its epilogue
+int conv_f32_run(const float* x, int x_kind, const float* w, const float* scale, const float* shift, const float* residual,
+                 int relu, float* y, int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                 const ConvGeom& c, void* workspace, size_t workspace_bytes, int flags, hipStream_t s) {
     const int M = (int)c.M, Kc = (int)c.Kc;
     char* p = static_cast<char*>(workspace);
     const float* col = x;
@@ -447,13 +446,66 @@ extern "C" int i2l_conv_f32_fwd(const float* x, int x_kind, const float* w, floa
         if (rc != I2L_OK) return rc;
         col = cimg;
     }
-    GemmArgs g = gemm_args();                         // z[m][n] = sum_k col[m][k] * w[n][k]
+    GemmArgs g = gemm_args();                         // y[m][n] = act(scale[n] * sum_k col[m][k] * w[n][k] + shift[n] + residual[m][n])
     g.split_bf16 = (flags & I2L_FLAG_EXACT_FP32) ? 0 : 1;
     g.A = col; g.lda = Kc;
     g.W = w; g.ldw = Kc;
-    g.C = z; g.ldc = Cout;
+    g.scale = scale; g.bias = shift; g.residual = residual;
+    g.relu = relu ? 1 : 0;
+    g.C = y; g.ldc = Cout;
     g.M = M; g.N = Cout; g.K = Kc;
     return i2l_gemm(g, p, workspace_bytes - (size_t)(p - static_cast<char*>(workspace)), s);
+}
+}  // namespace
+
+extern "C" int i2l_conv_f32_fwd(const float* x, int x_kind, const float* w, float* z, int B, int H, int W, int Cin, int Cout,
+                                int kh, int kw, int stride, int pad, void* workspace, size_t workspace_bytes, int flags,
+                                i2l_stream_t stream) {
+    ConvGeom c;
+    if (!x || !w || !z || Cout <= 0 || !conv_geom(x_kind, B, H, W, Cin, kh, kw, stride, pad, &c)) return I2L_ERR_ARG;
+    if (!workspace || workspace_bytes < i2l_conv_f32_workspace_bytes(x_kind, B, H, W, Cin, Cout, kh, kw, stride, pad, 0))
+        return I2L_ERR_WORKSPACE;
+    return conv_f32_run(x, x_kind, w, nullptr, nullptr, nullptr, 0, z, B, H, W, Cin, Cout, kh, kw, stride, pad, c, workspace,
+                        workspace_bytes, flags, i2l_s(stream));
+}
+
+// ---------------------------------------------------------------- eval-mode unit: conv + running-statistics BatchNorm
+// (+ residual) (+ ReLU) in ONE GEMM launch (encoder.py:185-199,242 under model.eval())
+namespace {
+__global__ __launch_bounds__(256) void bn_eval_fold_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           const float* __restrict__ mean, const float* __restrict__ var, float eps,
+                                                           float* __restrict__ scale, float* __restrict__ shift, int C) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    // in double, each output rounded once; the shift is taken against the ROUNDED scale, so that
+    // fmaf(z, scale, shift) = scale * (z - mean) + beta up to the shift's own rounding
+    const float sc = (float)((double)gamma[c] / sqrt((double)var[c] + (double)eps));
+    scale[c] = sc;
+    shift[c] = (float)((double)beta[c] - (double)mean[c] * (double)sc);
+}
+}  // namespace
+
+extern "C" int i2l_bn_eval_fold_f32(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                                    float eps, float* scale_out, float* shift_out, int C, i2l_stream_t stream) {
+    if (!gamma || !beta || !running_mean || !running_var || !scale_out || !shift_out || C <= 0) return I2L_ERR_ARG;
+    hipLaunchKernelGGL(bn_eval_fold_kernel, dim3(i2l_cdiv(C, 256)), dim3(256), 0, i2l_s(stream), gamma, beta, running_mean,
+                       running_var, eps, scale_out, shift_out, C);
+    I2L_CHECK_LAUNCH();
+    return I2L_OK;
+}
+
+extern "C" int i2l_conv_bn_act_f32_fwd(const float* x, int x_kind, const float* w, const float* scale, const float* shift,
+                                       const float* residual, float* y, int B, int H, int W, int Cin, int Cout, int kh, int kw,
+                                       int stride, int pad, int relu, void* workspace, size_t workspace_bytes, int flags,
+                                       i2l_stream_t stream) {
+    if (!x || !w || !scale || !shift || !y) return I2L_ERR_ARG;
+    if (x_kind != 1 && x_kind != 2) return I2L_ERR_UNSUPPORTED;          // NHWC bf16 input belongs to i2l_conv_bn_act_bf16_fwd
+    ConvGeom c;
+    if (Cout <= 0 || !conv_geom(x_kind, B, H, W, Cin, kh, kw, stride, pad, &c)) return I2L_ERR_ARG;
+    if (!workspace || workspace_bytes < i2l_conv_f32_workspace_bytes(x_kind, B, H, W, Cin, Cout, kh, kw, stride, pad, 0))
+        return I2L_ERR_WORKSPACE;
+    return conv_f32_run(x, x_kind, w, scale, shift, residual, relu, y, B, H, W, Cin, Cout, kh, kw, stride, pad, c, workspace,
+                        workspace_bytes, flags, i2l_s(stream));
 }
 
 extern "C" int i2l_conv_f32_bwd(const float* x, int x_kind, const float* w, const float* dz, float* dx, float* dw, int B, int H,

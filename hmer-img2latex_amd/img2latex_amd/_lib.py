@@ -135,6 +135,9 @@ _SIGNATURES.update({
     "i2l_conv_f32_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_size_t, c_int, c_void_p]),
     "i2l_conv_f32_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 +
                          [c_void_p, c_size_t, c_int, c_void_p]),
+    "i2l_bn_eval_fold_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    "i2l_conv_bn_act_f32_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 10 +
+                                [c_void_p, c_size_t, c_int, c_void_p]),
     "i2l_im2col_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "i2l_col2im_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "i2l_maxpool3x3s2_f32_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

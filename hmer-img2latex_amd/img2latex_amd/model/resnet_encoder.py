@@ -9,7 +9,14 @@ remote ImageNet weights (encoder.py:185-194); offline we use torchvision's rando
 expect real weights to arrive through ``load_state_dict``.
 
 Inference (``.eval()``): BatchNorm uses its running statistics, folded into the conv epilogue; convolutions run
-in bf16 on the matrix cores with fp32 accumulation (BASELINE config 5).
+in bf16 on the matrix cores with fp32 accumulation (BASELINE config 5).  That is ``eval_precision = "bf16"``, the default.
+With ``eval_precision = "fp32"`` the eval-mode trunk runs at fp32 grade, as the reference's (encoder.py:231-249 in its fp32
+branch, trainer.py:334-343): NHWC fp32 activations, each conv unit ONE launch of ``i2l_conv_bn_act_f32_fwd`` -- the
+split-bf16 matrix-core GEMM (``kernel_flags & FLAG_EXACT_FP32``: the fp32 MFMA GEMM) with the folded running-statistics
+BatchNorm, the shortcut add and the ReLU in its epilogue.  Its results do not depend on tile-shape flags, and it is the
+arithmetic a model trained here was optimised in: set it on ``model.encoder`` before validating or predicting with one.
+``Seq2SeqModel``, ``Predictor``, ``GreedyPipeline`` and ``training.validate`` only see the (B, E) fp32 output, so they work
+with either value unchanged.
 
 Training (``.train()``, r03; fp32 grade since r04): every BatchNorm2d normalises with BATCH statistics and updates its
 running statistics (also the frozen ones: ``freeze_backbone`` only clears ``requires_grad``, encoder.py:201-210); the
@@ -121,6 +128,18 @@ class ResNetEncoder(nn.Module):
         # 103 - 125 at B=256: one workgroup per CU walks its tiles phase by phase; profiles/r04/resnet_patch.txt, 8)
         self.fuse_joins = False
         self.trace_bwd = None      # a list here receives every unit's backward: dict(unit, dy, dz, dx, dres, names)
+        self.eval_precision = "bf16"   # "fp32": the eval-mode trunk at fp32 grade (_trunk_eval_f32); not part of the state_dict
+        self._folded = {}          # id(bn) -> (version key, (2, C) fp32 folded scale / shift, fold-done event, streams ordered behind it)
+
+    @property
+    def eval_precision(self) -> str:
+        return self._eval_precision
+
+    @eval_precision.setter
+    def eval_precision(self, value: str) -> None:
+        if value not in ("bf16", "fp32"):
+            raise ValueError(f"eval_precision must be 'bf16' or 'fp32', got {value!r}")
+        self._eval_precision = value
 
     # ------------------------------------------------------------------
     def _workspace(self, nbytes: int, device) -> torch.Tensor:
@@ -200,6 +219,8 @@ class ResNetEncoder(nn.Module):
         """(B,3,H,W) fp32 -> (B, 512|2048) fp32: the torchvision trunk incl. global average pooling."""
         if self.training:
             return self._trunk_train(x, None)
+        if self.eval_precision == "fp32":
+            return self._trunk_eval_f32(x)
         x = _lib.require_gpu(x, "images")
         B, C, H, W = x.shape
         if C != 3:
@@ -242,6 +263,82 @@ class ResNetEncoder(nn.Module):
         Bf, Hf, Wf, Cf = shp
         feat = torch.empty((B, Cf), dtype=torch.float32, device=x.device)
         _lib.check(L.i2l_global_avgpool_bf16_fwd(h.data_ptr(), feat.data_ptr(), B, Hf, Wf, Cf, _lib.stream_ptr()), "avgpool")
+        return feat
+
+    # ------------------------------------------------------------------ eval mode at fp32 grade (running statistics)
+    def _folded_bn(self, bn: nn.BatchNorm2d, device) -> torch.Tensor:
+        """(2, C) fp32: scale = gamma / sqrt(running_var + eps) and shift = beta - running_mean * scale
+        (i2l_bn_eval_fold_f32), redone whenever a BatchNorm parameter or statistic changed -- the rule of _packed_weights."""
+        tensors = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        key = tuple((t.data_ptr(), t._version) for t in tensors)
+        stream = _lib.stream_ptr()
+        hit = self._folded.get(id(bn))
+        if self.cache_packed_weights and hit is not None and hit[0] == key and hit[1].device == device:
+            if stream not in hit[3]:                 # folded on another stream (a pipeline's second encoder stream): order once
+                torch.cuda.current_stream().wait_event(hit[2])
+                hit[3].add(stream)
+            return hit[1]
+        C = bn.num_features
+        buf = torch.empty((2, C), dtype=torch.float32, device=device)
+        _lib.check(_lib.lib().i2l_bn_eval_fold_f32(bn.weight.detach().data_ptr(), bn.bias.detach().data_ptr(),
+                                                   bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps),
+                                                   buf[0].data_ptr(), buf[1].data_ptr(), C, stream), "bn_eval_fold_f32")
+        done = torch.cuda.Event()
+        done.record()
+        self._folded[id(bn)] = (key, buf, done, {stream})
+        return buf
+
+    def _conv_bn_f32(self, x, shape, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool, residual=None, nchw=False):
+        """One conv + running-statistics BatchNorm (+ residual) (+ ReLU) launch; x and y are NHWC fp32 (or x the NCHW images).
+        Of ``kernel_flags`` only FLAG_EXACT_FP32 reaches the kernel: the others are tile-shape hints of the bf16 trunk."""
+        B, H, W, Cin = shape
+        k, s, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        Ho, Wo = (H + 2 * pd - k) // s + 1, (W + 2 * pd - k) // s + 1
+        L = _lib.lib()
+        co, kind = conv.out_channels, 2 if nchw else 1
+        fold = self._folded_bn(bn, x.device)
+        y = torch.empty((B, Ho, Wo, co), dtype=torch.float32, device=x.device)
+        nbytes = L.i2l_conv_f32_workspace_bytes(kind, B, H, W, Cin, co, k, k, s, pd, 0)
+        ws = self._workspace(nbytes, x.device)
+        _lib.check(L.i2l_conv_bn_act_f32_fwd(x.data_ptr(), kind, conv.weight.detach().data_ptr(), fold[0].data_ptr(),
+                                             fold[1].data_ptr(), _lib.ptr(residual), y.data_ptr(), B, H, W, Cin, co, k, k, s,
+                                             pd, 1 if relu else 0, ws.data_ptr(), nbytes,
+                                             self.kernel_flags & _lib.FLAG_EXACT_FP32, _lib.stream_ptr()),
+                   "conv_bn_act_f32_fwd")
+        if self.trace is not None:
+            self.trace.append((conv, bn, x, residual, y, relu, nchw))
+        return y, (B, Ho, Wo, co)
+
+    def _trunk_eval_f32(self, x: torch.Tensor) -> torch.Tensor:
+        """The trunk under model.eval() with eval_precision = "fp32": the block structure of _trunk_train, one launch per
+        conv unit, no tape, and nothing written to a BatchNorm buffer."""
+        x = _lib.require_gpu(x, "images")
+        B, C, H, W = x.shape
+        if C != 3:
+            raise RuntimeError(f"ResNet expects 3-channel images, got {C}")
+        L = _lib.lib()
+        m = self.resnet
+        _lib.mark("begin")
+        h, shp = self._conv_bn_f32(x, (B, H, W, 3), m[0], m[1], True, nchw=True)
+        Bh, Hh, Wh, Ch = shp
+        Ho, Wo = (Hh - 1) // 2 + 1, (Wh - 1) // 2 + 1
+        p = torch.empty((B, Ho, Wo, Ch), dtype=torch.float32, device=x.device)
+        _lib.check(L.i2l_maxpool3x3s2_f32_fwd(h.data_ptr(), p.data_ptr(), B, Hh, Wh, Ch, _lib.stream_ptr()), "maxpool")
+        h, shp = p, (B, Ho, Wo, Ch)
+        for li in range(4, 8):
+            for blk in m[li]:
+                identity = h
+                o, s1 = self._conv_bn_f32(h, shp, blk.conv1, blk.bn1, True)
+                if isinstance(blk, _Bottleneck):
+                    o, s1 = self._conv_bn_f32(o, s1, blk.conv2, blk.bn2, True)
+                if blk.downsample is not None:
+                    identity, _ = self._conv_bn_f32(h, shp, blk.downsample[0], blk.downsample[1], False)
+                last = (blk.conv3, blk.bn3) if isinstance(blk, _Bottleneck) else (blk.conv2, blk.bn2)
+                h, shp = self._conv_bn_f32(o, s1, last[0], last[1], True, residual=identity)
+            _lib.mark(f"layer{li - 3}")
+        Bf, Hf, Wf, Cf = shp
+        feat = torch.empty((B, Cf), dtype=torch.float32, device=x.device)
+        _lib.check(L.i2l_global_avgpool_f32_fwd(h.data_ptr(), feat.data_ptr(), B, Hf, Wf, Cf, _lib.stream_ptr()), "avgpool")
         return feat
 
     # ------------------------------------------------------------------ training mode (batch statistics, backward)

@@ -58,7 +58,8 @@ class Seq2SeqModel(nn.Module):
     # ---------------------------------------------------------------- inference
     def inference(self, image: torch.Tensor, start_token_id: int, end_token_id: int, max_length: int = None,
                   temperature: float = None, top_k: int = None, top_p: float = None, beam_size: int = None):
-        """seq2seq.py:124-190: List[int] for one image, List[List[int]] for a batch."""
+        """seq2seq.py:124-190: List[int] for one image, List[List[int]] for a batch.  (A ResNet encoder runs the eval
+        trunk its ``eval_precision`` selects; nothing here depends on which.)"""
         max_length = 150 if max_length is None else max_length
         temperature = 1.0 if temperature is None else temperature
         top_k = 0 if top_k is None else top_k

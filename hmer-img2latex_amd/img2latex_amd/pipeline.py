@@ -28,7 +28,11 @@ from . import _lib
 
 
 class GreedyPipeline:
-    """submit(images) enqueues one batch; results come back in order from collect()."""
+    """submit(images) enqueues one batch; results come back in order from collect().
+
+    A ResNet encoder with ``eval_precision = "fp32"`` works unchanged: the pipeline sees (B, E) fp32 features, and the
+    multi-stream tile-shape flags it ORs into ``encoder.kernel_flags`` are hints of the bf16 trunk that the fp32 trunk
+    ignores (same bits with and without them)."""
 
     def __init__(self, model, start_token_id: int, end_token_id: int, max_length: int = 150,
                  temperature: float = 1.0, depth: int = 3, rows_per_workgroup: int = 2, decode_streams: int = 1,

@@ -198,7 +198,9 @@ class Predictor:
         """``predict_batch_ids`` (the greedy branch: argmax of softmax, sticky stop) for a STREAM of image batches, through
         ``GreedyPipeline``: the decode of batch i shares the GPU with the encoder of batch i + 1 (two batches in flight, the
         schedule bench.py times).  Yields one ``List[List[int]]`` per batch, in order, equal to what ``predict_batch_ids``
-        returns for that batch (up to fp32 near-ties between the two decode kernels)."""
+        returns for that batch (up to fp32 near-ties between the two decode kernels).  A ResNet encoder's bf16 trunk also
+        picks other tile shapes with two trunks in flight, which can move ids; with ``model.encoder.eval_precision =
+        "fp32"`` the features of the two paths are bit-identical."""
         from ..pipeline import GreedyPipeline
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
         n_enc = 2 if hasattr(self.model.encoder, "_trunk_train") else 1      # ResNet trunk: two in flight

@@ -195,7 +195,9 @@ def validate(model, loader: Iterable, pad_token_id: int, bleu_batches: int = 10,
              rng=None, epoch: int = 0, step: int = 0) -> Dict:
     """Trainer.validate over any sized iterable of {"images", "formulas"} batches (``len(loader)`` = total_batches,
     as trainer.py:490).  A grouped-decode timeout repeats the pass once on the row-per-workgroup kernels, with the
-    RNG restored to where this call found it (when it has getstate / setstate) so the same batches are sampled."""
+    RNG restored to where this call found it (when it has getstate / setstate) so the same batches are sampled.
+    A resnet_lstm model is validated through whatever ``model.encoder.eval_precision`` says ("bf16" by default); set it
+    to "fp32" for a model trained here, so that val_loss comes from the arithmetic being optimised."""
     rng = _random if rng is None else rng
     state = rng.getstate() if hasattr(rng, "getstate") else None
 

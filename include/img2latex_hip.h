@@ -243,6 +243,27 @@ int i2l_bn_train_bwd_f32(const float* dy, const float* y_relu, const float* z, c
                          const float* save_invstd, float* dz, float* dgamma, float* dbeta, float* dres,
                          int dres_accumulate, int64_t M, int C, void* workspace, size_t workspace_bytes,
                          i2l_stream_t stream);
+/* The same trunk under model.eval() at fp32 grade (encoder.py:185-199 builds it, :242 runs it; the reference's fp32
+ * branch, trainer.py:334-343): every unit of torchvision's BasicBlock / Bottleneck -- conv, BatchNorm2d on its RUNNING
+ * statistics, the shortcut add of the block's last unit, ReLU -- is ONE GEMM launch whose epilogue finalises an element as
+ *   v = fmaf(sum_k, scale[n], shift[n]);  v += residual[m][n];  v = relu ? max(v, 0) : v
+ * on the complete K sum (after the deterministic slab reduction where K is split: the result does not depend on the split).
+ *
+ * i2l_bn_eval_fold_f32 (encoder.py:185-199: the nn.BatchNorm2d layers of the torchvision trunk, in eval mode):
+ *   scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale, evaluated in double and rounded once
+ *   to fp32 each (the shift against the rounded scale), so the fold adds no error of its own; all arrays (C) fp32.
+ * i2l_conv_bn_act_f32_fwd (encoder.py:185-199,242: conv1/bn1/relu, the blocks' convN/bnN and downsample.0/.1):
+ *   y = act(scale * conv(x, w) + shift + residual), y and residual (may be NULL) (B,Ho,Wo,Cout) NHWC fp32; x, x_kind
+ *   (1 = NHWC fp32, 2 = NCHW fp32), w, flags (I2L_FLAG_EXACT_FP32: fp32 MFMA GEMM) and the workspace
+ *   (i2l_conv_f32_workspace_bytes(..., backward_dx = 0)) as i2l_conv_f32_fwd.  Refused before any launch: a NULL x, w,
+ *   scale, shift or y and a non-positive dimension (I2L_ERR_ARG), x_kind outside {1, 2} (I2L_ERR_UNSUPPORTED), a
+ *   missing or too small workspace (I2L_ERR_WORKSPACE). */
+int i2l_bn_eval_fold_f32(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                         float eps, float* scale_out, float* shift_out, int C, i2l_stream_t stream);
+int i2l_conv_bn_act_f32_fwd(const float* x, int x_kind, const float* w, const float* scale, const float* shift,
+                            const float* residual, float* y, int B, int H, int W, int Cin, int Cout, int kh, int kw,
+                            int stride, int pad, int relu, void* workspace, size_t workspace_bytes, int flags,
+                            i2l_stream_t stream);
 /* The two halves of the convolution entry points above, on their own: col (B*Ho*Wo, Cin*kh*kw) fp32 with the column
  * order (ci, ky, kx) of the weight tensor, and the deterministic gather of a column-image gradient back to
  * dx (B,H,W,Cin) NHWC fp32.  x_kind: 0 = NHWC bf16, 1 = NHWC fp32, 2 = NCHW fp32. */
