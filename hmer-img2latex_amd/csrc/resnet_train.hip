@@ -37,12 +37,9 @@ __device__ __forceinline__ void store8(float* __restrict__ p, const float (&v)[8
     *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
 }
 
-// Per-channel partial sums over a slab of rows.  Thread = (row lane r of 256 / CG, channel group of 8 channels);
-// backward (MODE 1): (sum g, sum g * xhat) with g = dy masked by y > 0.  The forward statistics have their own kernel
-// below: (sum d, sum d^2) with d = z - c, c = the channel's value in ROW 0 of the matrix -- a shift of the order of the mean,
-// so that the variance comes out of ONE pass without the cancellation of sum z^2 / M - mean^2 (r04 first used a second
-// pass over z - mean: two more launches per unit).
-template <int MODE>
+// Per-channel partial sums of the BatchNorm BACKWARD over a slab of rows: (sum g, sum g * xhat) with g = dy masked by
+// y > 0.  Thread = (row lane r of 256 / CG, channel group of 8 channels).  The forward statistics have their own kernel,
+// bn_stats_partial_kernel below.
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ z, const float* __restrict__ dy,
                                                          const float* __restrict__ y, const float* __restrict__ mean,
                                                          const float* __restrict__ invstd, long M, int C,
@@ -60,7 +57,7 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
 #pragma unroll
         for (int j = 0; j < 8; ++j) s0[j] = s1[j] = 0.f;
         float mu[8], is[8];
-        if (MODE == 1 && cg < groups && rl < lanes)
+        if (cg < groups && rl < lanes)
 #pragma unroll
             for (int j = 0; j < 8; ++j) { mu[j] = mean[cg * 8 + j]; is[j] = invstd[cg * 8 + j]; }
         if (cg < groups && rl < lanes) {
@@ -97,8 +94,11 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
     }
 }
 
-// The forward statistics' partial sums (sum d, sum d^2 with d = z - row 0, see above) accumulated and stored in DOUBLE: the
-// kernel is bound by reading z once, the fp64 adds are free, and the one-pass variance then keeps ~1e-7 whatever the shift.
+// The forward statistics' partial sums, same thread layout: (sum d, sum d^2) with d = z - c, c = the channel's value in ROW 0
+// of the matrix -- a shift of the order of the mean, so that the variance comes out of ONE pass without the cancellation of
+// sum z^2 / M - mean^2 (r04 first used a second pass over z - mean: two more launches per unit).  Accumulated and stored in
+// DOUBLE: the kernel is bound by reading z once, the fp64 adds are free, and the one-pass variance then keeps ~1e-7 whatever
+// the shift.
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __restrict__ z, long M, int C, double* __restrict__ part) {
     __shared__ double red[2][256][8];
     const int groups = C / 8;
@@ -606,7 +606,7 @@ extern "C" int i2l_bn_train_bwd_f32(const float* dy, const float* y_relu, const 
     const int slabs = (int)((M + SLAB_ROWS - 1) / SLAB_ROWS);
     float* part = static_cast<float*>(workspace);
     float* sums = reinterpret_cast<float*>(static_cast<char*>(workspace) + i2l_align((size_t)slabs * 2 * C * sizeof(float)));
-    hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(slabs), dim3(256), 0, s, z, dy, y_relu, save_mean, save_invstd, (long)M, C, part);
+    hipLaunchKernelGGL(bn_partial_kernel, dim3(slabs), dim3(256), 0, s, z, dy, y_relu, save_mean, save_invstd, (long)M, C, part);
     I2L_CHECK_LAUNCH();
     hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(i2l_cdiv(C, 32)), dim3(256), 0, s, part, slabs, C, sums, dgamma, dbeta);
     I2L_CHECK_LAUNCH();

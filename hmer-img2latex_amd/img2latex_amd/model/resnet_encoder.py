@@ -25,6 +25,12 @@ split-bf16 matrix-core GEMM, i.e. the arithmetic of the reference's fp32 branch)
 through the HIP gradient kernels (csrc/resnet_train.hip): BatchNorm / ReLU / residual backward, conv weight and data
 gradients as GEMMs over an explicit im2col image, max-pool and average-pool backward.  Gradients stop at the first unit that has a trainable
 parameter: with the default ``freeze_backbone=True`` that is layer4.
+
+The three forward paths (bf16 eval, fp32 eval, training) are ONE walk of the module tree, ``_walk``, driven by a row of
+``_PATHS``: the per-unit launcher (``_conv_bn`` / ``_conv_bn_f32`` / ``_conv_bn_train``), the activation dtype and the two pool
+entry points.  The weight-derived device images of the eval paths (packed bf16 filters, folded fp32 BatchNorm) live in ONE
+cache, ``_cached``: keyed by the source tensors' (data_ptr, version), each entry with the event of its build, which a stream
+that did not build it waits for once.
 """
 from __future__ import annotations
 
@@ -38,6 +44,10 @@ from .. import _lib
 _SPECS = {"resnet18": ("basic", [2, 2, 2, 2]), "resnet34": ("basic", [3, 4, 6, 3]),
           "resnet50": ("bottleneck", [3, 4, 6, 3]), "resnet101": ("bottleneck", [3, 4, 23, 3]),
           "resnet152": ("bottleneck", [3, 8, 36, 3])}
+# What the three trunk paths differ in (ResNetEncoder._walk): unit launcher, activation dtype, max-pool, average pool.
+_PATHS = {"bf16": ("_conv_bn", torch.bfloat16, "i2l_maxpool3x3s2_bf16_fwd", "i2l_global_avgpool_bf16_fwd"),
+          "fp32": ("_conv_bn_f32", torch.float32, "i2l_maxpool3x3s2_f32_fwd", "i2l_global_avgpool_f32_fwd"),
+          "train": ("_conv_bn_train", torch.float32, "i2l_maxpool3x3s2_f32_fwd", "i2l_global_avgpool_f32_fwd")}
 
 
 def _conv(cin, cout, k, stride=1):
@@ -118,7 +128,9 @@ class ResNetEncoder(nn.Module):
         self.activation = nn.ReLU()
         self.model_name = model_name
         self._ws = None            # {(device, stream): workspace bytes}
-        self._packed = {}          # id(conv) -> (version key, packed bf16 filter + folded BatchNorm)
+        # weight-derived device images (_cached): id(conv) -> packed bf16 filters + folded BatchNorm of the bf16 trunk, id(bn) ->
+        # (2, C) fp32 folded scale / shift of the fp32 trunk; each (version key, image, build-done event, streams ordered behind it)
+        self._images = {}
         self.cache_packed_weights = True
         self.kernel_flags = 0      # _lib.FLAG_RESNET_NO_RING / FLAG_RESNET_IM2COL_STEM / flag_resnet_ring_depth(n)
         self.trace = None          # a list here receives (conv, bn, x, residual, y, relu, nchw_f32) of every launch
@@ -128,8 +140,7 @@ class ResNetEncoder(nn.Module):
         # 103 - 125 at B=256: one workgroup per CU walks its tiles phase by phase; profiles/r04/resnet_patch.txt, 8)
         self.fuse_joins = False
         self.trace_bwd = None      # a list here receives every unit's backward: dict(unit, dy, dz, dx, dres, names)
-        self.eval_precision = "bf16"   # "fp32": the eval-mode trunk at fp32 grade (_trunk_eval_f32); not part of the state_dict
-        self._folded = {}          # id(bn) -> (version key, (2, C) fp32 folded scale / shift, fold-done event, streams ordered behind it)
+        self.eval_precision = "bf16"   # "fp32": the eval-mode trunk at fp32 grade (_conv_bn_f32 units); not part of the state_dict
 
     @property
     def eval_precision(self) -> str:
@@ -151,44 +162,83 @@ class ResNetEncoder(nn.Module):
             ws = self._ws[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
         return ws
 
-    def _conv_bn(self, x, shape, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool, residual=None, nchw_f32=False):
-        """One fused conv+BN(+residual)(+ReLU) launch; x is NHWC bf16 (or the NCHW fp32 images)."""
-        B, H, W, Cin = shape
-        k, s, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        Ho, Wo = (H + 2 * pd - k) // s + 1, (W + 2 * pd - k) // s + 1
-        L = _lib.lib()
-        packed = self._packed_weights(conv, bn, x.device)
-        y = torch.empty((B, Ho, Wo, conv.out_channels), dtype=torch.bfloat16, device=x.device)
-        nbytes = L.i2l_conv_bf16_workspace_bytes(B, H, W, Cin, conv.out_channels, k, k, s, pd, self.kernel_flags)
-        ws = self._workspace(nbytes, x.device)
-        _lib.check(L.i2l_conv_bn_act_bf16_fwd(
-            x.data_ptr(), 1 if nchw_f32 else 0, packed.data_ptr(), _lib.ptr(residual), y.data_ptr(), B, H, W, Cin,
-            conv.out_channels, k, k, s, pd, 1 if relu else 0, ws.data_ptr(), nbytes, self.kernel_flags,
-            _lib.stream_ptr()), "conv_bn_act_bf16_fwd")
-        if self.trace is not None:
-            self.trace.append((conv, bn, x, residual, y, relu, nchw_f32))
-        return y, (B, Ho, Wo, conv.out_channels)
-
-    def _packed_weights(self, conv: nn.Conv2d, bn: nn.BatchNorm2d, device) -> torch.Tensor:
-        """bf16 filter image + BatchNorm folded into scale/bias (i2l_conv_bn_bf16_pack): weight-only work, redone
-        whenever a weight or a BatchNorm statistic changed (or on every call with cache_packed_weights = False)."""
-        tensors = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    def _cached(self, owner: nn.Module, tensors, stream: int, build, *args) -> torch.Tensor:
+        """The device image that ``build(previous image or None, *args)`` derives from ``tensors`` on the current stream
+        (= ``stream``), cached per ``owner``: weight-only work, redone whenever one of the tensors was replaced or written in
+        place (or on every call with cache_packed_weights = False).  A stream that did not build the image waits once for the
+        build's event (a pipeline's second encoder stream); a hit on the building stream costs a set lookup."""
         key = tuple((t.data_ptr(), t._version) for t in tensors)
-        hit = self._packed.get(id(conv))
-        if self.cache_packed_weights and hit is not None and hit[0] == key and hit[1].device == device:
+        hit = self._images.get(id(owner))
+        if hit is not None and hit[1].device != tensors[0].device:
+            hit = None
+        if self.cache_packed_weights and hit is not None and hit[0] == key:
+            if stream not in hit[3]:
+                torch.cuda.current_stream().wait_event(hit[2])
+                hit[3].add(stream)
             return hit[1]
+        buf = build(None if hit is None else hit[1], *args)
+        done = torch.cuda.Event()
+        done.record()
+        self._images[id(owner)] = (key, buf, done, {stream})
+        return buf
+
+    def _pack(self, prev, conv: nn.Conv2d, bn: nn.BatchNorm2d) -> torch.Tensor:
+        """bf16 filter image + BatchNorm folded into scale/bias (i2l_conv_bn_bf16_pack), into ``prev`` where it fits."""
         L = _lib.lib()
         k = conv.kernel_size[0]
         nbytes = L.i2l_conv_bf16_packed_bytes(conv.out_channels, conv.in_channels, k, k)
-        buf = hit[1] if hit is not None and hit[1].numel() >= nbytes and hit[1].device == device else \
-            torch.empty(nbytes, dtype=torch.uint8, device=device)
+        buf = prev if prev is not None and prev.numel() >= nbytes else \
+            torch.empty(nbytes, dtype=torch.uint8, device=conv.weight.device)
         _lib.check(L.i2l_conv_bn_bf16_pack(conv.weight.detach().data_ptr(), bn.weight.detach().data_ptr(),
                                            bn.bias.detach().data_ptr(), bn.running_mean.data_ptr(),
                                            bn.running_var.data_ptr(), float(bn.eps), buf.data_ptr(), nbytes,
                                            conv.out_channels, conv.in_channels, k, k, _lib.stream_ptr()),
                    "conv_bn_bf16_pack")
-        self._packed[id(conv)] = (key, buf)
         return buf
+
+    def _packed_filters(self, conv: nn.Conv2d, bn: nn.BatchNorm2d, stream: int) -> torch.Tensor:
+        return self._cached(conv, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), stream,
+                            self._pack, conv, bn)
+
+    def _fold(self, prev, bn: nn.BatchNorm2d) -> torch.Tensor:
+        """(2, C) fp32: scale = gamma / sqrt(running_var + eps) and shift = beta - running_mean * scale
+        (i2l_bn_eval_fold_f32)."""
+        C = bn.num_features
+        buf = torch.empty((2, C), dtype=torch.float32, device=bn.weight.device)
+        _lib.check(_lib.lib().i2l_bn_eval_fold_f32(bn.weight.detach().data_ptr(), bn.bias.detach().data_ptr(),
+                                                   bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps),
+                                                   buf[0].data_ptr(), buf[1].data_ptr(), C, _lib.stream_ptr()),
+                   "bn_eval_fold_f32")
+        return buf
+
+    @staticmethod
+    def _geometry(conv: nn.Conv2d, shape):
+        """(kernel, stride, padding, Ho, Wo) of a square conv on an NHWC ``shape``."""
+        k, s, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        return k, s, pd, (shape[1] + 2 * pd - k) // s + 1, (shape[2] + 2 * pd - k) // s + 1
+
+    def _traced(self, conv, bn, x, residual, y, relu, nchw) -> None:
+        if self.trace is not None:
+            self.trace.append((conv, bn, x, residual, y, relu, nchw))
+
+    # The three unit launchers share one positional signature (``tape``: the training path's unit list), so that _walk
+    # calls each the same way; each returns (y, y's NHWC shape).
+    def _conv_bn(self, x, shape, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool, residual=None, nchw=False, tape=None):
+        """One fused conv+BN(+residual)(+ReLU) launch; x is NHWC bf16 (or the NCHW fp32 images)."""
+        B, H, W, Cin = shape
+        k, s, pd, Ho, Wo = self._geometry(conv, shape)
+        L = _lib.lib()
+        stream = _lib.stream_ptr()
+        packed = self._packed_filters(conv, bn, stream)
+        y = torch.empty((B, Ho, Wo, conv.out_channels), dtype=torch.bfloat16, device=x.device)
+        nbytes = L.i2l_conv_bf16_workspace_bytes(B, H, W, Cin, conv.out_channels, k, k, s, pd, self.kernel_flags)
+        ws = self._workspace(nbytes, x.device)
+        _lib.check(L.i2l_conv_bn_act_bf16_fwd(
+            x.data_ptr(), 1 if nchw else 0, packed.data_ptr(), _lib.ptr(residual), y.data_ptr(), B, H, W, Cin,
+            conv.out_channels, k, k, s, pd, 1 if relu else 0, ws.data_ptr(), nbytes, self.kernel_flags, stream),
+            "conv_bn_act_bf16_fwd")
+        self._traced(conv, bn, x, residual, y, relu, nchw)
+        return y, (B, Ho, Wo, conv.out_channels)
 
     def _join(self, o, shape, blk, identity, nxt):
         """conv3 + bn3 + identity + ReLU of `blk` and conv1 + bn1 + ReLU of the next block in one launch
@@ -203,151 +253,44 @@ class ResNetEncoder(nn.Module):
             return None
         B, H, W, _ = shape
         L = _lib.lib()
+        stream = _lib.stream_ptr()
         y = torch.empty((B, H, W, 256), dtype=torch.bfloat16, device=o.device)
         z = torch.empty((B, H, W, c1.out_channels), dtype=torch.bfloat16, device=o.device)
         _lib.check(L.i2l_bottleneck_join_bf16_fwd(
-            o.data_ptr(), self._packed_weights(c3, blk.bn3, o.device).data_ptr(), identity.data_ptr(), y.data_ptr(),
-            self._packed_weights(c1, nxt.bn1, o.device).data_ptr(), z.data_ptr(), B * H * W, 64, 256, c1.out_channels,
-            _lib.stream_ptr()), "bottleneck_join_bf16_fwd")
-        if self.trace is not None:                    # the same two records the two launches would leave
-            self.trace.append((c3, blk.bn3, o, identity, y, True, False))
-            self.trace.append((c1, nxt.bn1, y, None, z, True, False))
+            o.data_ptr(), self._packed_filters(c3, blk.bn3, stream).data_ptr(), identity.data_ptr(), y.data_ptr(),
+            self._packed_filters(c1, nxt.bn1, stream).data_ptr(), z.data_ptr(), B * H * W, 64, 256, c1.out_channels,
+            stream), "bottleneck_join_bf16_fwd")
+        self._traced(c3, blk.bn3, o, identity, y, True, False)          # the same two records the two launches would leave
+        self._traced(c1, nxt.bn1, y, None, z, True, False)
+        if self.trace is not None:
             self.joined_heads.append(c1)              # ... whose input was not read back from HBM
         return y, (B, H, W, 256), (z, (B, H, W, c1.out_channels))
 
-    def trunk(self, x: torch.Tensor) -> torch.Tensor:
-        """(B,3,H,W) fp32 -> (B, 512|2048) fp32: the torchvision trunk incl. global average pooling."""
-        if self.training:
-            return self._trunk_train(x, None)
-        if self.eval_precision == "fp32":
-            return self._trunk_eval_f32(x)
-        x = _lib.require_gpu(x, "images")
-        B, C, H, W = x.shape
-        if C != 3:
-            raise RuntimeError(f"ResNet expects 3-channel images, got {C}")
-        L = _lib.lib()
-        m = self.resnet
-        _lib.mark("begin")
-        h, shp = self._conv_bn(x, (B, H, W, 3), m[0], m[1], relu=True, nchw_f32=True)
-        Bh, Hh, Wh, Ch = shp
-        Ho, Wo = (Hh - 1) // 2 + 1, (Wh - 1) // 2 + 1
-        p = torch.empty((B, Ho, Wo, Ch), dtype=torch.bfloat16, device=x.device)
-        _lib.check(L.i2l_maxpool3x3s2_bf16_fwd(h.data_ptr(), p.data_ptr(), B, Hh, Wh, Ch, _lib.stream_ptr()), "maxpool")
-        h, shp = p, (B, Ho, Wo, Ch)
-        blocks = [blk for li in range(4, 8) for blk in m[li]]
-        layer_end = {id(m[li][-1]): li - 3 for li in range(4, 8)}
-        head = None                                   # (o, shape): this block's conv1 output, already made by the previous block's join
-        for bi, blk in enumerate(blocks):
-            identity, ishp = h, shp
-            if isinstance(blk, _Bottleneck):
-                if head is not None:
-                    (o, s1), head = head, None
-                else:
-                    o, s1 = self._conv_bn(h, shp, blk.conv1, blk.bn1, relu=True)
-                o, s2 = self._conv_bn(o, s1, blk.conv2, blk.bn2, relu=True)
-                if blk.downsample is not None:
-                    identity, _ = self._conv_bn(h, shp, blk.downsample[0], blk.downsample[1], relu=False)
-                nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
-                joined = self._join(o, s2, blk, identity, nxt) if self.fuse_joins else None
-                if joined is not None:
-                    h, shp, head = joined
-                else:
-                    h, shp = self._conv_bn(o, s2, blk.conv3, blk.bn3, relu=True, residual=identity)
-            else:
-                o, s1 = self._conv_bn(h, shp, blk.conv1, blk.bn1, relu=True)
-                if blk.downsample is not None:
-                    identity, _ = self._conv_bn(h, shp, blk.downsample[0], blk.downsample[1], relu=False)
-                h, shp = self._conv_bn(o, s1, blk.conv2, blk.bn2, relu=True, residual=identity)
-            if id(blk) in layer_end:
-                _lib.mark(f"layer{layer_end[id(blk)]}")
-        Bf, Hf, Wf, Cf = shp
-        feat = torch.empty((B, Cf), dtype=torch.float32, device=x.device)
-        _lib.check(L.i2l_global_avgpool_bf16_fwd(h.data_ptr(), feat.data_ptr(), B, Hf, Wf, Cf, _lib.stream_ptr()), "avgpool")
-        return feat
-
-    # ------------------------------------------------------------------ eval mode at fp32 grade (running statistics)
-    def _folded_bn(self, bn: nn.BatchNorm2d, device) -> torch.Tensor:
-        """(2, C) fp32: scale = gamma / sqrt(running_var + eps) and shift = beta - running_mean * scale
-        (i2l_bn_eval_fold_f32), redone whenever a BatchNorm parameter or statistic changed -- the rule of _packed_weights."""
-        tensors = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        key = tuple((t.data_ptr(), t._version) for t in tensors)
-        stream = _lib.stream_ptr()
-        hit = self._folded.get(id(bn))
-        if self.cache_packed_weights and hit is not None and hit[0] == key and hit[1].device == device:
-            if stream not in hit[3]:                 # folded on another stream (a pipeline's second encoder stream): order once
-                torch.cuda.current_stream().wait_event(hit[2])
-                hit[3].add(stream)
-            return hit[1]
-        C = bn.num_features
-        buf = torch.empty((2, C), dtype=torch.float32, device=device)
-        _lib.check(_lib.lib().i2l_bn_eval_fold_f32(bn.weight.detach().data_ptr(), bn.bias.detach().data_ptr(),
-                                                   bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps),
-                                                   buf[0].data_ptr(), buf[1].data_ptr(), C, stream), "bn_eval_fold_f32")
-        done = torch.cuda.Event()
-        done.record()
-        self._folded[id(bn)] = (key, buf, done, {stream})
-        return buf
-
-    def _conv_bn_f32(self, x, shape, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool, residual=None, nchw=False):
+    def _conv_bn_f32(self, x, shape, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool, residual=None, nchw=False, tape=None):
         """One conv + running-statistics BatchNorm (+ residual) (+ ReLU) launch; x and y are NHWC fp32 (or x the NCHW images).
         Of ``kernel_flags`` only FLAG_EXACT_FP32 reaches the kernel: the others are tile-shape hints of the bf16 trunk."""
         B, H, W, Cin = shape
-        k, s, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        Ho, Wo = (H + 2 * pd - k) // s + 1, (W + 2 * pd - k) // s + 1
+        k, s, pd, Ho, Wo = self._geometry(conv, shape)
         L = _lib.lib()
+        stream = _lib.stream_ptr()
         co, kind = conv.out_channels, 2 if nchw else 1
-        fold = self._folded_bn(bn, x.device)
+        fold = self._cached(bn, (bn.weight, bn.bias, bn.running_mean, bn.running_var), stream, self._fold, bn)
         y = torch.empty((B, Ho, Wo, co), dtype=torch.float32, device=x.device)
         nbytes = L.i2l_conv_f32_workspace_bytes(kind, B, H, W, Cin, co, k, k, s, pd, 0)
         ws = self._workspace(nbytes, x.device)
         _lib.check(L.i2l_conv_bn_act_f32_fwd(x.data_ptr(), kind, conv.weight.detach().data_ptr(), fold[0].data_ptr(),
                                              fold[1].data_ptr(), _lib.ptr(residual), y.data_ptr(), B, H, W, Cin, co, k, k, s,
                                              pd, 1 if relu else 0, ws.data_ptr(), nbytes,
-                                             self.kernel_flags & _lib.FLAG_EXACT_FP32, _lib.stream_ptr()),
+                                             self.kernel_flags & _lib.FLAG_EXACT_FP32, stream),
                    "conv_bn_act_f32_fwd")
-        if self.trace is not None:
-            self.trace.append((conv, bn, x, residual, y, relu, nchw))
+        self._traced(conv, bn, x, residual, y, relu, nchw)
         return y, (B, Ho, Wo, co)
 
-    def _trunk_eval_f32(self, x: torch.Tensor) -> torch.Tensor:
-        """The trunk under model.eval() with eval_precision = "fp32": the block structure of _trunk_train, one launch per
-        conv unit, no tape, and nothing written to a BatchNorm buffer."""
-        x = _lib.require_gpu(x, "images")
-        B, C, H, W = x.shape
-        if C != 3:
-            raise RuntimeError(f"ResNet expects 3-channel images, got {C}")
-        L = _lib.lib()
-        m = self.resnet
-        _lib.mark("begin")
-        h, shp = self._conv_bn_f32(x, (B, H, W, 3), m[0], m[1], True, nchw=True)
-        Bh, Hh, Wh, Ch = shp
-        Ho, Wo = (Hh - 1) // 2 + 1, (Wh - 1) // 2 + 1
-        p = torch.empty((B, Ho, Wo, Ch), dtype=torch.float32, device=x.device)
-        _lib.check(L.i2l_maxpool3x3s2_f32_fwd(h.data_ptr(), p.data_ptr(), B, Hh, Wh, Ch, _lib.stream_ptr()), "maxpool")
-        h, shp = p, (B, Ho, Wo, Ch)
-        for li in range(4, 8):
-            for blk in m[li]:
-                identity = h
-                o, s1 = self._conv_bn_f32(h, shp, blk.conv1, blk.bn1, True)
-                if isinstance(blk, _Bottleneck):
-                    o, s1 = self._conv_bn_f32(o, s1, blk.conv2, blk.bn2, True)
-                if blk.downsample is not None:
-                    identity, _ = self._conv_bn_f32(h, shp, blk.downsample[0], blk.downsample[1], False)
-                last = (blk.conv3, blk.bn3) if isinstance(blk, _Bottleneck) else (blk.conv2, blk.bn2)
-                h, shp = self._conv_bn_f32(o, s1, last[0], last[1], True, residual=identity)
-            _lib.mark(f"layer{li - 3}")
-        Bf, Hf, Wf, Cf = shp
-        feat = torch.empty((B, Cf), dtype=torch.float32, device=x.device)
-        _lib.check(L.i2l_global_avgpool_f32_fwd(h.data_ptr(), feat.data_ptr(), B, Hf, Wf, Cf, _lib.stream_ptr()), "avgpool")
-        return feat
-
-    # ------------------------------------------------------------------ training mode (batch statistics, backward)
-    def _conv_bn_train(self, x, shape, conv, bn, relu, residual, nchw, tape):
+    def _conv_bn_train(self, x, shape, conv, bn, relu, residual=None, nchw=False, tape=None):
         """conv -> z, batch-statistics BatchNorm (+ residual) (+ ReLU) -> y, all NHWC fp32 (fp32-grade GEMM on the
         split-bf16 matrix-core kernel, csrc/resnet_train.hip); records the unit on the tape."""
         B, H, W, Cin = shape
-        k, s, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        Ho, Wo = (H + 2 * pd - k) // s + 1, (W + 2 * pd - k) // s + 1
+        k, s, pd, Ho, Wo = self._geometry(conv, shape)
         L = _lib.lib()
         dev, co = x.device, conv.out_channels
         kind = 2 if nchw else 1
@@ -380,15 +323,31 @@ class ResNetEncoder(nn.Module):
                                           1 if relu else 0, y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), M, co,
                                           ws.data_ptr(), nb, _lib.stream_ptr()), "bn_train_fwd_f32")
         if track:
-            for t in (bn.running_mean, bn.running_var):              # written through raw pointers: packed-weight caches
+            for t in (bn.running_mean, bn.running_var):              # written through raw pointers: the eval paths' caches
                 torch.autograd.graph.increment_version(t)
         if tape is not None:
             tape.append(dict(conv=conv, bn=bn, x=x, in_shape=shape, nchw=nchw, z=z, y=y, relu=relu, mean=mean,
                              invstd=invstd, out_shape=(B, Ho, Wo, co), residual=residual, conv_ws=conv_ws))
         return y, (B, Ho, Wo, co)
 
+    # ------------------------------------------------------------------ the trunk: one walk for the three paths
+    def trunk(self, x: torch.Tensor) -> torch.Tensor:
+        """(B,3,H,W) fp32 -> (B, 512|2048) fp32: the torchvision trunk incl. global average pooling."""
+        if self.training:
+            return self._trunk_train(x, None)
+        return self._walk(x, self.eval_precision)
+
     def _trunk_train(self, x: torch.Tensor, tape) -> torch.Tensor:
         """The trunk under model.train().  ``tape``: a dict that receives what the backward needs (None: forward only)."""
+        return self._walk(x, "train", tape)
+
+    def _walk(self, x: torch.Tensor, path: str, tape=None) -> torch.Tensor:
+        """Stem unit, 3x3/2 max-pool, the blocks of layer1..4 and the global average pool, launched through ``path``'s row
+        of _PATHS.  Eval paths report the stages to _lib.mark; the training path fills ``tape`` (units, blocks, pool)."""
+        unit_name, dtype, maxpool, avgpool = _PATHS[path]
+        unit = getattr(self, unit_name)                       # looked up per pass: profiles wrap the launchers by name
+        evaluating = path != "train"
+        joins = self.fuse_joins and path == "bf16"
         x = _lib.require_gpu(x, "images")
         B, C, H, W = x.shape
         if C != 3:
@@ -396,37 +355,47 @@ class ResNetEncoder(nn.Module):
         L = _lib.lib()
         m = self.resnet
         units = [] if tape is not None else None
-        h, shp = self._conv_bn_train(x, (B, H, W, 3), m[0], m[1], True, None, True, units)
-        Bh, Hh, Wh, Ch = shp
-        Ho, Wo = (Hh - 1) // 2 + 1, (Wh - 1) // 2 + 1
-        p = torch.empty((B, Ho, Wo, Ch), dtype=torch.float32, device=x.device)
-        _lib.check(L.i2l_maxpool3x3s2_f32_fwd(h.data_ptr(), p.data_ptr(), B, Hh, Wh, Ch, _lib.stream_ptr()), "maxpool")
-        pool_in, pool_shape = h, shp
-        h, shp = p, (B, Ho, Wo, Ch)
+        if evaluating:
+            _lib.mark("begin")
+        pool_in, pool_shape = unit(x, (B, H, W, 3), m[0], m[1], True, None, True, units)
+        _, Hh, Wh, Ch = pool_shape
+        shp = (B, (Hh - 1) // 2 + 1, (Wh - 1) // 2 + 1, Ch)
+        h = torch.empty(shp, dtype=dtype, device=x.device)
+        _lib.check(getattr(L, maxpool)(pool_in.data_ptr(), h.data_ptr(), B, Hh, Wh, Ch, _lib.stream_ptr()), "maxpool")
         blocks = []
+        head = None                                   # (o, shape): this block's conv1 output, already made by the previous block's join
         for li in range(4, 8):
-            for blk in m[li]:
-                identity, rec = h, dict(kind="bottleneck" if isinstance(blk, _Bottleneck) else "basic", down=None)
-                first = len(units) if units is not None else 0
-                if isinstance(blk, _Bottleneck):
-                    o, s1 = self._conv_bn_train(h, shp, blk.conv1, blk.bn1, True, None, False, units)
-                    o, s2 = self._conv_bn_train(o, s1, blk.conv2, blk.bn2, True, None, False, units)
-                    if blk.downsample is not None:
-                        identity, _ = self._conv_bn_train(h, shp, blk.downsample[0], blk.downsample[1], False, None, False, units)
-                        rec["down"] = len(units) - 1 if units is not None else None
-                    h, shp = self._conv_bn_train(o, s2, blk.conv3, blk.bn3, True, identity, False, units)
+            layer = m[li]
+            for bi, blk in enumerate(layer):
+                bottleneck = isinstance(blk, _Bottleneck)
+                identity, down, first = h, None, len(units) if units is not None else 0
+                if head is not None:
+                    (o, so), head = head, None
                 else:
-                    o, s1 = self._conv_bn_train(h, shp, blk.conv1, blk.bn1, True, None, False, units)
-                    if blk.downsample is not None:
-                        identity, _ = self._conv_bn_train(h, shp, blk.downsample[0], blk.downsample[1], False, None, False, units)
-                        rec["down"] = len(units) - 1 if units is not None else None
-                    h, shp = self._conv_bn_train(o, s1, blk.conv2, blk.bn2, True, identity, False, units)
+                    o, so = unit(h, shp, blk.conv1, blk.bn1, True, None, False, units)
+                if bottleneck:
+                    o, so = unit(o, so, blk.conv2, blk.bn2, True, None, False, units)
+                if blk.downsample is not None:
+                    identity, _ = unit(h, shp, blk.downsample[0], blk.downsample[1], False, None, False, units)
+                    down = len(units) - 1 if units is not None else None
+                joined = None
+                if joins and bottleneck:
+                    nxt = layer[bi + 1] if bi + 1 < len(layer) else (m[li + 1][0] if li < 7 else None)
+                    joined = self._join(o, so, blk, identity, nxt)
+                if joined is not None:
+                    h, shp, head = joined
+                elif bottleneck:
+                    h, shp = unit(o, so, blk.conv3, blk.bn3, True, identity, False, units)
+                else:
+                    h, shp = unit(o, so, blk.conv2, blk.bn2, True, identity, False, units)
                 if units is not None:
-                    rec["main"] = [i for i in range(first, len(units)) if i != rec["down"]]
-                    blocks.append(rec)
+                    blocks.append(dict(kind="bottleneck" if bottleneck else "basic", down=down,
+                                       main=[i for i in range(first, len(units)) if i != down]))
+            if evaluating:
+                _lib.mark(f"layer{li - 3}")
         Bf, Hf, Wf, Cf = shp
         feat = torch.empty((B, Cf), dtype=torch.float32, device=x.device)
-        _lib.check(L.i2l_global_avgpool_f32_fwd(h.data_ptr(), feat.data_ptr(), B, Hf, Wf, Cf, _lib.stream_ptr()), "avgpool")
+        _lib.check(getattr(L, avgpool)(h.data_ptr(), feat.data_ptr(), B, Hf, Wf, Cf, _lib.stream_ptr()), "avgpool")
         if tape is not None:
             tape.update(units=units, blocks=blocks, pool_in=pool_in, pool_shape=pool_shape, final_shape=shp)
         return feat
