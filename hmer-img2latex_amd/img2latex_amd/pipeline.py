@@ -28,7 +28,8 @@ from . import _lib
 
 
 class GreedyPipeline:
-    """submit(images) enqueues one batch; results come back in order from collect().
+    """submit(images) enqueues one batch; results come back in order from collect() -- or, with ``detokenize=`` a
+    ``training.predictor.DetokenizeTable``, as strings from collect_strings().
 
     A ResNet encoder with ``eval_precision = "fp32"`` works unchanged: the pipeline sees (B, E) fp32 features, and the
     multi-stream tile-shape flags it ORs into ``encoder.kernel_flags`` are hints of the bf16 trunk that the fp32 trunk
@@ -39,7 +40,7 @@ class GreedyPipeline:
                  decode_flags: int = 0, encoder_flags: int = 0, decode_priority: int = 0, encoder_streams: int = 1,
                  encoder_priority: int = 0, hold_encoder: Optional[bool] = None, wait_timeout_us: float = 20000.0,
                  clear_early: bool = True,
-                 stop: int = _lib.STOP_NONE, select: int = _lib.SELECT_LOGITS):
+                 stop: int = _lib.STOP_NONE, select: int = _lib.SELECT_LOGITS, detokenize=None):
         self.model = model
         self.start, self.end, self.max_length, self.temperature = start_token_id, end_token_id, max_length, temperature
         dev = next(model.parameters()).device
@@ -97,6 +98,12 @@ class GreedyPipeline:
         self._slots = self.depth + 1                 # decoder workspaces in rotation: a slot is rewritten only after its batch was collected
         self._free: List[torch.Tensor] = []          # pinned host buffers not in use
         self._lent: Optional[torch.Tensor] = None    # buffer handed to the caller by the last collect()
+        # strings (training.predictor.DetokenizeTable or None): i2l_detokenize runs behind every decode on its stream -- rows
+        # cut before `end_token_id`, the table's special ids dropped, tokens joined -- and the packed bytes + row offsets
+        # travel to pinned memory beside the ids: collect_strings().  Device buffers per slot, as the decoder workspaces.
+        self.detok = detokenize
+        self._text_dev: dict = {}
+        self._text_free: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
     def submit(self, images: torch.Tensor) -> None:
         """Enqueue encoder + decoder prepare (stream A) and decode + id copy (stream B) for one batch."""
@@ -162,8 +169,19 @@ class GreedyPipeline:
                 if rec is not None:
                     rec["dec_end"].record(dec_stream)
                 host = self._host_buffer(ids.shape)
+                text = dev_text = None
+                if self.detok is not None:
+                    key = (slot, tuple(ids.shape))
+                    if key not in self._text_dev:
+                        self._text_dev = {k: v for k, v in self._text_dev.items() if k[0] != slot}
+                        self._text_dev[key] = self.detok.buffers(*ids.shape)
+                    dev_text = self.detok.launch(ids, self.end, self._text_dev[key])
+                    text = self._text_buffer(dev_text)
                 if self.copy_stream is None:
                     host.copy_(ids, non_blocking=True)
+                    if text is not None:
+                        text[0].copy_(dev_text[0], non_blocking=True)
+                        text[1].copy_(dev_text[1], non_blocking=True)
                     done = torch.cuda.Event()
                     done.record(dec_stream)
                 else:                                              # the id copy leaves the decode stream: decode(i + 1) need not wait for it
@@ -172,10 +190,13 @@ class GreedyPipeline:
                     self.copy_stream.wait_event(decoded)
                     with torch.cuda.stream(self.copy_stream):
                         host.copy_(ids, non_blocking=True)
+                        if text is not None:
+                            text[0].copy_(dev_text[0], non_blocking=True)
+                            text[1].copy_(dev_text[1], non_blocking=True)
                         done = torch.cuda.Event()
                         done.record(self.copy_stream)
                     ids.record_stream(self.copy_stream)
-        self._inflight.append((done, host, enc))
+        self._inflight.append((done, host, enc, text))
 
     def close(self) -> None:
         """Give the decoder workspaces of this pipeline's slots back (they live in the decoder's cache under this
@@ -192,6 +213,7 @@ class GreedyPipeline:
             for s in self.enc_streams + self.dec_streams + [self.copy_stream]:
                 if s is not None:
                     s.synchronize()
+        self._text_dev = {}                          # (behind the waits above: no detokenize launch still writes them)
         dec = getattr(getattr(self, "model", None), "decoder", None)
         if dec is not None and hasattr(dec, "release_slots"):
             dec.release_slots(id(self))
@@ -208,15 +230,46 @@ class GreedyPipeline:
                 return self._free.pop(i)
         return torch.empty(shape, dtype=torch.int32).pin_memory()
 
+    def _text_buffer(self, dev_text) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Pinned landing buffers of one batch's (bytes, offsets + status); back on the list once its strings are built."""
+        shapes = (dev_text[0].shape, dev_text[1].shape)
+        for i, t in enumerate(self._text_free):
+            if (t[0].shape, t[1].shape) == shapes:
+                return self._text_free.pop(i)
+        return (torch.empty(shapes[0], dtype=torch.uint8).pin_memory(), torch.empty(shapes[1], dtype=torch.int32).pin_memory())
+
     def pending(self) -> int:
         return len(self._inflight)
 
     def collect(self) -> Optional[torch.Tensor]:
         """Oldest finished batch: (B, steps) int32 ids in pinned host memory, valid until the next
         collect(); ``to_sequences`` applies the reference's stop rule and list conversion."""
+        entry = self._collect()
+        if entry is None:
+            return None
+        if entry[1] is not None:
+            self._text_free.append(entry[1])
+        return entry[0]
+
+    def collect_strings(self) -> Optional[List[str]]:
+        """Oldest finished batch as strings, one per row: what ``tokenizer.decode`` gives for the row's ids before its first
+        END (``detokenize=`` must have been given); the same wait and the same time-out fallback as ``collect()``."""
+        if self.detok is None:
+            raise RuntimeError("GreedyPipeline: collect_strings() needs detokenize=<DetokenizeTable>")
+        entry = self._collect()
+        if entry is None:
+            return None
+        text = entry[1]
+        try:
+            return self.detok.strings(*text)
+        finally:
+            self._text_free.append(text)
+
+    def _collect(self):
+        """(ids in pinned host memory, pinned (bytes, offsets) or None) of the oldest batch: the ONE host wait per batch."""
         if not self._inflight:
             return None
-        done, host, enc = self._inflight.popleft()
+        done, host, enc, text = self._inflight.popleft()
         done.synchronize()
         if _lib.ids_timed_out(host):
             # a grouped decode needs its members resident together; on a GPU shared with other work a bounded wait can
@@ -228,10 +281,14 @@ class GreedyPipeline:
                 ids, _ = self.model.greedy_ids(enc, self.start, self.end, self.max_length, self.temperature,
                                                stop=self.stop, select=self.select, rows_per_workgroup=1)
             host.copy_(ids)
+            if text is not None:                     # the strings of the first attempt are those of the -3 rows: again
+                dev_text = self.detok.launch(ids, self.end)
+                text[0].copy_(dev_text[0])
+                text[1].copy_(dev_text[1])
         if self._lent is not None:
             self._free.append(self._lent)
         self._lent = host
-        return _lib.check_ids(host)
+        return _lib.check_ids(host), text
 
     def drain(self) -> List[torch.Tensor]:
         out = []

@@ -14,6 +14,7 @@ drivers: SURVEY 8b "feed tensors straight to the encoder").
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
@@ -50,6 +51,109 @@ class TokenTable:
     def config(self) -> Dict:
         return {"token_to_id": self.token_to_id, "special_tokens": self.special_tokens,
                 "max_sequence_length": self.max_sequence_length}
+
+
+def token_image(tokenizer):
+    """The vocabulary as i2l_detokenize reads it, built on the host: ``(tok_bytes uint8, tok_off int32 (V + 1), drop ids,
+    unk id)``.  Slot v, for v in 0 .. max id, is ``id_to_token.get(v, UNK string)`` in UTF-8 at
+    ``tok_bytes[tok_off[v]:tok_off[v + 1]]`` -- a gap in the id map reads as the UNK string, as ``decode`` reads it
+    (tokenizer.py:166-192); the drop ids are the special tokens ``decode(skip_special_tokens=True)`` removes.  Works on
+    anything with ``id_to_token``, ``token_to_id`` and ``special_tokens`` (TokenTable, the reference's LaTeXTokenizer).
+    None -- the caller keeps the host ``decode`` -- for a tokenizer without them, with more than 8 special ids (the
+    kernel's limit), or whose UNK slot does not hold the UNK string (an id beyond the map could not be spelled)."""
+    try:
+        id_to_token, token_to_id, special = tokenizer.id_to_token, tokenizer.token_to_id, tokenizer.special_tokens
+        unk = special["UNK"]
+        unk_id = int(token_to_id[unk])
+        drop = sorted({int(token_to_id[t]) for t in special.values()})
+    except (AttributeError, KeyError, TypeError):
+        return None
+    ids = [int(i) for i in id_to_token if int(i) >= 0]
+    if not ids or len(drop) > 8 or min(drop) < 0 or id_to_token.get(unk_id) != unk:
+        return None
+    slots = [id_to_token.get(v, unk).encode("utf-8") for v in range(max(ids) + 1)]
+    off = np.zeros(len(slots) + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in slots], out=off[1:])
+    if int(off[-1]) > 0x7fffffff:
+        return None
+    return np.frombuffer(b"".join(slots), dtype=np.uint8).copy(), off.astype(np.int32), drop, unk_id
+
+
+class DetokenizeTable:
+    """``token_image`` of one tokenizer on one device, and the calls that use it.  ``launch`` enqueues i2l_detokenize on the
+    current stream and returns device tensors; ``strings`` slices host copies of them into Python strings."""
+
+    def __init__(self, tokenizer, device):
+        image = token_image(tokenizer)
+        if image is None:
+            raise ValueError("img2latex_amd: this tokenizer has no device vocabulary image (see token_image)")
+        tok_bytes, tok_off, drop, self.unk_id = image
+        self.device = torch.device(device)
+        self.vocab = len(tok_off) - 1
+        self.longest = int(np.diff(tok_off).max())
+        self.n_drop = len(drop)
+        self.tok_bytes = torch.from_numpy(tok_bytes if tok_bytes.size else np.zeros(1, np.uint8)).to(self.device)
+        self.tok_off = torch.from_numpy(tok_off).to(self.device)
+        self.drop = torch.tensor(drop, dtype=torch.int32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()         # i2l_detokenize reads tok_off from the host
+
+    def capacity(self, rows: int, width: int) -> int:
+        """Bytes that hold ANY (rows, width) id matrix: every position the longest token plus a separator."""
+        return rows * width * (self.longest + 1)
+
+    def buffers(self, rows: int, width: int):
+        """(out_bytes, out_off with the status word behind it (rows + 2 int32), workspace) for ``launch``."""
+        L = _lib.lib()
+        return (torch.empty((max(self.capacity(rows, width), 1),), dtype=torch.uint8, device=self.device),
+                torch.empty((rows + 2,), dtype=torch.int32, device=self.device),
+                torch.empty((L.i2l_detokenize_workspace_bytes(rows),), dtype=torch.uint8, device=self.device))
+
+    def launch(self, ids: torch.Tensor, end_id: int, buffers=None, width: Optional[int] = None):
+        """ids (rows, >= width) int32 on the device -> (out_bytes, out_off + status) on the current stream."""
+        rows, width = ids.shape[0], int(ids.shape[1] if width is None else width)
+        out, off, ws = buffers if buffers is not None else self.buffers(rows, width)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().i2l_detokenize(
+                ids.data_ptr(), rows, width, ids.stride(0), int(end_id), self.drop.data_ptr(), self.n_drop,
+                self.tok_bytes.data_ptr(), self.tok_off.data_ptr(), self.vocab, self.unk_id, out.data_ptr(), out.numel(),
+                off.data_ptr(), off.data_ptr() + 4 * (rows + 1), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "detokenize")
+        return out, off
+
+    @staticmethod
+    def strings(host_bytes: torch.Tensor, host_off: torch.Tensor) -> List[str]:
+        """Host copies of ``launch``'s two tensors (complete: the caller has waited) -> one string per row."""
+        off = host_off.tolist()
+        if off[-1] != 0:
+            raise RuntimeError(f"img2latex_amd: detokenize needs {off[-2]} bytes, the buffer holds {host_bytes.numel()}")
+        text = host_bytes.numpy()[:off[-2]].tobytes()
+        return [text[a:b].decode("utf-8") for a, b in zip(off[:-2], off[1:-1])]
+
+    def decode_now(self, ids: torch.Tensor, end_id: int):
+        """``launch`` + the copies + the wait, for the one-batch callers: (strings, first id of every row on the host --
+        what ``_lib.ids_timed_out`` looks at)."""
+        out, off = self.launch(ids, end_id)
+        tail = torch.cat([off, ids[:, 0]]).cpu()                     # offsets, status, first column: one copy
+        n = off.numel()
+        total = int(tail[n - 2])
+        return self.strings(out[:min(total, out.numel())].cpu(), tail[:n]), tail[n:]
+
+
+_TABLES: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
+
+
+def detokenize_table(tokenizer, device) -> Optional[DetokenizeTable]:
+    """The DetokenizeTable of (tokenizer, device), built once (the cache dies with the tokenizer; a tokenizer edited
+    afterwards needs a new table: build a DetokenizeTable directly).  None when ``token_image`` gives none."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    try:
+        per_tok = _TABLES.setdefault(tokenizer, {})
+    except TypeError:                                                # not hashable / not weakly referenceable: no cache
+        per_tok = {}
+    if device not in per_tok:
+        per_tok[device] = DetokenizeTable(tokenizer, device) if token_image(tokenizer) is not None else None
+    return per_tok[device]
 
 
 def model_from_checkpoint_config(config: Dict, vocab_size: int) -> Seq2SeqModel:
@@ -180,12 +284,7 @@ class Predictor:
         with torch.no_grad():
             enc = self.model.encoder(x)
             if temperature > 0 and (top_k > 0 or top_p > 0.0):
-                if seed is None:
-                    seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                tok0 = torch.full((enc.shape[0],), int(start), dtype=torch.int32, device=enc.device)
-                ids, _ = self.model.decoder.sample_steps(enc, max_length, tok0, temperature, top_k, top_p, seed,
-                                                         stop=_lib.STOP_STICKY, end_id=end)
-                ids = _lib.check_ids(ids.cpu())
+                ids = _lib.check_ids(self._sample_ids(enc, max_length, temperature, top_k, top_p, seed).cpu())
             else:       # same timeout fallback as Seq2SeqModel._greedy_search
                 ids = self.model.greedy_ids_host(enc, start, end, max_length, temperature, stop=_lib.STOP_STICKY,
                                                  select=_lib.SELECT_SOFTMAX)
@@ -194,6 +293,44 @@ class Predictor:
         lens = np.where(stop.any(axis=1), stop.argmax(axis=1), a.shape[1]).tolist()
         return [[start] + row[:n] for row, n in zip(a.tolist(), lens)]
 
+    def _sample_ids(self, enc, max_length, temperature, top_k, top_p, seed) -> torch.Tensor:
+        """The sampling branch of the batched loop (predictor.py:295-331): (B, max_length) ids on the device."""
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        tok0 = torch.full((enc.shape[0],), int(self.tokenizer.start_token_id), dtype=torch.int32, device=enc.device)
+        ids, _ = self.model.decoder.sample_steps(enc, max_length, tok0, temperature, top_k, top_p, seed,
+                                                 stop=_lib.STOP_STICKY, end_id=self.tokenizer.end_token_id)
+        return ids
+
+    def _greedy_strings(self, table: DetokenizeTable, enc, max_length, temperature, **loop) -> List[str]:
+        """greedy_ids -> i2l_detokenize -> strings, with ``Seq2SeqModel.greedy_ids_host``'s timeout fallback: the first id
+        of every row comes back with the row offsets."""
+        import warnings
+        start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
+        ids, _ = self.model.greedy_ids(enc, start, end, max_length, temperature, **loop)
+        texts, first = table.decode_now(ids, end)
+        if _lib.ids_timed_out(first):
+            warnings.warn("img2latex_amd: grouped decode timed out (GPU oversubscribed?); "
+                          "re-running on the row-per-workgroup kernel", RuntimeWarning)
+            ids, _ = self.model.greedy_ids(enc, start, end, max_length, temperature, rows_per_workgroup=1, **loop)
+            texts, first = table.decode_now(ids, end)
+            _lib.check_ids(first)
+        return texts
+
+    def _batch_strings(self, table: DetokenizeTable, x: torch.Tensor, max_length, temperature, top_k, top_p, seed) -> List[str]:
+        """``predict_batch_ids`` + START / END stripping + ``tokenizer.decode`` (predictor.py:384-391) with the ids staying
+        on the device: the same loop launches, then i2l_detokenize (cut before END, drop the special ids, join)."""
+        x = self._as_batch(x)
+        with torch.no_grad():
+            enc = self.model.encoder(x)
+            if temperature > 0 and (top_k > 0 or top_p > 0.0):
+                ids = self._sample_ids(enc, max_length, temperature, top_k, top_p, seed)
+                texts, first = table.decode_now(ids, self.tokenizer.end_token_id)
+                _lib.check_ids(first)
+                return texts
+            return self._greedy_strings(table, enc, max_length, temperature, stop=_lib.STOP_STICKY,
+                                        select=_lib.SELECT_SOFTMAX)
+
     def predict_ids_stream(self, batches, max_length: int = 141, temperature: float = 1.0):
         """``predict_batch_ids`` (the greedy branch: argmax of softmax, sticky stop) for a STREAM of image batches, through
         ``GreedyPipeline``: the decode of batch i shares the GPU with the encoder of batch i + 1 (two batches in flight, the
@@ -201,12 +338,27 @@ class Predictor:
         returns for that batch (up to fp32 near-ties between the two decode kernels).  A ResNet encoder's bf16 trunk also
         picks other tile shapes with two trunks in flight, which can move ids; with ``model.encoder.eval_precision =
         "fp32"`` the features of the two paths are bit-identical."""
+        return self._stream(batches, max_length, temperature, None)
+
+    def predict_strings_stream(self, batches, max_length: int = 141, temperature: float = 1.0):
+        """``predict_ids_stream`` with the strings built on the device: per batch exactly
+        ``[tokenizer.decode(seq[1:]) for seq in <that batch of predict_ids_stream>]``.  The pipeline runs i2l_detokenize
+        behind each decode and copies the packed bytes + row offsets beside the ids; the host slices them.  A tokenizer
+        without a device image (``token_image`` gives None) takes the host ``decode`` on the id stream."""
+        table = detokenize_table(self.tokenizer, self.device)
+        if table is None:
+            for seqs in self._stream(batches, max_length, temperature, None):
+                yield [self.tokenizer.decode(seq[1:]) for seq in seqs]
+            return
+        yield from self._stream(batches, max_length, temperature, table)
+
+    def _stream(self, batches, max_length, temperature, table):
         from ..pipeline import GreedyPipeline
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
         n_enc = 2 if hasattr(self.model.encoder, "_trunk_train") else 1      # ResNet trunk: two in flight
         pipe = GreedyPipeline(self.model, start, end, max_length, temperature, rows_per_workgroup=0,
                               decode_flags=_lib.FLAG_DECODE_GROUP16, decode_priority=-1, encoder_streams=n_enc,
-                              stop=_lib.STOP_STICKY, select=_lib.SELECT_SOFTMAX)
+                              stop=_lib.STOP_STICKY, select=_lib.SELECT_SOFTMAX, detokenize=table)
 
         def finish(ids_host):
             a = ids_host.numpy()
@@ -214,17 +366,19 @@ class Predictor:
             lens = np.where(stop.any(axis=1), stop.argmax(axis=1), a.shape[1]).tolist()
             return [[start] + row[:n] for row, n in zip(a.tolist(), lens)]
 
+        collect = (lambda: finish(pipe.collect())) if table is None else pipe.collect_strings
         try:
             for images in batches:
                 if pipe.pending() >= pipe.depth:
-                    yield finish(pipe.collect())
+                    yield collect()
                 pipe.submit(self._as_batch(images))
             while pipe.pending():
-                yield finish(pipe.collect())
+                yield collect()
         finally:
             pipe.close()                                     # gives its decoder workspaces back
 
-    def evaluate_batch(self, images, targets: torch.Tensor, max_length: Optional[int] = None) -> Dict:
+    def evaluate_batch(self, images, targets: torch.Tensor, max_length: Optional[int] = None,
+                       return_strings: bool = False) -> Dict:
         """One batch of the reference's ``evaluate`` command (cli.py:449-495) with every stage on the device and
         the token ids never leaving HBM between them:
 
@@ -236,8 +390,11 @@ class Predictor:
             float64 formulas (calculate_metrics, metrics.py:184-223).
 
         Returns {"bleu", "levenshtein", "batch_size"} as ``calculate_metrics`` does, plus "pred_ids"/"pred_len"
-        (device tensors) for callers that also want the strings."""
-        return self._evaluate_finish(self._evaluate_launch(images, targets, max_length))
+        (device tensors) for callers that also want the strings.  ``return_strings``: also "pred_text", the
+        ``tokenizer.decode`` of every row of "pred_ids", built by i2l_detokenize in the same chain (from the decode's ids
+        under the compaction's own cut and drop rule: the compacted rows are zero-padded and the kernel takes no
+        lengths) and copied beside the statistics; a tokenizer without a device image decodes "pred_ids" on the host."""
+        return self._evaluate_finish(self._evaluate_launch(images, targets, max_length, return_strings=return_strings))
 
     def evaluate_stream(self, batches, max_length: Optional[int] = None, lookahead: int = 2):
         """``evaluate_batch`` over an iterable of (images, targets), one result per batch in order, software-pipelined:
@@ -261,7 +418,7 @@ class Predictor:
             yield self._evaluate_finish(pending.popleft())
 
     def _evaluate_launch(self, images, targets: torch.Tensor, max_length: Optional[int], side_upload: bool = False,
-                         rows_per_workgroup: int = 0, coresident: bool = False):
+                         rows_per_workgroup: int = 0, coresident: bool = False, return_strings: bool = False):
         """Enqueues the whole chain of one batch and the copy of its statistics to pinned memory; no host wait.
         ``coresident``: two streams -- everything up to the decoder's prepare on the first, the decode and what follows on the
         second (see evaluate_stream); otherwise the whole chain on the current stream."""
@@ -369,10 +526,21 @@ class Predictor:
                 ring["bufs"][slot] = torch.empty((packed.numel(),), dtype=torch.int32).pin_memory()
             host = ring["bufs"][slot][:packed.numel()].view(packed.shape)
             host.copy_(packed, non_blocking=True)
+            text = None
+            table = detokenize_table(tk, dev) if return_strings else None
+            if table is not None:
+                t_bytes, t_off = table.launch(ids, int(tk.end_token_id), width=T)
+                land = ring.setdefault("text", [None] * 4)           # the strings' landing buffers rotate with the statistics'
+                if land[slot] is None or land[slot][0].numel() < t_bytes.numel() or land[slot][1].numel() < t_off.numel():
+                    land[slot] = (torch.empty((t_bytes.numel(),), dtype=torch.uint8).pin_memory(),
+                                  torch.empty((t_off.numel(),), dtype=torch.int32).pin_memory())
+                text = (land[slot][0][:t_bytes.numel()], land[slot][1][:t_off.numel()])
+                text[0].copy_(t_bytes, non_blocking=True)
+                text[1].copy_(t_off, non_blocking=True)
             done = torch.cuda.Event()
             done.record()
         return dict(host=host, done=done, keep=(packed, x, tgt), p_ids=p_ids, p_len=p_len, raw=(raw, targets, max_length),
-                    rows_per_workgroup=rows_per_workgroup)
+                    rows_per_workgroup=rows_per_workgroup, return_strings=return_strings, text=text)
 
     def _evaluate_finish(self, h) -> Dict:
         from . import metrics as M
@@ -381,10 +549,16 @@ class Predictor:
         if _lib.ids_timed_out(host[:, 9:10]) and h["rows_per_workgroup"] == 0:
             # the timeout fallback of Seq2SeqModel.greedy_ids_host: the row-per-workgroup kernel needs no partner
             raw, targets, max_length = h["raw"]
-            return self._evaluate_finish(self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=1))
+            return self._evaluate_finish(self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=1,
+                                                               return_strings=h["return_strings"]))
         _lib.check_ids(host[:, 9:10])
         out = M.metrics_from_packed(host)
         out["pred_ids"], out["pred_len"] = h["p_ids"], h["p_len"]
+        if h["text"] is not None:
+            out["pred_text"] = DetokenizeTable.strings(*h["text"])
+        elif h["return_strings"]:
+            rows, lens = h["p_ids"].cpu().tolist(), h["p_len"].cpu().tolist()
+            out["pred_text"] = [self.tokenizer.decode(r[:n]) for r, n in zip(rows, lens)]
         return out
 
     def predict_batch(self, images, beam_size: int = 0, max_length: int = 141, temperature: float = 1.0,
@@ -395,10 +569,15 @@ class Predictor:
             images = [images] if images.dim() <= 3 else list(images)
         results: List[str] = []
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
+        table = detokenize_table(self.tokenizer, self.device)               # None: the tokenizer keeps its host decode
         for i in range(0, len(images), batch_size):
             x = torch.stack([self._prepare_image(im) for im in images[i:i + batch_size]])
             if x.dim() == 5 and x.shape[1] == 1:                            # :254-257
                 x = x.squeeze(1)
+            if table is not None:
+                results.extend(self._batch_strings(table, x, max_length, temperature, top_k, top_p,
+                                                   None if seed is None else seed + i))
+                continue
             for seq in self.predict_batch_ids(x, max_length, temperature, top_k, top_p,
                                               None if seed is None else seed + i):
                 if seq and seq[0] == start:                                 # :384-388
@@ -414,6 +593,12 @@ class Predictor:
         Seq2SeqModel.inference (greedy; beam clamped to 0)."""
         x = self._prepare_image(image).to(self.device)
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
+        table = detokenize_table(self.tokenizer, self.device)
+        if table is not None and x.dim() == 4 and x.shape[0] == 1:
+            # one image: _greedy_search's loop (logits arg max, no sticky stop; top_k / top_p ignored as there), the row
+            # cut before its first END and decoded on the device
+            with torch.no_grad():
+                return self._greedy_strings(table, self.model.encoder(x), max_length, temperature)[0]
         with torch.no_grad():
             seq = self.model.inference(image=x, start_token_id=start, end_token_id=end, max_length=max_length,
                                        beam_size=0, temperature=temperature, top_k=top_k, top_p=top_p)

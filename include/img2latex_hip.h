@@ -499,6 +499,28 @@ int i2l_scores_from_statistics(const int32_t* stats, int pairs, int stride, int 
 int i2l_compact_ids(const int32_t* ids, int rows, int width, int stride, int end_id, const int32_t* drop_ids,
                     int n_drop, int32_t* out_ids, int out_stride, int32_t* out_len, i2l_stream_t stream);
 
+/* Token ids -> text on the device: LaTeXTokenizer.decode(skip_special_tokens=True) (tokenizer.py:166-192) on top of the
+ * predictor's END handling (predictor.py:350-358,384-391), i.e. what Predictor.predict_batch returns per row.
+ * Row rule = i2l_compact_ids': keep, in order, the ids before the first stop position (id == end_id, or id < 0; with
+ * end_id = -1 only a negative id stops a row) that are not one of drop_ids[0..n_drop) (DEVICE array, <= 8); a kept id
+ * outside [0, vocab) reads as unk_id.  Text rule = " ".join: token v is tok_bytes[tok_off[v] .. tok_off[v + 1]) (DEVICE
+ * arrays, tok_off of vocab + 1 ascending int32; the bytes are opaque -- UTF-8 in practice), one 0x20 between consecutive
+ * kept tokens, none in front of the first or behind the last; a zero-length token still takes its separators; a row with
+ * nothing kept is the empty string.  Row r is out_bytes[out_off[r] .. out_off[r + 1]), packed without gaps; out_off has
+ * rows + 1 int32 (the exclusive scan of the row sizes, [rows] = the total).
+ * *status (device word) = 0, or 1 when the total exceeds out_capacity: out_off is complete all the same (the caller
+ * learns the size needed) and no byte at or beyond out_capacity is written.
+ * I2L_ERR_UNSUPPORTED before any launch: n_drop > 8; vocab <= 0; rows * width * (longest token + 1) beyond int32 (the
+ * byte counts are int32).  For that bound, and to refuse offsets that do not ascend (I2L_ERR_ARG), the call READS
+ * tok_off from the host with one blocking copy of vocab + 1 words: the table must be complete when it is called.
+ * Three launches on `stream` (size per row, scan over the rows -- any number of them --, write); the writing pass maps
+ * lanes to OUTPUT bytes, so neighbouring lanes store neighbouring bytes.  workspace: rows int32. */
+size_t i2l_detokenize_workspace_bytes(int rows);
+int i2l_detokenize(const int32_t* ids, int rows, int width, int stride, int end_id, const int32_t* drop_ids, int n_drop,
+                   const uint8_t* tok_bytes, const int32_t* tok_off, int vocab, int unk_id, uint8_t* out_bytes,
+                   int64_t out_capacity, int32_t* out_off, int32_t* status, void* workspace, size_t workspace_bytes,
+                   i2l_stream_t stream);
+
 /* masked_accuracy, metrics.py:226-238 (trainer.py:391,526): over rows = B*T logits rows of `vocab` floats,
  * correct_total_out[0] = #(argmax == target and target != pad), [1] = #(target != pad); first index wins
  * ties.  The (B,T,V) logits never leave the device (the reference copies them to the host every step). */
