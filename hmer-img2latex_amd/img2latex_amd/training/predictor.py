@@ -377,13 +377,16 @@ class Predictor:
         finally:
             pipe.close()                                     # gives its decoder workspaces back
 
-    def evaluate_batch(self, images, targets: torch.Tensor, max_length: Optional[int] = None,
+    def evaluate_batch(self, images, targets: Union[torch.Tensor, Sequence[str]], max_length: Optional[int] = None,
                        return_strings: bool = False) -> Dict:
         """One batch of the reference's ``evaluate`` command (cli.py:449-495) with every stage on the device and
         the token ids never leaving HBM between them:
 
             images    a (B,C,H,W) tensor already shaped for the model, or a list of decoded uint8 arrays
                       ((h,w) / (h,w,3)) that first go through ``preprocess_batch`` (= load_image, data/utils.py:18-90)
+            targets   a (B, L) id tensor padded with PAD, or a list of B ``str``: the raw formulas as the data set holds
+                      them, tokenized on the device by ``TokenizeTable.collate`` (START formula END, never cut, padded
+                      to the longest row: dataset.py:333-335, collator :59-66) and entering the chain as that tensor would
             encoder -> sticky greedy loop (predictor.py:283-358) -> i2l_compact_ids (cut before END, drop the special
             tokens: what tokenizer.decode + tokenizer.encode do to a prediction at cli.py:466-481; targets: drop PAD)
             -> i2l_sequence_metrics -> ONE small device->host copy of the integer statistics -> the reference's
@@ -406,7 +409,16 @@ class Predictor:
         ``lookahead`` batches are enqueued beyond the one whose statistics the host waits for (r04: 2 -- with 1 the host only
         began batch i + 2 once batch i had finished, its 0.7 ms of packing then landed inside decode(i + 1), and the
         encoder of batch i + 2 started where that decode ended instead of beside it: profiles/r04/evaluate_chain.txt).
-        This is the loop of cli.py:449-495."""
+        This is the loop of cli.py:449-495.
+
+        A batch's targets may be a list of ``str`` (raw formulas) instead of a tensor; batches of both kinds may be mixed.
+        The text is packed and uploaded where a tensor's upload goes, and tokenized behind it on the caller's stream, at a
+        width known without asking the device: ``tokenizer.max_sequence_length + 2``, with the compaction dropping the
+        PAD.  ``collate``'s exact width would need a host wait for the counts in the middle of the look-ahead, and the
+        other host-known width, the byte-length bound, is about twice as wide and takes the statistics kernel off its
+        <= 256 path; the statistics do not depend on the padded width.  ``collate`` never cuts a row, so i2l_tokenize's
+        status word travels with the statistics, and a batch in which a row WAS cut (a formula of more than
+        max_sequence_length tokens) is run again with ``collate``'s width when its statistics are collected."""
         from collections import deque
         pending = deque()
         lookahead = max(1, min(int(lookahead), 2))           # the landing buffers / decoder slots rotate over 4 / 3
@@ -417,7 +429,7 @@ class Predictor:
         while pending:
             yield self._evaluate_finish(pending.popleft())
 
-    def _evaluate_launch(self, images, targets: torch.Tensor, max_length: Optional[int], side_upload: bool = False,
+    def _evaluate_launch(self, images, targets, max_length: Optional[int], side_upload: bool = False,
                          rows_per_workgroup: int = 0, coresident: bool = False, return_strings: bool = False):
         """Enqueues the whole chain of one batch and the copy of its statistics to pinned memory; no host wait.
         ``coresident``: two streams -- everything up to the decoder's prepare on the first, the decode and what follows on the
@@ -429,7 +441,20 @@ class Predictor:
         raw = images
         # host-side preparation and everything that touches the CALLER's stream first (targets, the small constant tensors)
         T = int(max_length if max_length is not None else tk.max_sequence_length)
-        tgt = targets.to(self.device, dtype=torch.int32).contiguous()
+        tok_status = None
+        if isinstance(targets, (list, tuple)) and targets and all(isinstance(t, str) for t in targets):
+            from .tokenizer import tokenize_table
+            ttable = tokenize_table(tk, self.device)
+            if ttable is None:
+                raise ValueError("img2latex_amd: string targets need a tokenizer with a device vocabulary table "
+                                 "(tokenize_image); encode them with the tokenizer's own encode and pass the id tensor")
+            if side_upload:                                  # evaluate_stream: no host wait (see its docstring)
+                text, row_off = ttable.upload(targets)
+                tgt, _, _, tok_status = ttable.launch(text, row_off, int(tk.max_sequence_length) + 2, True)
+            else:
+                tgt = ttable.collate(targets)
+        else:
+            tgt = targets.to(self.device, dtype=torch.int32).contiguous()
         if tgt.dim() != 2:
             raise RuntimeError(f"targets must be (B, L) token ids, got {tuple(tgt.shape)}")
         special = getattr(tk, "special_tokens", DEFAULT_SPECIAL_TOKENS)
@@ -506,7 +531,7 @@ class Predictor:
         with on_stat(), torch.cuda.device(dev):
             if coresident:
                 s_stat.wait_event(decoded)
-                for t_ in (ids, t_ids, t_len):
+                for t_ in (ids, t_ids, t_len) + (() if tok_status is None else (tok_status,)):
                     t_.record_stream(s_stat)
             p_ids = torch.zeros((B, W), dtype=torch.int32, device=dev)
             p_len = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -516,7 +541,7 @@ class Predictor:
                                              _lib.stream_ptr()), "compact_ids")
                 packed = M.device_sequence_statistics(p_ids, p_len, t_ids, t_len, 4, tk.pad_token_id, _max_len=W, defer=True)
             # statistics + the first id of every row (-3 = the grouped decode timed out) in ONE device->host copy
-            packed = torch.cat([packed, ids[:, :1]], dim=1)
+            packed = torch.cat([packed, ids[:, :1]] + ([] if tok_status is None else [tok_status.expand(B)[:, None]]), dim=1)
             # pinned landing buffers are reused (registering pinned memory costs ~1 ms): a ring of 4, more than the
             # two batches evaluate_stream ever has in flight
             ring = self.__dict__.setdefault("_host_ring", {"bufs": [None] * 4, "next": 0})
@@ -552,6 +577,11 @@ class Predictor:
             return self._evaluate_finish(self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=1,
                                                                return_strings=h["return_strings"]))
         _lib.check_ids(host[:, 9:10])
+        if host.shape[1] > 10 and int(host[0, 10]) != 0:
+            # string targets at the stream's fixed width and a row was cut: once more with collate's width
+            raw, targets, max_length = h["raw"]
+            return self._evaluate_finish(self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=h["rows_per_workgroup"],
+                                                               return_strings=h["return_strings"]))
         out = M.metrics_from_packed(host)
         out["pred_ids"], out["pred_len"] = h["p_ids"], h["p_len"]
         if h["text"] is not None:

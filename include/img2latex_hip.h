@@ -521,6 +521,45 @@ int i2l_detokenize(const int32_t* ids, int rows, int width, int stride, int end_
                    int64_t out_capacity, int32_t* out_off, int32_t* status, void* workspace, size_t workspace_bytes,
                    i2l_stream_t stream);
 
+/* Text -> token ids on the device: LaTeXTokenizer.encode / encode_batch (tokenizer.py:143-164,196-232) and the data
+ * set's "START formula END" rule (dataset.py:333-335, collator :59-66).  Row r is text[row_off[r] .. row_off[r + 1])
+ * (DEVICE arrays: uint8 text of text_bytes, int32 row_off of rows + 1; read on the device only -- no host
+ * synchronisation, the offsets change with every batch).
+ * Token rule = str.split() without an argument: tokens are the maximal runs of bytes outside every whitespace character;
+ * leading / trailing whitespace, an empty row and an all-whitespace row give no token.  Whitespace is exactly the 29 code
+ * points of str.isspace() -- U+0009-000D, 001C-0020, 0085, 00A0, 1680, 2000-200A, 2028, 2029, 202F, 205F, 3000 -- matched
+ * by their UTF-8 byte patterns (09-0D, 1C-20; C2 85, C2 A0; E1 9A 80; E2 80 80..8A, E2 80 A8, E2 80 A9, E2 80 AF; E2 81
+ * 9F; E3 80 80) at any byte position: exact for well-formed UTF-8, which the caller promises.  Every other byte is opaque
+ * token content.
+ * Id rule (tokenizer.py:162) = the id of the table key whose bytes EQUAL the token's bytes, else unk_id; a hash match
+ * never decides alone, and a token of any length works (one longer than the longest key is UNK without a probe).
+ * Row rule (tokenizer.py:155-156,219-227): with add_special = 1, start_id first and end_id behind the last token (the
+ * literal text "<START>" inside a row is an ordinary token for the table); the row is then cut to `width` (an over-long
+ * row loses its END) and padded with pad_id.  out_ids (rows, out_stride >= width) int32: all `width` columns of every
+ * row are written, nothing behind them; out_len (rows) = ids before the padding (<= width); out_count (rows, or NULL) =
+ * the count before the cut, START and END included.
+ * *status (device word, cleared by the call) = 0, or bit 0: some row was cut; bit 1: some row's offsets were unusable
+ * (end < start, or outside [0, text_bytes]) -- such a row is an empty row and no byte outside `text` is ever read; bit 2:
+ * the table image does not describe itself (wrong magic or sizes) -- every token is then unk_id.
+ * The table is the self-contained image i2l_tokenize_table_build writes on the HOST (HOST pointers: n keys, key i =
+ * tok_bytes[tok_off[i] .. tok_off[i + 1]) with id tok_id[i]; image of i2l_tokenize_table_bytes(n, tok_off[n] -
+ * tok_off[0]) bytes, 0 when that is beyond int32), uploaded once per tokenizer: open addressing with linear probing over
+ * a power of two of 16-byte slots (FNV-1a hash, key start, key length, id), load factor <= 1/2, the key bytes behind
+ * them.  A zero-length key is accepted and can never be hit (a token has a byte); the same key twice is I2L_ERR_ARG, a
+ * too-small image I2L_ERR_WORKSPACE.
+ * I2L_ERR_UNSUPPORTED before any launch: width <= 0; out_stride < width; text_bytes beyond int32.  rows == 0 is I2L_OK
+ * with no launch.  Otherwise one memset of *status and ONE kernel on `stream`: a wave per row, lane = byte (neighbouring
+ * lanes read neighbouring bytes), 64 bytes at a time with the whitespace state, the last two pattern lengths and the
+ * token count carried from chunk to chunk (rows of any length); the lane of a token's first byte hashes, probes and
+ * compares.  No workspace. */
+size_t i2l_tokenize_table_bytes(int n, int64_t key_bytes);
+int i2l_tokenize_table_build(const uint8_t* tok_bytes, const int32_t* tok_off, const int32_t* tok_id, int n, void* image,
+                             size_t image_bytes);
+int i2l_tokenize(const uint8_t* text, int64_t text_bytes, const int32_t* row_off, int rows, const void* table,
+                 size_t table_bytes, int unk_id, int pad_id, int start_id, int end_id, int add_special, int width,
+                 int32_t* out_ids, int out_stride, int32_t* out_len, int32_t* out_count, int32_t* status,
+                 i2l_stream_t stream);
+
 /* masked_accuracy, metrics.py:226-238 (trainer.py:391,526): over rows = B*T logits rows of `vocab` floats,
  * correct_total_out[0] = #(argmax == target and target != pad), [1] = #(target != pad); first index wins
  * ties.  The (B,T,V) logits never leave the device (the reference copies them to the host every step). */
