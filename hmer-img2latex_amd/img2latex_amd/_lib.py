@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libimg2latex_hip.so")
 
 OK = 0
+ERR_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_LAUNCH = -1, -2, -3, -4      # include/img2latex_hip.h I2L_ERR_*
 STOP_NONE, STOP_STICKY = 0, 1
 SELECT_LOGITS, SELECT_SOFTMAX, SELECT_SAMPLE = 0, 1, 2
 PREP_WEIGHTS, PREP_ROWS, PREP_ALL = 1, 2, 3
@@ -163,6 +164,8 @@ _SIGNATURES.update({
     "i2l_teacher_forced_eval_workspace_bytes": (c_size_t, [c_int, c_int]),
     "i2l_teacher_forced_eval": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "i2l_affine_nearest_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, c_void_p]),
+    "i2l_affine_nearest_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
 })
 FILTER_LANCZOS, FILTER_BICUBIC = 1, 3          # include/img2latex_hip.h I2L_FILTER_* (= PIL.Image.Resampling values)
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

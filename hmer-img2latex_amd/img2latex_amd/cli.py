@@ -5,6 +5,7 @@
                                                      [--top-k K] [--top-p P] [--device cuda]
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
                                   [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
+                                  [--augment]
 
 ``predict`` is the reference's chain end to end on the device: Predictor.from_checkpoint (predictor.py:61-137) ->
 Predictor.predict(image_path) (:139-203) -> load_image (data/utils.py:18-90) -> encoder -> greedy search -> string.
@@ -20,7 +21,11 @@ the deterministic generator the benchmarks use.  After every epoch it validates 
 ``training.early_stopping_patience`` epochs without improvement, and ``metrics/metrics.json`` when
 ``evaluation.save_basic_metrics`` is set.  A synthetic run validates only with ``--synthetic-val-steps N`` (N synthetic
 batches from a seed disjoint from the training batches; it then runs ``training.epochs`` epochs over the same training
-batches); without it, it makes one pass and writes one plain checkpoint, as before.  Experiment registry, logging setup
+batches); without it, it makes one pass and writes one plain checkpoint, as before.  ``--augment`` warps every training
+batch on the device as the reference's training split is warped (data/dataset.py:486-492: rotation within 5 degrees,
+then a shift within 2 %, NEAREST, white fill; ``data.Augment.tensor``), never a validation batch.  One difference: the
+batches arrive preprocessed, so the 2 % is a fraction of the preprocessed tensor's size, not of the raw page's as in the
+reference; ``data.preprocess_batch(pages, augment=...)`` is the reference-order path for raw pages.  Experiment registry, logging setup
 and rich console output are the reference's host-side orchestration and are not rebuilt here.
 
 The device is a ROCm GPU; ``--device cpu`` is refused (there is no CPU fallback in this package).
@@ -86,11 +91,12 @@ def _synthetic_batches(config: Dict, steps: int, vocab_size: int, seed: int):
 def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: str = "img2latex_v1",
           checkpoint_path: Optional[str] = None, data_dir: Optional[str] = None, device: Optional[str] = None,
           seed: int = 42, synthetic_steps: int = 0, synthetic_vocab: int = 512, output_dir: str = "outputs",
-          synthetic_val_steps: int = 0) -> Dict:
+          synthetic_val_steps: int = 0, augment: bool = False) -> Dict:
     """cli.py:104-250 reduced to the hot path: model from the config, optional resume, TrainStep over the batches, a
     checkpoint in the reference's layout (trainer.py:209-224) per epoch, and -- with validation batches -- the epoch-end
     validation / LR schedule / best checkpoint / early stop of trainer.py:713-766.  Returns {"loss", "steps",
-    "global_step", "checkpoint"}, plus {"best_val_loss", "val_metrics"} when validation ran."""
+    "global_step", "checkpoint"}, plus {"best_val_loss", "val_metrics"} when validation ran.  ``augment``: warp each
+    training batch with ``data.Augment(seed=seed).tensor`` (keyed by epoch and the sample's position in the epoch)."""
     import random
     from . import data as D
     from .training import EarlyStopping, PlateauSchedule, TokenTable, TrainStep, save_checkpoint, validate
@@ -157,13 +163,18 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
     stopper = EarlyStopping.from_checkpoint(int(tcfg.get("early_stopping_patience", 10)), resume)   # :120-122,257-262
     val_metrics = None
     accum = max(1, int(tcfg.get("accumulation_steps", 1)))                  # trainer.py:86-88 (the shipped config: 4)
+    warp = D.Augment(seed=seed) if augment else None                        # dataset.py:486-492, the defaults are its values
     for epoch in range(start_epoch + 1, max_epochs + 1):                    # `epoch` = trainer.py's current_epoch + 1
         batches = _synthetic_batches(config, synthetic_steps, tokenizer.vocab_size, seed) if loaders is None else loaders["train"]
         it = iter(batches)
-        batch, batch_idx = next(it, None), 0
+        batch, batch_idx, seen = next(it, None), 0, 0
         while batch is not None:
             nxt = next(it, None)                                            # one batch of look-ahead: "is this the last one?" (:374)
             images = batch["images"].to(dev)                                # data/utils.py:113-135 prepare_batch
+            if warp is not None:                                            # white after load_image's normalisation
+                ids = range(seen, seen + images.shape[0])
+                images = warp.tensor(images.float(), D.white_fill(images.shape[1], True), ids, epoch - 1)
+            seen += images.shape[0]
             if is_resnet and images.shape[1] == 1:
                 images = D.batch_convert_for_resnet(images)
             update = (batch_idx + 1) % accum == 0 or nxt is None
@@ -245,6 +256,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     t.add_argument("--synthetic-val-steps", type=int, default=0,
                    help="(this package) with --synthetic-steps: validate every epoch on N synthetic batches and run "
                         "training.epochs epochs with LR scheduling and early stopping")
+    t.add_argument("--augment", action="store_true",
+                   help="(this package) warp each training batch on the device as the reference's training split is "
+                        "(rotation within 5 degrees, shift within 2 %% of the batch's size, NEAREST, white fill)")
     args = ap.parse_args(argv)
     if args.command == "predict":
         latex = predict(args.checkpoint_path, args.image_path, args.beam_size, args.max_length, args.temperature,
@@ -254,7 +268,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,
-              args.synthetic_steps, args.synthetic_vocab, args.output_dir, args.synthetic_val_steps)
+              args.synthetic_steps, args.synthetic_vocab, args.output_dir, args.synthetic_val_steps, args.augment)
     except SystemExit:
         raise
     except Exception as exc:                                                # cli.py:247-250: failure -> exit code 1

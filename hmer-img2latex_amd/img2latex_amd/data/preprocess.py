@@ -126,7 +126,8 @@ def _extents(flt: int, ins: np.ndarray, outs: np.ndarray):
 
 def preprocess_batch(images: Sequence[np.ndarray], img_size: Tuple[int, int] = (64, 800), channels: int = 1,
                      normalize=True, device=None, keep_aspect: bool = True, resample: str = "lanczos",
-                     upload_stream=None, tables: str = "device") -> torch.Tensor:
+                     upload_stream=None, tables: str = "device", augment=None, sample_ids=None,
+                     epoch: int = 0) -> torch.Tensor:
     """`load_image` for already decoded images: uint8 arrays (H, W) ["L"] or (H, W, 3) ["RGB"], any sizes.
     Returns (n, channels, img_size[0], img_size[1]) float32 on the device.
 
@@ -139,7 +140,12 @@ def preprocess_batch(images: Sequence[np.ndarray], img_size: Tuple[int, int] = (
     tables are built on the device (``tables="device"``, i2l_resample_coeffs_device).  ``tables="host"``: the library's
     host helper (libm: Pillow's own arithmetic) with look-ups in a device-resident pool, new sizes computed on the host's
     cores.  ``upload_stream``: run the upload on a side stream (the kernels, on the current stream, wait for it) so that
-    it overlaps whatever the current stream is still doing."""
+    it overlaps whatever the current stream is still doing.
+
+    ``augment``: an ``Augment`` (data/augment.py) warps every page first, as the reference's training split does
+    (dataset.py:486-492: rotation, then shift, NEAREST, white fill), keyed by ``sample_ids`` (default 0 .. n-1) and
+    ``epoch``.  Its parameter block rides in the same upload and ONE more launch (i2l_affine_nearest_u8) writes the
+    warped pages to a second pixel buffer, on which the unchanged plans and tables then run.  ``None``: nothing changes."""
     if tables not in ("device", "host"):
         raise ValueError("tables must be 'device' or 'host'")
     flt = {"lanczos": _lib.FILTER_LANCZOS, "bicubic": _lib.FILTER_BICUBIC}[resample]
@@ -218,6 +224,10 @@ def preprocess_batch(images: Sequence[np.ndarray], img_size: Tuple[int, int] = (
         req_bytes = 0 if tab_req is None else 2 * n * (4 + 4 + 8)
         p0 = (total_px + 255) // 256 * 256
         p1 = (p0 + plan_bytes + 255) // 256 * 256
+        if augment is not None:                                   # the warp parameters: behind everything else
+            warp = augment.params(list(zip(h.tolist(), w.tolist())), np.arange(n) if sample_ids is None else sample_ids, epoch)
+            p2 = (p1 + req_bytes + 255) // 256 * 256
+            req_bytes = p2 - p1 + warp.nbytes
         st, slot, pinned = _staging(dev, p1 + req_bytes + 256)
         host = pinned.numpy()
         # the pages -> one pinned block, on several host threads (one thread copies 16 MB in ~3 ms)
@@ -230,6 +240,8 @@ def preprocess_batch(images: Sequence[np.ndarray], img_size: Tuple[int, int] = (
             host[p1:p1 + 8 * n] = t_in.view(np.uint8)
             host[p1 + 8 * n:p1 + 16 * n] = t_out.view(np.uint8)
             host[p1 + 16 * n:p1 + 32 * n] = t_off.view(np.uint8)
+        if augment is not None:
+            host[p2:p2 + warp.nbytes] = warp.view(np.uint8)
         cur = torch.cuda.current_stream(dev)
         with torch.cuda.stream(upload_stream if upload_stream is not None else cur):
             # allocated under the uploading stream: memory the caching allocator hands out there has no pending work
@@ -252,7 +264,11 @@ def preprocess_batch(images: Sequence[np.ndarray], img_size: Tuple[int, int] = (
             _lib.check(_lib.lib().i2l_resample_coeffs_device(flt, 2 * n, d_all.data_ptr() + p1, d_all.data_ptr() + p1 + 8 * n,
                                                              d_all.data_ptr() + p1 + 16 * n, tab.data_ptr(), t_max_out,
                                                              _lib.stream_ptr()), "resample_coeffs_device")
-        _lib.check(_lib.lib().i2l_preprocess_images(d_all.data_ptr(), d_all.data_ptr() + p0, tab.data_ptr(), n,
+        pages = d_all
+        if augment is not None:
+            pages = augment.pages(d_all[:p0], d_all.data_ptr() + p0, d_all.data_ptr() + p2, n, int(max(h.max(), w.max())),
+                                  int(sizes.max()))
+        _lib.check(_lib.lib().i2l_preprocess_images(pages.data_ptr(), d_all.data_ptr() + p0, tab.data_ptr(), n,
                                                     max_tmp_px, channels, out_h, out_w, normalize,
                                                     ws.data_ptr(), out.data_ptr(), _lib.stream_ptr()), "preprocess_images")
     return out

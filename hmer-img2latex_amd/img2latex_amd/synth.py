@@ -39,14 +39,20 @@ def _mix64(z: np.ndarray) -> np.ndarray:
     return z
 
 
-def raw_bits(seed: int, name: str, n: int, lane: int = 0) -> np.ndarray:
-    """n uint64 words for (seed, name, lane); counter = element index."""
+def keyed_bits(seed: int, name: str, counters, lane: int = 0) -> np.ndarray:
+    """One uint64 word per entry of `counters` for (seed, name, lane): the word depends on the counter's value only,
+    not on its position or on the other entries (what a per-sample draw needs)."""
     base = (seed * 0x9E3779B97F4A7C15 + _fnv1a64(name) * 0xD1B54A32D192ED03
             + lane * 0x8CB92BA72F3D8DD7) & 0xFFFFFFFFFFFFFFFF
-    idx = np.arange(n, dtype=np.uint64)
+    idx = np.asarray(counters).astype(np.uint64)
     with np.errstate(over="ignore"):
         z = idx * np.uint64(0x9E3779B97F4A7C15) + np.uint64(base)
     return _mix64(_mix64(z))
+
+
+def raw_bits(seed: int, name: str, n: int, lane: int = 0) -> np.ndarray:
+    """n uint64 words for (seed, name, lane); counter = element index."""
+    return keyed_bits(seed, name, np.arange(n, dtype=np.uint64), lane)
 
 
 def u24(seed: int, name: str, n: int, lane: int = 0) -> np.ndarray:

@@ -665,6 +665,49 @@ int i2l_preprocess_images(const uint8_t* pixels, const i2l_resize_plan* plans, c
 int i2l_resize_bilinear_f32(const float* in, float* out, int64_t planes, int in_h, int in_w, int out_h, int out_w,
                             i2l_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Train-time augmentation (reference img2latex/data/dataset.py:486-492: RandomRotation(degrees=5, fill=(255,)) then
+ * RandomAffine(degrees=0, translate=(0.02, 0.02), fill=(255,)) on the decoded page, before load_image's chain)
+ * ---------------------------------------------------------------------- */
+
+/* One image's warp.  On PIL images both transforms resample NEAREST and end in two Pillow calls,
+ *     rot = page.rotate(angle, NEAREST, expand=False, center=None, fillcolor=white)
+ *     out = rot.transform(rot.size, AFFINE, (1, 0, -tx, 0, 1, -ty), NEAREST, fillcolor=white)
+ * with white = 255 on every band, angle uniform in [-degrees, degrees], tx = int(round(u)) for u uniform in
+ * [-translate[0]*W, translate[0]*W] and ty likewise from translate[1]*H.  Pillow's nearest affine is 16.16 fixed point
+ * (libImaging/Geometry.c): with FIX(v) = floor(v*65536 + 0.5) and Image.rotate's matrix m (PIL/Image.py; doubles:
+ * a = -radians(angle % 360), m = [round(cos a, 15), round(sin a, 15), 0, round(-sin a, 15), round(cos a, 15), 0],
+ * (m2, m5) = m applied to (-W/2, -H/2), m2 += W/2, m5 += H/2),
+ *     a0, a1, a3, a4 = FIX(m0), FIX(m1), FIX(m3), FIX(m4);  a2 = FIX(m2 + m0*0.5 + m1*0.5);  a5 = FIX(m5 + m3*0.5 + m4*0.5)
+ * and output pixel (x, y) is source pixel (yin, xin), xin = (a2 + a0*x + a1*y) >> 16, yin = (a5 + a3*x + a4*y) >> 16
+ * (arithmetic shift), when 0 <= xin < W and 0 <= yin < H, else the fill.  The shift pass reduces to (x - tx, y - ty)
+ * exactly, so both passes are ONE gather per output pixel: x' = x - tx, y' = y - ty; the fill if (x', y') is off the
+ * page; otherwise the rotation look-up at (x', y'), which may itself give the fill.  angle 0 is the identity
+ * (a = {65536, 0, 32768, 0, 65536, 32768}); Pillow's transpose shortcuts for 90 / 180 / 270 are not reproduced.  The
+ * coefficients come from the host (Python doubles, data/augment.py); the device sums the indices in 64 bits. */
+typedef struct i2l_affine_params {
+    int32_t a0, a1, a2, a3, a4, a5;    /* 16.16 fixed point, as above */
+    int32_t tx, ty;                    /* shift in whole pixels       */
+} i2l_affine_params;
+
+/* The warp of a ragged batch of interleaved uint8 pages in ONE launch: page i is the (src_h, src_w, src_c) image at
+ * pixels + plans[i].src_offset (src_c 1 or 3; the layout i2l_preprocess_images reads, and only those four fields of the
+ * plan are read), warped by params[i] with fill 255 into out + plans[i].src_offset.  Bytes of `out` outside the pages are
+ * not written, so the same plans and tables then run unchanged on `out`.  plans and params are DEVICE arrays; out must
+ * not alias pixels.  max_side = the largest src_h / src_w of the batch, max_page_bytes = the largest src_h*src_w*src_c
+ * (it sizes the grid).  I2L_ERR_UNSUPPORTED before any launch for max_side > 16384; a page of the batch beyond that
+ * (a wrong max_side) is left unwritten. */
+int i2l_affine_nearest_u8(const uint8_t* pixels, uint8_t* out, const i2l_resize_plan* plans,
+                          const i2l_affine_params* params, int n, int max_side, int64_t max_page_bytes,
+                          i2l_stream_t stream);
+
+/* The same gather on a dense (n, c, h, w) fp32 batch (what the reference's data loaders yield: pages already through
+ * load_image): image i warped by params[i] (DEVICE array), every channel alike, fill[ch] (HOST array of c values, read
+ * during the call) where the look-up leaves the page.  A gather: the values are copied, no arithmetic touches them.
+ * I2L_ERR_UNSUPPORTED before any launch for c > 4 or a side above 16384. */
+int i2l_affine_nearest_f32(const float* x, float* out, const i2l_affine_params* params, const float* fill, int n,
+                           int c, int h, int w, i2l_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
