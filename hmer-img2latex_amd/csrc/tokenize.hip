@@ -2,7 +2,7 @@
 // img2latex/data/tokenizer.py:143-164,196-232) and the data set's "START formula END" rule (data/dataset.py:333-335,
 // collator :59-66).  Token rule = Python's str.split() without an argument: tokens are the maximal runs of bytes that
 // belong to no whitespace character, whitespace being the 29 code points of str.isspace(), matched by their UTF-8 byte
-// patterns (ws_len below; exact at any byte position of well-formed UTF-8, which is self-synchronising).  Id rule = the
+// patterns (ws_len; exact at any byte position of well-formed UTF-8, which is self-synchronising).  Id rule = the
 // table entry whose bytes EQUAL the token's bytes, else unk_id (tokenizer.py:162).
 //
 // One launch, one wave per row, lane = byte: per 64 bytes every lane classifies its byte from the bytes p, p + 1, p + 2
@@ -11,17 +11,19 @@
 // the chunks before gives every token its ordinal = its output column, and the lane of a token's first byte walks the
 // token (FNV-1a, stopping one byte past the longest key: such a token is in no table), probes the open-addressing table
 // and compares the bytes of a slot whose hash and length agree.  Tokens past `width` are counted, not looked up.  The
-// wave then writes START / END and pads the row.
+// wave then writes START / END and pads the row.  The classifier, the chunk scan and the walk are text_scan.inc.h,
+// shared with vocab_fit.hip.
 #include "common.h"
 
 #include <string.h>
 
 namespace {
 
+#include "text_scan.inc.h"
+
 constexpr int TT = 256;                         // threads per workgroup: four rows
 constexpr uint32_t TABLE_MAGIC = 0x314e4b54u;   // "TKN1"
 constexpr int HDR_WORDS = 8;                    // magic, slots, longest key, keys, byte offset of the key bytes, total bytes, 0, 0
-constexpr uint32_t FNV_SEED = 2166136261u;
 
 struct Slot {                                   // 16 bytes; len < 0: empty
     uint32_t hash;
@@ -29,23 +31,6 @@ struct Slot {                                   // 16 bytes; len < 0: empty
     int32_t len;
     int32_t id;
 };
-
-__host__ __device__ inline uint32_t fnv_step(uint32_t h, uint32_t b) { return (h ^ b) * 16777619u; }
-__host__ __device__ inline uint32_t first_slot(uint32_t h, uint32_t mask) { return (h ^ (h >> 16)) & mask; }
-
-// Bytes of the whitespace character that BEGINS with c0 c1 c2 (0: none does).  U+0009-000D, 001C-0020; C2 85, C2 A0;
-// E1 9A 80; E2 80 80..8A, E2 80 A8, E2 80 A9, E2 80 AF; E2 81 9F; E3 80 80.
-__host__ __device__ inline int ws_len(unsigned c0, unsigned c1, unsigned c2) {
-    if ((c0 >= 0x09u && c0 <= 0x0du) || (c0 >= 0x1cu && c0 <= 0x20u)) return 1;
-    if (c0 == 0xc2u) return (c1 == 0x85u || c1 == 0xa0u) ? 2 : 0;
-    if (c0 == 0xe1u) return (c1 == 0x9au && c2 == 0x80u) ? 3 : 0;
-    if (c0 == 0xe2u) {
-        if (c1 == 0x80u) return ((c2 >= 0x80u && c2 <= 0x8au) || c2 == 0xa8u || c2 == 0xa9u || c2 == 0xafu) ? 3 : 0;
-        return (c1 == 0x81u && c2 == 0x9fu) ? 3 : 0;
-    }
-    if (c0 == 0xe3u) return (c1 == 0x80u && c2 == 0x80u) ? 3 : 0;
-    return 0;
-}
 
 __host__ __device__ inline size_t slots_for(size_t n) {
     size_t s = 2;
@@ -82,37 +67,15 @@ __global__ __launch_bounds__(TT) void tokenize_kernel(const uint8_t* __restrict_
     int32_t* out = out_ids + (size_t)row * out_stride;
 
     int n_tok = 0;                                                   // tokens of the chunks before
-    int carry1 = 0, carry2 = 0;                                      // ws_len of the previous chunk's last / second-last byte
-    bool prev_ws = true;                                             // the byte before this chunk is whitespace (or the row's start)
+    ChunkScan scan;
     for (long long base = s; base < e; base += 64) {
         const long long p = base + lane;
-        const unsigned c0 = p < e ? text[p] : 0u, c1 = p + 1 < e ? text[p + 1] : 0u, c2 = p + 2 < e ? text[p + 2] : 0u;
-        const int L = p < e ? ws_len(c0, c1, c2) : 0;
-        int L1 = __shfl_up(L, 1, 64), L2 = __shfl_up(L, 2, 64);
-        if (lane == 0) { L1 = carry1; L2 = carry2; }
-        if (lane == 1) L2 = carry1;
-        const bool ws = L > 0 || L1 >= 2 || L2 == 3 || p >= e;      // beyond the row: no token either
-        const unsigned long long wsm = __ballot(ws);
-        const bool before_ws = lane == 0 ? prev_ws : ((wsm >> (lane - 1)) & 1ull) != 0;
-        const bool tok_start = !ws && before_ws;
-        const unsigned long long tsm = __ballot(tok_start);
-        const long long col = (long long)n_tok + __popcll(tsm & ((1ull << lane) - 1ull)) + add_special;
+        const bool tok_start = scan.step(text, base, e, lane);
+        const long long col = (long long)n_tok + scan.before(lane) + add_special;
         if (tok_start && col < width) {
-            // the token ends in front of the next whitespace character (its bytes are in none, so that character BEGINS
-            // there) or at the row's end; one byte past the longest key it is UNK wherever it ends
-            uint32_t h = FNV_SEED;
-            long long len = 0, q = p;
-            unsigned a0 = c0, a1 = c1, a2 = c2;
-            for (;;) {
-                h = fnv_step(h, a0);
-                ++len;
-                ++q;
-                if (q >= e || len > max_key) break;
-                a0 = a1;
-                a1 = a2;
-                a2 = q + 2 < e ? text[q + 2] : 0u;
-                if (ws_len(a0, a1, a2) > 0) break;
-            }
+            // one byte past the longest key the token is UNK wherever it ends
+            uint32_t h;
+            const long long len = token_walk(text, p, e, scan.c0, scan.c1, scan.c2, max_key, h);
             int id = unk_id;
             if (table_ok && len <= max_key) {
                 uint32_t sl = first_slot(h, mask);
@@ -133,10 +96,7 @@ __global__ __launch_bounds__(TT) void tokenize_kernel(const uint8_t* __restrict_
             }
             out[col] = id;
         }
-        n_tok += __popcll(tsm);
-        carry1 = __shfl(L, 63, 64);
-        carry2 = __shfl(L, 62, 64);
-        prev_ws = ((wsm >> 63) & 1ull) != 0;
+        n_tok += __popcll(scan.starts);
     }
     const long long count = (long long)n_tok + (add_special ? 2 : 0);
     const int n = (int)(count < width ? count : width);

@@ -1,20 +1,21 @@
 """The two entry points of the reference's CLI that sit on the hot path, with its argument and option names
-(img2latex/cli.py:104-120 ``train``, :253-269 ``predict``):
+(img2latex/cli.py:104-120 ``train``, :253-269 ``predict``), and ``vocab``, which this package adds:
 
     python -m img2latex_amd predict CHECKPOINT IMAGE [--beam-size N] [--max-length N] [--temperature T]
                                                      [--top-k K] [--top-p P] [--device cuda]
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
                                   [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
                                   [--augment]
+    python -m img2latex_amd vocab FORMULAS_FILE OUT [--max-sequence-length N] [--device cuda]
 
 ``predict`` is the reference's chain end to end on the device: Predictor.from_checkpoint (predictor.py:61-137) ->
 Predictor.predict(image_path) (:139-203) -> load_image (data/utils.py:18-90) -> encoder -> greedy search -> string.
 
 ``train`` builds the model from the YAML exactly as cli.py:195-217 does, resumes model + Adam state from a reference
 checkpoint (trainer.py:235-269) and drives ``TrainStep`` (the optimisation step of trainer.py:303-343 on the HIP
-kernels) over the batches of the data loaders.  Dataset classes, file decoding and vocabulary fitting are outside this
-package's scope: the batches come from the reference's own ``create_data_loaders`` /
-``LaTeXTokenizer`` when the ``img2latex`` package is importable beside this one, or -- ``--synthetic-steps N`` -- from
+kernels) over the batches of the data loaders.  Dataset classes and file decoding are outside this
+package's scope: the batches come from the reference's own ``create_data_loaders`` with its
+``LaTeXTokenizer`` (``train`` still fits its vocabulary there) when the ``img2latex`` package is importable beside this one, or -- ``--synthetic-steps N`` -- from
 the deterministic generator the benchmarks use.  After every epoch it validates as Trainer.train does
 (trainer.py:667-766): ``training.validate`` on the validation batches, ReduceLROnPlateau on val_loss, a best checkpoint
 (``best_checkpoint_epoch_E_step_S.pt`` + ``best_checkpoint.pt``) or a plain one, early stopping after
@@ -27,6 +28,10 @@ then a shift within 2 %, NEAREST, white fill; ``data.Augment.tensor``), never a 
 batches arrive preprocessed, so the 2 % is a fraction of the preprocessed tensor's size, not of the raw page's as in the
 reference; ``data.preprocess_batch(pages, augment=...)`` is the reference-order path for raw pages.  Experiment registry, logging setup
 and rich console output are the reference's host-side orchestration and are not rebuilt here.
+
+``vocab`` fits the vocabulary of a formulas file on the device (LaTeXTokenizer.fit_on_formulas_file, tokenizer.py:
+119-141, through ``TokenTable.fit_on_formulas_file``) and writes it in LaTeXTokenizer.save's layout (:257-275), which both
+``TokenTable.load`` and the reference's ``LaTeXTokenizer.load`` read.
 
 The device is a ROCm GPU; ``--device cpu`` is refused (there is no CPU fallback in this package).
 """
@@ -56,6 +61,17 @@ def predict(checkpoint_path: str, image_path: str, beam_size: int = 0, max_lengt
     predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device))
     return predictor.predict(image=image_path, beam_size=beam_size, max_length=max_length, temperature=temperature,
                              top_k=top_k, top_p=top_p)
+
+
+def vocab(formulas_file: str, out_path: str, max_sequence_length: int = 150, device: Optional[str] = None):
+    """Fit on ``formulas_file``, save to ``out_path``; returns the fitted TokenTable."""
+    from .training import TokenTable
+    table = TokenTable(max_sequence_length=max_sequence_length)
+    fitted = table.fit_on_formulas_file(formulas_file, device=_device(device))
+    table.save(out_path)
+    print(f"vocabulary of {table.vocab_size} tokens from {fitted.rows} formulas ({fitted.total_tokens} tokens, longest "
+          f"{fitted.longest_row}) -> {out_path}")
+    return table
 
 
 def load_config(config_path: str) -> Dict:
@@ -259,12 +275,20 @@ def main(argv: Optional[List[str]] = None) -> int:
     t.add_argument("--augment", action="store_true",
                    help="(this package) warp each training batch on the device as the reference's training split is "
                         "(rotation within 5 degrees, shift within 2 %% of the batch's size, NEAREST, white fill)")
+    v = sub.add_parser("vocab", help="(this package) Fit the vocabulary of a formulas file on the device and save it.")
+    v.add_argument("formulas_file", help="Path to the formulas file, one formula per line")
+    v.add_argument("out_path", help="Path to save the vocabulary to (LaTeXTokenizer.save's layout)")
+    v.add_argument("--max-sequence-length", type=int, default=150, help="Maximum sequence length stored with the vocabulary")
+    v.add_argument("--device", default=None, help="Device to fit on (cuda)")
     args = ap.parse_args(argv)
     if args.command == "predict":
         latex = predict(args.checkpoint_path, args.image_path, args.beam_size, args.max_length, args.temperature,
                         args.top_k, args.top_p, args.device)
         print("Generated LaTeX:")
         print(latex)
+        return 0
+    if args.command == "vocab":
+        vocab(args.formulas_file, args.out_path, args.max_sequence_length, args.device)
         return 0
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,

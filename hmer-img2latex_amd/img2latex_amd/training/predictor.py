@@ -14,6 +14,8 @@ drivers: SURVEY 8b "feed tensors straight to the encoder").
 """
 from __future__ import annotations
 
+import os
+import warnings
 import weakref
 from typing import Dict, List, Optional, Sequence, Union
 
@@ -27,18 +29,22 @@ DEFAULT_SPECIAL_TOKENS = {"PAD": "<PAD>", "START": "<START>", "END": "<END>", "U
 
 
 class TokenTable:
-    """The part of LaTeXTokenizer the predictor touches: id maps, special ids, decode()
-    (tokenizer.py:68-78,166-192).  String <-> id only; fitting a vocabulary is out of scope."""
+    """LaTeXTokenizer's host surface (tokenizer.py:24-321): id maps, special ids, encode() / decode(), save() / load() in
+    the reference's file layout, and fit() / fit_on_formulas_file(), which count and order the tokens on the device
+    (training/vocab.py, i2l_vocab_fit).  The batch calls are TokenizeTable / DetokenizeTable."""
 
     def __init__(self, token_to_id: Optional[Dict[str, int]] = None, special_tokens: Optional[Dict[str, str]] = None,
                  max_sequence_length: int = 141):
         self.special_tokens = dict(special_tokens or DEFAULT_SPECIAL_TOKENS)
         if token_to_id is None:
             token_to_id = {tok: i for i, tok in enumerate(self.special_tokens.values())}
+        self.max_sequence_length = max_sequence_length
+        self._set_vocabulary(token_to_id)
+
+    def _set_vocabulary(self, token_to_id: Dict[str, int]) -> None:
         self.token_to_id = dict(token_to_id)
         self.id_to_token = {i: t for t, i in self.token_to_id.items()}
         self.vocab_size = len(self.token_to_id)
-        self.max_sequence_length = max_sequence_length
         self.pad_token_id = self.token_to_id[self.special_tokens["PAD"]]
         self.start_token_id = self.token_to_id[self.special_tokens["START"]]
         self.end_token_id = self.token_to_id[self.special_tokens["END"]]
@@ -51,6 +57,56 @@ class TokenTable:
     def config(self) -> Dict:
         return {"token_to_id": self.token_to_id, "special_tokens": self.special_tokens,
                 "max_sequence_length": self.max_sequence_length}
+
+    def encode(self, text: str, add_special_tokens: bool = False) -> List[int]:
+        """tokenizer.py:143-164 on the host: ``str.split()``, unknown -> UNK, START / END around the text when asked."""
+        if add_special_tokens:
+            text = f"{self.special_tokens['START']} {text} {self.special_tokens['END']}"
+        return [self.token_to_id.get(tok, self.unk_token_id) for tok in text.split()]
+
+    def _refit(self, fitted) -> None:
+        """Take a fitted vocabulary (training/vocab.py): the maps and the four special ids anew, as ``_init_special_tokens``
+        + ``fit`` leave them, this object's cached device tables dropped (they hold the old vocabulary), and the
+        reference's warning about rows longer than ``max_sequence_length`` (tokenizer.py:106-113)."""
+        from . import tokenizer as _tokenizer
+        self._set_vocabulary(fitted.token_to_id)
+        for cache in (_TABLES, _tokenizer._TABLES):
+            cache.pop(self, None)
+        if self.max_sequence_length is not None and fitted.longest_row > self.max_sequence_length:
+            warnings.warn(f"Found sequences of length {fitted.longest_row}, which is longer than max_sequence_length "
+                          f"({self.max_sequence_length}). Consider increasing max_sequence_length.")
+
+    def fit(self, texts: Sequence[str], device=None):
+        """LaTeXTokenizer.fit (tokenizer.py:80-117) with the counting and ordering on the device: the vocabulary is reset
+        to the special tokens, then every other token of ``texts`` (``str.split()``) gets the next id by descending
+        count, ties in first-seen order.  Returns the ``VocabFit`` (counts, total, longest row).  An empty ``texts``
+        raises ValueError, as the reference's ``max()`` does."""
+        from .vocab import fit_vocabulary
+        fitted = fit_vocabulary(texts, self.special_tokens, device)
+        self._refit(fitted)
+        return fitted
+
+    def fit_on_formulas_file(self, file_path: str, device=None):
+        """tokenizer.py:119-141: one formula per line (UTF-8, universal newlines), each wrapped in START / END -- which
+        changes no id and adds 2 to every row's length.  The file's bytes go to the device as they are."""
+        from .vocab import fit_formulas_file
+        fitted = fit_formulas_file(file_path, self.special_tokens, device)
+        self._refit(fitted)
+        return fitted
+
+    def save(self, file_path: str) -> None:
+        """tokenizer.py:257-275: ``torch.save`` of ``config()``'s three keys; LaTeXTokenizer.load reads it."""
+        if os.path.dirname(file_path):
+            os.makedirs(os.path.dirname(file_path), exist_ok=True)
+        torch.save(self.config(), file_path)
+
+    @classmethod
+    def load(cls, file_path: str) -> "TokenTable":
+        """tokenizer.py:277-321: reads what ``save`` or LaTeXTokenizer.save wrote."""
+        if not os.path.exists(file_path):
+            raise FileNotFoundError(f"Tokenizer file not found: {file_path}")
+        saved = torch.load(file_path, map_location="cpu")
+        return cls(saved["token_to_id"], saved["special_tokens"], saved["max_sequence_length"])
 
 
 def token_image(tokenizer):

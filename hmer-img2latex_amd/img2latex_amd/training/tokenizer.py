@@ -32,6 +32,17 @@ def pack_texts(texts: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
     return np.frombuffer(blob, dtype=np.uint8), off
 
 
+def upload_packed(data: np.ndarray, off: np.ndarray, device):
+    """``pack_texts``' result in ONE host -> device copy on the current stream, the offsets in front of the bytes:
+    ``(text uint8, row_off int32)`` device views of it."""
+    head = off.size * 4
+    both = np.empty(head + max(data.size, 1), dtype=np.uint8)
+    both[:head] = off.view(np.uint8)
+    both[head:head + data.size] = data
+    dev = torch.from_numpy(both).to(device)
+    return dev[head:head + data.size], dev[:head].view(torch.int32)
+
+
 def tokenize_image(tokenizer) -> Optional[np.ndarray]:
     """The vocabulary as i2l_tokenize probes it: the self-contained hash table image the library's host function
     i2l_tokenize_table_build makes from ``token_to_id`` (every key in UTF-8 with its id), as a uint8 array.  Works on
@@ -85,13 +96,7 @@ class TokenizeTable:
     def upload(self, texts: Sequence[str], packed=None):
         """``pack_texts`` (or its result, ``packed``) + ONE host -> device copy on the current stream, the offsets in front
         of the bytes: ``(text uint8, row_off int32)`` device views of it."""
-        data, off = pack_texts(texts) if packed is None else packed
-        head = off.size * 4
-        both = np.empty(head + max(data.size, 1), dtype=np.uint8)
-        both[:head] = off.view(np.uint8)
-        both[head:head + data.size] = data
-        dev = torch.from_numpy(both).to(self.device)
-        return dev[head:head + data.size], dev[:head].view(torch.int32)
+        return upload_packed(*(pack_texts(texts) if packed is None else packed), self.device)
 
     def launch(self, text: torch.Tensor, row_off: torch.Tensor, width: int, add_special: bool = False,
                out: Optional[torch.Tensor] = None):

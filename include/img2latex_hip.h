@@ -560,6 +560,43 @@ int i2l_tokenize(const uint8_t* text, int64_t text_bytes, const int32_t* row_off
                  int32_t* out_ids, int out_stride, int32_t* out_len, int32_t* out_count, int32_t* status,
                  i2l_stream_t stream);
 
+/* Text -> the fitted vocabulary on the device: LaTeXTokenizer.fit (tokenizer.py:80-117).  text / row_off / rows and the
+ * token rule are i2l_tokenize's (DEVICE arrays, str.split() per row; a row boundary separates tokens).  Every distinct
+ * token is counted; the tokens are ordered by count descending, ties by first occurrence in the corpus (the smallest
+ * byte offset into `text` of any occurrence: Counter's insertion order under a stable sort), so the order is unique and
+ * does not depend on scheduling.  A token whose bytes equal one of the n_skip skip strings (HOST pointers: string i =
+ * skip_bytes[skip_off[i] .. skip_off[i + 1]), at most 8 strings and 256 bytes together -- the special tokens, which
+ * keep their ids) is counted and not emitted.
+ * Outputs (DEVICE), in rank order r = 0 .. emitted - 1: token r = out_bytes[out_off[r] .. out_off[r + 1]) packed without
+ * gaps (out_off: out_capacity + 1 int32), out_count[r], out_first[r] (its first byte offset in `text`); out_capacity
+ * tokens and out_byte_capacity bytes at most, nothing is written beyond either.
+ * meta (DEVICE, I2L_VOCAB_FIT_META_WORDS int32, all written by the call): [0] distinct tokens to emit, [1] distinct
+ * tokens skipped, [2] tokens in total, [3] the largest token count of a row, [4] bytes the emitted tokens need,
+ * [5] status, [6..7] 0, [8 + i] the count of skip string i (0 when it does not occur).
+ * status bits: I2L_VOCAB_FIT_FULL -- more than slots / 2 distinct tokens, or a probe found no slot: the results are not to
+ * be used, call again with more slots; I2L_VOCAB_FIT_BAD_OFFSETS -- i2l_tokenize's rule, the row reads as empty;
+ * I2L_VOCAB_FIT_OUT_TOO_SMALL -- [0] > out_capacity or [4] > out_byte_capacity (both still say what is needed).
+ * slots: a power of two in [2, 2^28], the open-addressing table in the workspace (24 bytes per slot;
+ * i2l_vocab_fit_workspace_bytes is pure host code and returns 0 for rows < 0 or unusable slots).  The workspace
+ * (8-byte aligned) is cleared on `stream` by the call itself; the library keeps no state between calls.
+ * flags: 0, or I2L_VOCAB_FIT_NO_AGGREGATE -- count with one global atomic per token instead of gathering per workgroup
+ * in LDS first (same results; kept for the ablation in profiles/vocab_fit_cost.py).
+ * I2L_ERR_UNSUPPORTED before any launch: text_bytes beyond int32, n_skip > 8, more than 256 skip bytes; I2L_ERR_ARG: a
+ * negative size, slots no power of two, unknown flags, a missing pointer, descending skip offsets; I2L_ERR_WORKSPACE.
+ * Launches on `stream`, no host synchronisation: count (a wave per row, lane = byte; find-or-claim by ONE 64-bit
+ * compare-and-swap of (offset << 32 | length) of a representative occurrence, nothing waits), compact, bitonic sort by
+ * (~count << 32 | first offset), offsets + meta, emit. */
+#define I2L_VOCAB_FIT_META_WORDS 16
+#define I2L_VOCAB_FIT_FULL 1
+#define I2L_VOCAB_FIT_BAD_OFFSETS 2
+#define I2L_VOCAB_FIT_OUT_TOO_SMALL 4
+#define I2L_VOCAB_FIT_NO_AGGREGATE 1
+size_t i2l_vocab_fit_workspace_bytes(int rows, int64_t slots);
+int i2l_vocab_fit(const uint8_t* text, int64_t text_bytes, const int32_t* row_off, int rows, const uint8_t* skip_bytes,
+                  const int32_t* skip_off, int n_skip, int64_t slots, int flags, uint8_t* out_bytes,
+                  int64_t out_byte_capacity, int32_t* out_off, int32_t* out_count, int32_t* out_first, int out_capacity,
+                  int32_t* meta, void* workspace, size_t workspace_bytes, i2l_stream_t stream);
+
 /* masked_accuracy, metrics.py:226-238 (trainer.py:391,526): over rows = B*T logits rows of `vocab` floats,
  * correct_total_out[0] = #(argmax == target and target != pad), [1] = #(target != pad); first index wins
  * ties.  The (B,T,V) logits never leave the device (the reference copies them to the host every step). */
