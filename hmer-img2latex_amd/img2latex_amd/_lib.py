@@ -129,6 +129,13 @@ _SIGNATURES.update({
     "i2l_tokenize_table_build": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     "i2l_tokenize": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_size_t] + [c_int] * 6 +
                      [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "i2l_tokenize_packed_workspace_bytes": (c_size_t, [c_int]),
+    "i2l_tokenize_packed": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_size_t] + [c_int] * 4 +
+                            [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2l_collate_ids": (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_int, c_int, c_int,
+                                c_void_p, c_int, c_void_p, c_void_p]),
+    "i2l_gather_ragged_u8": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p,
+                                     ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
     "i2l_vocab_fit_workspace_bytes": (c_size_t, [c_int, ctypes.c_int64]),
     "i2l_vocab_fit": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int,
                       c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t,

@@ -1,11 +1,13 @@
-"""The two entry points of the reference's CLI that sit on the hot path, with its argument and option names
-(img2latex/cli.py:104-120 ``train``, :253-269 ``predict``), and ``vocab``, which this package adds:
+"""The three entry points of the reference's CLI that sit on the hot path, with its argument and option names
+(img2latex/cli.py:104-120 ``train``, :253-269 ``predict``, :315-332 ``evaluate``), and ``vocab``, which this package adds:
 
     python -m img2latex_amd predict CHECKPOINT IMAGE [--beam-size N] [--max-length N] [--temperature T]
                                                      [--top-k K] [--top-p P] [--device cuda]
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
                                   [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
-                                  [--augment]
+                                  [--augment] [--data {auto,native,reference}]
+    python -m img2latex_amd evaluate CHECKPOINT DATA_DIR [--split test] [--batch-size 32] [--num-samples N]
+                                                         [--beam-size 0] [--device cuda] [--output-dir outputs]
     python -m img2latex_amd vocab FORMULAS_FILE OUT [--max-sequence-length N] [--device cuda]
 
 ``predict`` is the reference's chain end to end on the device: Predictor.from_checkpoint (predictor.py:61-137) ->
@@ -13,10 +15,13 @@ Predictor.predict(image_path) (:139-203) -> load_image (data/utils.py:18-90) -> 
 
 ``train`` builds the model from the YAML exactly as cli.py:195-217 does, resumes model + Adam state from a reference
 checkpoint (trainer.py:235-269) and drives ``TrainStep`` (the optimisation step of trainer.py:303-343 on the HIP
-kernels) over the batches of the data loaders.  Dataset classes and file decoding are outside this
-package's scope: the batches come from the reference's own ``create_data_loaders`` with its
-``LaTeXTokenizer`` (``train`` still fits its vocabulary there) when the ``img2latex`` package is importable beside this one, or -- ``--synthetic-steps N`` -- from
-the deterministic generator the benchmarks use.  After every epoch it validates as Trainer.train does
+kernels) over the batches of the data loaders.  ``--data native``: the vocabulary is fitted on the device
+(``TokenTable.fit_on_formulas_file``) and the batches come from this package's device-resident data set
+(``data.create_data_loaders``, data/dataset.py: pages decoded and uploaded once, formulas tokenized once, the
+reference's samples, order and batches).  ``--data reference``: the reference's own ``create_data_loaders`` with its
+``LaTeXTokenizer``, which needs the ``img2latex`` package beside this one.  ``--data auto`` (the default) takes the
+reference's when that package is importable, as before, and the native ones otherwise.  ``--synthetic-steps N``: the
+deterministic generator the benchmarks use instead of a data directory.  After every epoch it validates as Trainer.train does
 (trainer.py:667-766): ``training.validate`` on the validation batches, ReduceLROnPlateau on val_loss, a best checkpoint
 (``best_checkpoint_epoch_E_step_S.pt`` + ``best_checkpoint.pt``) or a plain one, early stopping after
 ``training.early_stopping_patience`` epochs without improvement, and ``metrics/metrics.json`` when
@@ -26,8 +31,14 @@ batches); without it, it makes one pass and writes one plain checkpoint, as befo
 batch on the device as the reference's training split is warped (data/dataset.py:486-492: rotation within 5 degrees,
 then a shift within 2 %, NEAREST, white fill; ``data.Augment.tensor``), never a validation batch.  One difference: the
 batches arrive preprocessed, so the 2 % is a fraction of the preprocessed tensor's size, not of the raw page's as in the
-reference; ``data.preprocess_batch(pages, augment=...)`` is the reference-order path for raw pages.  Experiment registry, logging setup
-and rich console output are the reference's host-side orchestration and are not rebuilt here.
+reference; ``data.preprocess_batch(pages, augment=...)`` is the reference-order path for raw pages, and the one the
+native loaders take: with ``--data native`` the warp is applied to the raw page, inside the loader.  Experiment
+registry, logging setup and rich console output are the reference's host-side orchestration and are not rebuilt here.
+
+``evaluate`` is cli.py:315-518: Predictor.from_checkpoint, the native loaders built from the checkpoint's config and
+tokenizer, ``Predictor.evaluate_stream`` over the split (greedy; a beam size above 0 is clamped with a warning, as the
+reference clamps it), the three result lines, and ``<output-dir>/<experiment>/predictions/predictions.json`` with the
+experiment name taken from the checkpoint's path.  BLEU and Levenshtein are means over all pairs of the split.
 
 ``vocab`` fits the vocabulary of a formulas file on the device (LaTeXTokenizer.fit_on_formulas_file, tokenizer.py:
 119-141, through ``TokenTable.fit_on_formulas_file``) and writes it in LaTeXTokenizer.save's layout (:257-275), which both
@@ -107,12 +118,14 @@ def _synthetic_batches(config: Dict, steps: int, vocab_size: int, seed: int):
 def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: str = "img2latex_v1",
           checkpoint_path: Optional[str] = None, data_dir: Optional[str] = None, device: Optional[str] = None,
           seed: int = 42, synthetic_steps: int = 0, synthetic_vocab: int = 512, output_dir: str = "outputs",
-          synthetic_val_steps: int = 0, augment: bool = False) -> Dict:
+          synthetic_val_steps: int = 0, augment: bool = False, data: str = "auto") -> Dict:
     """cli.py:104-250 reduced to the hot path: model from the config, optional resume, TrainStep over the batches, a
     checkpoint in the reference's layout (trainer.py:209-224) per epoch, and -- with validation batches -- the epoch-end
     validation / LR schedule / best checkpoint / early stop of trainer.py:713-766.  Returns {"loss", "steps",
     "global_step", "checkpoint"}, plus {"best_val_loss", "val_metrics"} when validation ran.  ``augment``: warp each
-    training batch with ``data.Augment(seed=seed).tensor`` (keyed by epoch and the sample's position in the epoch)."""
+    training batch with ``data.Augment(seed=seed).tensor`` (keyed by epoch and the sample's position in the epoch); the
+    native loaders warp the raw pages with the same keys instead.  ``data``: "auto", "native" or "reference" (see the
+    module docstring)."""
     import random
     from . import data as D
     from .training import EarlyStopping, PlateauSchedule, TokenTable, TrainStep, save_checkpoint, validate
@@ -125,6 +138,7 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
     dev = _device(device or config["training"].get("device"))
     tcfg = config["training"]
     resume = torch.load(checkpoint_path, map_location="cpu", weights_only=False) if checkpoint_path else None
+    native = False                                                          # the native loaders warp the raw pages themselves
     if synthetic_steps > 0:
         if resume is not None:
             tk = resume["tokenizer_config"]
@@ -137,16 +151,30 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
         if synthetic_val_steps > 0:                                         # ... unless there is something to validate on
             max_epochs = int(tcfg.get("epochs", 50))
     else:
-        try:
-            from img2latex.data.dataset import create_data_loaders          # the reference's own dataset + tokenizer
-            from img2latex.data.tokenizer import LaTeXTokenizer
-        except ImportError as exc:
-            raise SystemExit("img2latex_amd train: datasets and vocabulary fitting are the reference's (img2latex.data."
-                             "dataset / tokenizer, outside this package's scope); install it beside this package, or "
-                             f"pass --synthetic-steps N.  ({exc})")
-        tokenizer = LaTeXTokenizer(max_sequence_length=config["data"]["max_seq_length"])
-        tokenizer.fit_on_formulas_file(os.path.join(config["data"]["data_dir"], config["data"]["formulas_file"]))
-        loaders = create_data_loaders(config=config, tokenizer=tokenizer, max_samples=None)
+        if data not in ("auto", "native", "reference"):
+            raise SystemExit(f"img2latex_amd train: --data {data}: expected auto, native or reference")
+        create_data_loaders = None
+        if data != "native":
+            try:
+                from img2latex.data.dataset import create_data_loaders      # the reference's own dataset + tokenizer
+                from img2latex.data.tokenizer import LaTeXTokenizer
+            except ImportError as exc:
+                if data == "reference":
+                    raise SystemExit("img2latex_amd train --data reference: the reference's datasets and tokenizer "
+                                     "(img2latex.data.dataset / tokenizer) are not importable; install that package "
+                                     f"beside this one, or use --data native.  ({exc})")
+        formulas_path = os.path.join(config["data"]["data_dir"], config["data"].get("formulas_file", "im2latex_formulas.norm.lst"))
+        if create_data_loaders is not None:
+            tokenizer = LaTeXTokenizer(max_sequence_length=config["data"]["max_seq_length"])
+            tokenizer.fit_on_formulas_file(formulas_path)
+            loaders = create_data_loaders(config=config, tokenizer=tokenizer, max_samples=None)
+        else:
+            native = True
+            tokenizer = TokenTable(max_sequence_length=int(config["data"].get("max_seq_length", 150)))
+            tokenizer.fit_on_formulas_file(formulas_path, device=dev)
+            loaders = D.create_data_loaders(config, tokenizer, device=dev, augment=D.Augment(seed=seed) if augment else None)
+            if not loaders:
+                raise SystemExit(f"img2latex_amd train: no samples under {config['data']['data_dir']}")
         max_epochs = int(tcfg.get("epochs", 50))                            # trainer.py:118
     model = build_model(config, tokenizer.vocab_size)
     if resume is not None:
@@ -179,9 +207,11 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
     stopper = EarlyStopping.from_checkpoint(int(tcfg.get("early_stopping_patience", 10)), resume)   # :120-122,257-262
     val_metrics = None
     accum = max(1, int(tcfg.get("accumulation_steps", 1)))                  # trainer.py:86-88 (the shipped config: 4)
-    warp = D.Augment(seed=seed) if augment else None                        # dataset.py:486-492, the defaults are its values
+    warp = D.Augment(seed=seed) if augment and not native else None         # dataset.py:486-492, the defaults are its values
     for epoch in range(start_epoch + 1, max_epochs + 1):                    # `epoch` = trainer.py's current_epoch + 1
         batches = _synthetic_batches(config, synthetic_steps, tokenizer.vocab_size, seed) if loaders is None else loaders["train"]
+        if native:
+            batches.set_epoch(epoch - 1)                                    # the warp's key, as below
         it = iter(batches)
         batch, batch_idx, seen = next(it, None), 0, 0
         while batch is not None:
@@ -231,6 +261,77 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
     return out
 
 
+def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_size: int = 32,
+             num_samples: Optional[int] = None, beam_size: int = 0, device: Optional[str] = None,
+             output_dir: str = "outputs") -> Dict:
+    """cli.py:315-518 on the device: returns {"bleu", "levenshtein", "batch_size"} over the whole split -- the means over
+    all pairs, as ``calculate_metrics`` on the reference's two lists computes them -- after printing the three result
+    lines and writing ``predictions.json``.
+
+    One thing the reference does on the way is kept because it decides the predictions: its loop hands the loader's
+    image TENSORS to ``predict_batch``, whose ``_prepare_image`` (predictor.py:464-499) rescales every tensor with a value
+    below 0 or above 1 once more, ``x / 255 * 2 - 1`` -- which is every normalised page, but not the zero image of an
+    unreadable file.  ``_prepare_image``'s other step, the bilinear resize of a tensor that is not 64 x 800, is not
+    repeated: the loaders are built at the model's own input size, and the reference's encoder cannot run any other."""
+    import json
+    import warnings
+    from pathlib import Path
+    from . import data as D
+    from .training import Predictor
+    from .training import metrics as M
+    dev = _device(device)
+    experiment_name = Path(checkpoint_path).parent.parent.name              # cli.py:340-349: outputs/<experiment>/checkpoints/<file>
+    config = torch.load(checkpoint_path, map_location="cpu", weights_only=False).get("config", {}) or {}
+    predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=dev)
+    max_samples = {"train": None, "val": None, "test": None}
+    if num_samples:
+        max_samples[split] = num_samples
+    cfg_data = config.setdefault("data", {})                                # cli.py:412-420
+    cfg_data.setdefault("data_dir", data_dir)
+    cfg_data.setdefault("batch_size", batch_size)
+    cfg_data.setdefault("num_workers", 0)
+    loaders = D.create_data_loaders(config, predictor.tokenizer, max_samples=max_samples, device=dev)
+    if split not in loaders:
+        raise SystemExit(f"Invalid split: {split}")
+    loader = loaders[split]
+    if beam_size > 0:                                                       # predictor.py:231-235
+        warnings.warn("Beam search is unsupported; using greedy decoding (beam_size=0).")
+    print(f"Evaluating on {split} split with {len(loader.dataset)} samples")
+    is_resnet = predictor.model_type == "resnet_lstm"
+    raw: List[str] = []
+
+    def batches():
+        for batch in loader:
+            x = batch["images"]
+            lo, hi = x.amin(dim=(1, 2, 3), keepdim=True), x.amax(dim=(1, 2, 3), keepdim=True)
+            x = torch.where((lo < 0) | (hi > 1), x / 255.0 * 2.0 - 1.0, x)  # predictor.py:493-497, per image
+            if is_resnet and x.shape[1] == 1:                               # :453-455
+                x = D.batch_convert_for_resnet(x)
+            raw.extend(batch["raw_formulas"])
+            yield x, batch["formulas"]
+
+    stats, predictions = [], []
+    for out in predictor.evaluate_stream(batches(), max_length=predictor.tokenizer.max_sequence_length, return_strings=True,
+                                         return_statistics=True):
+        stats.append(out["statistics"])
+        predictions.extend(out["pred_text"])
+    if not stats:
+        raise SystemExit(f"img2latex_amd evaluate: the {split} split is empty")
+    metrics = M.metrics_from_packed(torch.cat(stats).contiguous())
+    print("Evaluation Results:")
+    print(f"BLEU-4 Score: {metrics['bleu']:.4f}")
+    print(f"Levenshtein Similarity: {metrics['levenshtein']:.4f}")
+    print(f"Number of Samples: {metrics['batch_size']}")
+    if experiment_name:                                                     # cli.py:504-517
+        predictions_dir = os.path.join(output_dir, experiment_name, "predictions")
+        os.makedirs(predictions_dir, exist_ok=True)
+        save_path = os.path.join(predictions_dir, "predictions.json")
+        with open(save_path, "w") as f:
+            json.dump([{"prediction": p, "reference": r} for p, r in zip(predictions, raw)], f, indent=2)
+        print(f"Predictions saved to: {save_path}")
+    return metrics
+
+
 def _save_basic_metrics(metrics_dir: str, epoch: int, val_metrics: Dict) -> None:
     """trainer.py:645-661: metrics.json keyed by the 1-based epoch, merged into what the file already holds."""
     import json
@@ -275,6 +376,18 @@ def main(argv: Optional[List[str]] = None) -> int:
     t.add_argument("--augment", action="store_true",
                    help="(this package) warp each training batch on the device as the reference's training split is "
                         "(rotation within 5 degrees, shift within 2 %% of the batch's size, NEAREST, white fill)")
+    t.add_argument("--data", choices=("auto", "native", "reference"), default="auto",
+                   help="(this package) where the batches come from: this package's device-resident data set (native), the "
+                        "reference's data loaders (reference), or the reference's when importable and else the native ones (auto)")
+    e = sub.add_parser("evaluate", help="Evaluate the model on a dataset.")
+    e.add_argument("checkpoint_path", help="Path to trained model checkpoint")
+    e.add_argument("data_dir", help="Path to data directory")
+    e.add_argument("--split", default="test", help="Data split to evaluate on (train, val, test)")
+    e.add_argument("--batch-size", type=int, default=32, help="Batch size for evaluation")
+    e.add_argument("--num-samples", type=int, default=None, help="Number of samples to evaluate (None for all)")
+    e.add_argument("--beam-size", type=int, default=0, help="Beam size for beam search (0 for greedy search)")
+    e.add_argument("--device", default=None, help="Device to use for evaluation (cuda)")
+    e.add_argument("--output-dir", default="outputs", help="(this package) root of <experiment>/predictions")
     v = sub.add_parser("vocab", help="(this package) Fit the vocabulary of a formulas file on the device and save it.")
     v.add_argument("formulas_file", help="Path to the formulas file, one formula per line")
     v.add_argument("out_path", help="Path to save the vocabulary to (LaTeXTokenizer.save's layout)")
@@ -290,9 +403,14 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.command == "vocab":
         vocab(args.formulas_file, args.out_path, args.max_sequence_length, args.device)
         return 0
+    if args.command == "evaluate":
+        evaluate(args.checkpoint_path, args.data_dir, args.split, args.batch_size, args.num_samples, args.beam_size,
+                 args.device, args.output_dir)
+        return 0
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,
-              args.synthetic_steps, args.synthetic_vocab, args.output_dir, args.synthetic_val_steps, args.augment)
+              args.synthetic_steps, args.synthetic_vocab, args.output_dir, args.synthetic_val_steps, args.augment,
+              args.data)
     except SystemExit:
         raise
     except Exception as exc:                                                # cli.py:247-250: failure -> exit code 1

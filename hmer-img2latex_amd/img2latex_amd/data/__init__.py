@@ -1,4 +1,8 @@
 from .augment import Augment, white_fill
-from .preprocess import batch_convert_for_resnet, load_image, preprocess_batch, resize_bilinear
+from .dataset import (DeviceDataset, DeviceLoader, FormulaStore, PageStore, create_data_loaders, loader_settings,
+                      read_split)
+from .preprocess import batch_convert_for_resnet, load_image, preprocess_batch, preprocess_resident, resize_bilinear
 
-__all__ = ["load_image", "preprocess_batch", "batch_convert_for_resnet", "resize_bilinear", "Augment", "white_fill"]
+__all__ = ["load_image", "preprocess_batch", "preprocess_resident", "batch_convert_for_resnet", "resize_bilinear", "Augment",
+           "white_fill", "FormulaStore", "PageStore", "DeviceDataset", "DeviceLoader", "create_data_loaders",
+           "loader_settings", "read_split"]

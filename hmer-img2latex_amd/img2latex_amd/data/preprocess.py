@@ -124,6 +124,170 @@ def _extents(flt: int, ins: np.ndarray, outs: np.ndarray):
     return first.astype(np.int64), last.astype(np.int64)
 
 
+def _check_options(channels: int, resample: str, normalize, tables: str, device):
+    """The options preprocess_batch and preprocess_resident share: (filter, normalize code, device)."""
+    if tables not in ("device", "host"):
+        raise ValueError("tables must be 'device' or 'host'")
+    flt = {"lanczos": _lib.FILTER_LANCZOS, "bicubic": _lib.FILTER_BICUBIC}[resample]
+    normalize = 2 if normalize == "symmetric" else int(bool(normalize))
+    if channels not in (1, 3):
+        raise ValueError("channels must be 1 or 3")
+    if not torch.cuda.is_available():
+        raise RuntimeError("img2latex_amd: the preprocessing kernels need the ROCm device; there is no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return flt, normalize, dev
+
+
+class _BatchPlan:
+    """What the planning part hands to the uploading and the launching part: the shapes (h, w, c), the plan records, the
+    table request (None with ``tables="host"``: the plans then point into the device's table pool ``pool``), the page
+    sizes and their packed offsets, and the temporary rows."""
+    __slots__ = ("n", "h", "w", "c", "new_w", "plans", "tab_req", "pool", "sizes", "src_off", "tmp_rows", "tmp_bytes")
+
+
+def _plan_batch(shapes: np.ndarray, out_h: int, channels: int, keep_aspect: bool, out_w: int, flt: int, tables: str,
+                dev: torch.device) -> _BatchPlan:
+    """The part that plans: (n, 3) int64 shapes (h, w, c) -> plans and table requests.  Touches the device only with
+    ``tables="host"`` (new sizes enter the table pool).  Call under ``torch.cuda.device(dev)``."""
+    P = _BatchPlan()
+    n = P.n = shapes.shape[0]
+    h, w, c = shapes[:, 0], shapes[:, 1], shapes[:, 2]
+    P.h, P.w, P.c = h, w, c
+    if int(h.min()) == 0 or int(w.min()) == 0:
+        raise ValueError("empty image")
+    # transforms.py:33-36: int(round(target_h * (w / h))) -- Python's round() and numpy's both round half to even
+    new_w = np.round(out_h * (w / h)).astype(np.int64) if keep_aspect else np.full(n, out_w, np.int64)
+    if int(new_w.min()) <= 0:
+        bad = int(np.argmin(new_w))
+        raise ValueError(f"image {bad} ({int(h[bad])}x{int(w[bad])}) collapses to zero width at height {out_h}")
+    P.new_w, P.pool = new_w, None
+    if tables == "host":
+        pool = P.pool = _pool(dev)
+        hkeys = [(int(a), int(b), flt) for a, b in zip(w, new_w)]
+        vkeys = [(int(a), out_h, flt) for a in h]
+        pool.lookup(hkeys + vkeys)
+        ent_h = np.array([pool.index[k] for k in hkeys], np.int64)
+        ent_v = np.array([pool.index[k] for k in vkeys], np.int64)
+        P.tab_req = None
+    else:
+        # 2n tables (n horizontal w -> new_w, n vertical h -> out_h) laid out back to back in one per-batch buffer
+        t_in = np.concatenate([w, h]).astype(np.int32)
+        t_out = np.concatenate([new_w, np.full(n, out_h, np.int64)]).astype(np.int32)
+        ks = _ksizes(flt, t_in, t_out)
+        if int(ks.max()) > 2 * 512:
+            raise ValueError("down-scaling by more than ~80x is not supported")
+        t_size = t_out.astype(np.int64) * (2 + ks)
+        t_off = np.zeros(2 * n, np.int64)
+        t_off[1:] = np.cumsum(t_size[:-1])
+        first, last = _extents(flt, t_in[n:], t_out[n:])
+        ent_h = np.stack([t_off[:n], t_off[:n] + 2 * t_out[:n], ks[:n]], axis=1)
+        ent_v = np.stack([t_off[n:], t_off[n:] + 2 * t_out[n:], ks[n:], first, last], axis=1)
+        P.tab_req = (t_in, t_out, t_off, int(t_size.sum()), int(t_out.max()))
+    plans = P.plans = np.zeros(n, PLAN_DTYPE)
+    sizes = P.sizes = h * w * c
+    src_off = P.src_off = np.zeros(n, np.int64)
+    src_off[1:] = np.cumsum(sizes[:-1])
+    need_h = new_w != w
+    tmp_rows = P.tmp_rows = np.where(need_h, ent_v[:, 4] - ent_v[:, 3], 0)
+    tmp_bytes = P.tmp_bytes = (tmp_rows * new_w * channels + 255) // 256 * 256
+    tmp_off = np.zeros(n, np.int64)
+    tmp_off[1:] = np.cumsum(tmp_bytes[:-1])
+    plans["src_offset"], plans["tmp_offset"] = src_off, tmp_off
+    plans["bh_offset"], plans["kh_offset"], plans["kh_ksize"] = ent_h[:, 0], ent_h[:, 1], ent_h[:, 2]
+    plans["bv_offset"], plans["kv_offset"], plans["kv_ksize"] = ent_v[:, 0], ent_v[:, 1], ent_v[:, 2]
+    plans["src_h"], plans["src_w"], plans["src_c"], plans["new_w"] = h, w, c, new_w
+    plans["ybox_first"] = np.where(need_h, ent_v[:, 3], 0)
+    plans["tmp_rows"] = tmp_rows
+    plans["need_h"], plans["need_v"] = need_h, h != out_h
+    return P
+
+
+def _upload_batch(dev: torch.device, P: _BatchPlan, flats, warp, upload_stream, tail: np.ndarray = None):
+    """The part that uploads: ONE pinned block -> ONE device block ``d_all``, laid out as [pixels | plans | table
+    requests | warp parameters | tail], every part at a multiple of 256 bytes.  ``flats``: the host pages, packed into the
+    pixel region (i2l_pack_host); None: the pixel region is left for the device to fill and only what lies behind it is
+    uploaded.  ``tail``: any further uint8 block (the resident path's gather list).  Returns ``(d_all, p0, p1, p2, p3)``:
+    the byte offsets of the plans, the table requests, the warp parameters and the tail."""
+    n = P.n
+    total_px = int(P.sizes.sum())
+    plan_bytes = n * PLAN_DTYPE.itemsize
+    req_bytes = 0 if P.tab_req is None else 2 * n * (4 + 4 + 8)
+    p0 = (total_px + 255) // 256 * 256
+    p1 = (p0 + plan_bytes + 255) // 256 * 256
+    p2 = p3 = None
+    if warp is not None:                                          # the warp parameters: behind everything else
+        p2 = (p1 + req_bytes + 255) // 256 * 256
+        req_bytes = p2 - p1 + warp.nbytes
+    if tail is not None:
+        p3 = (p1 + req_bytes + 255) // 256 * 256
+        req_bytes = p3 - p1 + tail.nbytes
+    first = 0 if flats is not None else p0                        # the first byte that is uploaded
+    st, slot, pinned = _staging(dev, p1 + req_bytes + 256)
+    host = pinned.numpy()
+    if flats is not None:
+        # the pages -> one pinned block, on several host threads (one thread copies 16 MB in ~3 ms)
+        ptrs = np.fromiter((a.__array_interface__["data"][0] for a in flats), dtype=np.uint64, count=n)
+        _lib.check(_lib.lib().i2l_pack_host(ptrs.ctypes.data, P.sizes.ctypes.data, P.src_off.ctypes.data, n, pinned.data_ptr(),
+                                            min(4, os.cpu_count() or 1)), "pack_host")      # 16 MB: 0.39 / 0.18 / 0.25 ms on 1 / 4 / 8 threads
+    host[p0:p0 + plan_bytes] = P.plans.view(np.uint8)
+    if P.tab_req is not None:
+        t_in, t_out, t_off, t_total, t_max_out = P.tab_req
+        host[p1:p1 + 8 * n] = t_in.view(np.uint8)
+        host[p1 + 8 * n:p1 + 16 * n] = t_out.view(np.uint8)
+        host[p1 + 16 * n:p1 + 32 * n] = t_off.view(np.uint8)
+    if warp is not None:
+        host[p2:p2 + warp.nbytes] = warp.view(np.uint8)
+    if tail is not None:
+        host[p3:p3 + tail.nbytes] = tail
+    cur = torch.cuda.current_stream(dev)
+    with torch.cuda.stream(upload_stream if upload_stream is not None else cur):
+        # allocated under the uploading stream: memory the caching allocator hands out there has no pending work
+        # of the compute stream on it, so the copy need not wait for the previous batch's kernels
+        d_all = torch.empty((p1 + req_bytes,), dtype=torch.uint8, device=dev)
+        d_all[first:].copy_(pinned[first:p1 + req_bytes], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+    st["events"][slot] = ev
+    if upload_stream is not None:
+        cur.wait_event(ev)
+        d_all.record_stream(cur)
+    return d_all, p0, p1, p2, p3
+
+
+def _launch_batch(dev: torch.device, P: _BatchPlan, d_all: torch.Tensor, p0: int, p1: int, p2, flt: int, channels: int,
+                  out_h: int, out_w: int, normalize: int, augment) -> torch.Tensor:
+    """The part that launches, on the current stream: the tables (``tables="device"``), the optional warp, then
+    i2l_preprocess_images on the pixel region of ``d_all``."""
+    n = P.n
+    max_tmp_px = int((P.tmp_rows * P.new_w).max())
+    ws = torch.empty((max(int(P.tmp_bytes.sum()), 16),), dtype=torch.uint8, device=dev)
+    out = torch.empty((n, channels, out_h, out_w), dtype=torch.float32, device=dev)
+    if P.tab_req is None:
+        tab = P.pool.tables
+    else:
+        t_total, t_max_out = P.tab_req[3], P.tab_req[4]
+        tab = torch.empty((max(t_total, 4),), dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().i2l_resample_coeffs_device(flt, 2 * n, d_all.data_ptr() + p1, d_all.data_ptr() + p1 + 8 * n,
+                                                         d_all.data_ptr() + p1 + 16 * n, tab.data_ptr(), t_max_out,
+                                                         _lib.stream_ptr()), "resample_coeffs_device")
+    pages = d_all
+    if augment is not None:
+        pages = augment.pages(d_all[:p0], d_all.data_ptr() + p0, d_all.data_ptr() + p2, n, int(max(P.h.max(), P.w.max())),
+                              int(P.sizes.max()))
+    _lib.check(_lib.lib().i2l_preprocess_images(pages.data_ptr(), d_all.data_ptr() + p0, tab.data_ptr(), n,
+                                                max_tmp_px, channels, out_h, out_w, normalize,
+                                                ws.data_ptr(), out.data_ptr(), _lib.stream_ptr()), "preprocess_images")
+    return out
+
+
+def _warp_params(augment, P: _BatchPlan, sample_ids, epoch: int):
+    if augment is None:
+        return None
+    return augment.params(list(zip(P.h.tolist(), P.w.tolist())), np.arange(P.n) if sample_ids is None else sample_ids, epoch)
+
+
 def preprocess_batch(images: Sequence[np.ndarray], img_size: Tuple[int, int] = (64, 800), channels: int = 1,
                      normalize=True, device=None, keep_aspect: bool = True, resample: str = "lanczos",
                      upload_stream=None, tables: str = "device", augment=None, sample_ids=None,
@@ -146,17 +310,7 @@ def preprocess_batch(images: Sequence[np.ndarray], img_size: Tuple[int, int] = (
     (dataset.py:486-492: rotation, then shift, NEAREST, white fill), keyed by ``sample_ids`` (default 0 .. n-1) and
     ``epoch``.  Its parameter block rides in the same upload and ONE more launch (i2l_affine_nearest_u8) writes the
     warped pages to a second pixel buffer, on which the unchanged plans and tables then run.  ``None``: nothing changes."""
-    if tables not in ("device", "host"):
-        raise ValueError("tables must be 'device' or 'host'")
-    flt = {"lanczos": _lib.FILTER_LANCZOS, "bicubic": _lib.FILTER_BICUBIC}[resample]
-    normalize = 2 if normalize == "symmetric" else int(bool(normalize))
-    if channels not in (1, 3):
-        raise ValueError("channels must be 1 or 3")
-    if not torch.cuda.is_available():
-        raise RuntimeError("img2latex_amd: the preprocessing kernels need the ROCm device; there is no CPU fallback")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    flt, normalize, dev = _check_options(channels, resample, normalize, tables, device)
     out_h, out_w = int(img_size[0]), int(img_size[1])
     n = len(images)
     if n == 0:
@@ -172,106 +326,42 @@ def preprocess_batch(images: Sequence[np.ndarray], img_size: Tuple[int, int] = (
         raise TypeError("images must be uint8 arrays of shape (H, W) or (H, W, 3)")
     flats = [a if a.flags.c_contiguous else np.ascontiguousarray(a) for a in images]
     shapes = np.array(dims, np.int64).reshape(n, 3)
-    h, w, c = shapes[:, 0], shapes[:, 1], shapes[:, 2]
-    if int(h.min()) == 0 or int(w.min()) == 0:
-        raise ValueError("empty image")
-    # transforms.py:33-36: int(round(target_h * (w / h))) -- Python's round() and numpy's both round half to even
-    new_w = np.round(out_h * (w / h)).astype(np.int64) if keep_aspect else np.full(n, out_w, np.int64)
-    if int(new_w.min()) <= 0:
-        bad = int(np.argmin(new_w))
-        raise ValueError(f"image {bad} ({int(h[bad])}x{int(w[bad])}) collapses to zero width at height {out_h}")
     with torch.cuda.device(dev):
-        if tables == "host":
-            pool = _pool(dev)
-            hkeys = [(int(a), int(b), flt) for a, b in zip(w, new_w)]
-            vkeys = [(int(a), out_h, flt) for a in h]
-            pool.lookup(hkeys + vkeys)
-            ent_h = np.array([pool.index[k] for k in hkeys], np.int64)
-            ent_v = np.array([pool.index[k] for k in vkeys], np.int64)
-            tab_req = None
-        else:
-            # 2n tables (n horizontal w -> new_w, n vertical h -> out_h) laid out back to back in one per-batch buffer
-            t_in = np.concatenate([w, h]).astype(np.int32)
-            t_out = np.concatenate([new_w, np.full(n, out_h, np.int64)]).astype(np.int32)
-            ks = _ksizes(flt, t_in, t_out)
-            if int(ks.max()) > 2 * 512:
-                raise ValueError("down-scaling by more than ~80x is not supported")
-            t_size = t_out.astype(np.int64) * (2 + ks)
-            t_off = np.zeros(2 * n, np.int64)
-            t_off[1:] = np.cumsum(t_size[:-1])
-            first, last = _extents(flt, t_in[n:], t_out[n:])
-            ent_h = np.stack([t_off[:n], t_off[:n] + 2 * t_out[:n], ks[:n]], axis=1)
-            ent_v = np.stack([t_off[n:], t_off[n:] + 2 * t_out[n:], ks[n:], first, last], axis=1)
-            tab_req = (t_in, t_out, t_off, int(t_size.sum()), int(t_out.max()))
-        plans = np.zeros(n, PLAN_DTYPE)
-        sizes = h * w * c
-        src_off = np.zeros(n, np.int64)
-        src_off[1:] = np.cumsum(sizes[:-1])
-        need_h = new_w != w
-        tmp_rows = np.where(need_h, ent_v[:, 4] - ent_v[:, 3], 0)
-        tmp_bytes = (tmp_rows * new_w * channels + 255) // 256 * 256
-        tmp_off = np.zeros(n, np.int64)
-        tmp_off[1:] = np.cumsum(tmp_bytes[:-1])
-        plans["src_offset"], plans["tmp_offset"] = src_off, tmp_off
-        plans["bh_offset"], plans["kh_offset"], plans["kh_ksize"] = ent_h[:, 0], ent_h[:, 1], ent_h[:, 2]
-        plans["bv_offset"], plans["kv_offset"], plans["kv_ksize"] = ent_v[:, 0], ent_v[:, 1], ent_v[:, 2]
-        plans["src_h"], plans["src_w"], plans["src_c"], plans["new_w"] = h, w, c, new_w
-        plans["ybox_first"] = np.where(need_h, ent_v[:, 3], 0)
-        plans["tmp_rows"] = tmp_rows
-        plans["need_h"], plans["need_v"] = need_h, h != out_h
-        total_px = int(sizes.sum())
-        plan_bytes = n * PLAN_DTYPE.itemsize
-        req_bytes = 0 if tab_req is None else 2 * n * (4 + 4 + 8)
-        p0 = (total_px + 255) // 256 * 256
-        p1 = (p0 + plan_bytes + 255) // 256 * 256
-        if augment is not None:                                   # the warp parameters: behind everything else
-            warp = augment.params(list(zip(h.tolist(), w.tolist())), np.arange(n) if sample_ids is None else sample_ids, epoch)
-            p2 = (p1 + req_bytes + 255) // 256 * 256
-            req_bytes = p2 - p1 + warp.nbytes
-        st, slot, pinned = _staging(dev, p1 + req_bytes + 256)
-        host = pinned.numpy()
-        # the pages -> one pinned block, on several host threads (one thread copies 16 MB in ~3 ms)
-        ptrs = np.fromiter((a.__array_interface__["data"][0] for a in flats), dtype=np.uint64, count=n)
-        _lib.check(_lib.lib().i2l_pack_host(ptrs.ctypes.data, sizes.ctypes.data, src_off.ctypes.data, n, pinned.data_ptr(),
-                                            min(4, os.cpu_count() or 1)), "pack_host")      # 16 MB: 0.39 / 0.18 / 0.25 ms on 1 / 4 / 8 threads
-        host[p0:p0 + plan_bytes] = plans.view(np.uint8)
-        if tab_req is not None:
-            t_in, t_out, t_off, t_total, t_max_out = tab_req
-            host[p1:p1 + 8 * n] = t_in.view(np.uint8)
-            host[p1 + 8 * n:p1 + 16 * n] = t_out.view(np.uint8)
-            host[p1 + 16 * n:p1 + 32 * n] = t_off.view(np.uint8)
-        if augment is not None:
-            host[p2:p2 + warp.nbytes] = warp.view(np.uint8)
-        cur = torch.cuda.current_stream(dev)
-        with torch.cuda.stream(upload_stream if upload_stream is not None else cur):
-            # allocated under the uploading stream: memory the caching allocator hands out there has no pending work
-            # of the compute stream on it, so the copy need not wait for the previous batch's kernels
-            d_all = torch.empty((p1 + req_bytes,), dtype=torch.uint8, device=dev)
-            d_all.copy_(pinned[:p1 + req_bytes], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        st["events"][slot] = ev
-        if upload_stream is not None:
-            cur.wait_event(ev)
-            d_all.record_stream(cur)
-        max_tmp_px = int((tmp_rows * new_w).max())
-        ws = torch.empty((max(int(tmp_bytes.sum()), 16),), dtype=torch.uint8, device=dev)
-        out = torch.empty((n, channels, out_h, out_w), dtype=torch.float32, device=dev)
-        if tab_req is None:
-            tab = pool.tables
-        else:
-            tab = torch.empty((max(t_total, 4),), dtype=torch.int32, device=dev)
-            _lib.check(_lib.lib().i2l_resample_coeffs_device(flt, 2 * n, d_all.data_ptr() + p1, d_all.data_ptr() + p1 + 8 * n,
-                                                             d_all.data_ptr() + p1 + 16 * n, tab.data_ptr(), t_max_out,
-                                                             _lib.stream_ptr()), "resample_coeffs_device")
-        pages = d_all
-        if augment is not None:
-            pages = augment.pages(d_all[:p0], d_all.data_ptr() + p0, d_all.data_ptr() + p2, n, int(max(h.max(), w.max())),
-                                  int(sizes.max()))
-        _lib.check(_lib.lib().i2l_preprocess_images(pages.data_ptr(), d_all.data_ptr() + p0, tab.data_ptr(), n,
-                                                    max_tmp_px, channels, out_h, out_w, normalize,
-                                                    ws.data_ptr(), out.data_ptr(), _lib.stream_ptr()), "preprocess_images")
-    return out
+        P = _plan_batch(shapes, out_h, channels, keep_aspect, out_w, flt, tables, dev)
+        d_all, p0, p1, p2, _ = _upload_batch(dev, P, flats, _warp_params(augment, P, sample_ids, epoch), upload_stream)
+        return _launch_batch(dev, P, d_all, p0, p1, p2, flt, channels, out_h, out_w, normalize, augment)
+
+
+def preprocess_resident(store, indices, img_size: Tuple[int, int] = (64, 800), channels: int = 1, normalize=True,
+                        keep_aspect: bool = True, resample: str = "lanczos", upload_stream=None, tables: str = "device",
+                        augment=None, sample_ids=None, epoch: int = 0) -> torch.Tensor:
+    """``preprocess_batch`` for pages that already live on the device: ``store`` is a ``PageStore`` (data/dataset.py),
+    ``indices`` the batch's store rows (repeats allowed, none of a failed page).  The planning and the launches are
+    ``preprocess_batch``'s own; what differs is the upload: only the small block -- plans, table requests, warp
+    parameters and the gather list (three int64 per page) -- crosses the bus, and ONE more launch (i2l_gather_ragged_u8)
+    copies the pages from the store into the batch's pixel region, at the offsets the plans already name.  The result
+    is bit-identical to ``preprocess_batch`` on the same pages."""
+    dev = store.device
+    flt, normalize, dev = _check_options(channels, resample, normalize, tables, dev)
+    out_h, out_w = int(img_size[0]), int(img_size[1])
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    n = idx.size
+    if n == 0:
+        return torch.empty((0, channels, out_h, out_w), dtype=torch.float32, device=dev)
+    if int(idx.min()) < 0 or int(idx.max()) >= len(store) or bool(store.failed[idx].any()):
+        raise IndexError("preprocess_resident: an index outside the store, or of a page that failed to decode")
+    shapes = np.ascontiguousarray(store.shapes[idx])
+    with torch.cuda.device(dev):
+        P = _plan_batch(shapes, out_h, channels, keep_aspect, out_w, flt, tables, dev)
+        gather = np.concatenate([store.offsets[idx], P.sizes, P.src_off]).astype(np.int64)
+        d_all, p0, p1, p2, p3 = _upload_batch(dev, P, None, _warp_params(augment, P, sample_ids, epoch), upload_stream,
+                                              gather.view(np.uint8))
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        g = d_all.data_ptr() + p3
+        _lib.check(_lib.lib().i2l_gather_ragged_u8(store.pixels.data_ptr(), store.pixels.numel(), g, g + 8 * n, n,
+                                                   int(P.sizes.max()), d_all.data_ptr(), p0, g + 16 * n, status.data_ptr(),
+                                                   _lib.stream_ptr()), "gather_ragged_u8")
+        return _launch_batch(dev, P, d_all, p0, p1, p2, flt, channels, out_h, out_w, normalize, augment)
 
 
 def load_image(image_path: str, img_size: Tuple[int, int] = (64, 800), channels: int = 1,

@@ -455,7 +455,8 @@ class Predictor:
         lengths) and copied beside the statistics; a tokenizer without a device image decodes "pred_ids" on the host."""
         return self._evaluate_finish(self._evaluate_launch(images, targets, max_length, return_strings=return_strings))
 
-    def evaluate_stream(self, batches, max_length: Optional[int] = None, lookahead: int = 2):
+    def evaluate_stream(self, batches, max_length: Optional[int] = None, lookahead: int = 2, return_strings: bool = False,
+                        return_statistics: bool = False):
         """``evaluate_batch`` over an iterable of (images, targets), one result per batch in order, software-pipelined:
         the host work of batch i+1 (shape pass, packing the ragged pages into pinned memory, their upload on a side
         stream) runs while the device is still busy with batch i, and the host only waits for batch i's statistics
@@ -474,12 +475,18 @@ class Predictor:
         other host-known width, the byte-length bound, is about twice as wide and takes the statistics kernel off its
         <= 256 path; the statistics do not depend on the padded width.  ``collate`` never cuts a row, so i2l_tokenize's
         status word travels with the statistics, and a batch in which a row WAS cut (a formula of more than
-        max_sequence_length tokens) is run again with ``collate``'s width when its statistics are collected."""
+        max_sequence_length tokens) is run again with ``collate``'s width when its statistics are collected.
+
+        ``return_strings``: as in ``evaluate_batch`` ("pred_text").  ``return_statistics``: every result also carries
+        "statistics", a host copy of its (B, 9) int32 statistics rows; ``metrics.metrics_from_packed`` of the rows of all
+        batches, concatenated, gives the means over all pairs of a split (not means of batch means)."""
         from collections import deque
         pending = deque()
         lookahead = max(1, min(int(lookahead), 2))           # the landing buffers / decoder slots rotate over 4 / 3
         for images, targets in batches:
-            pending.append(self._evaluate_launch(images, targets, max_length, side_upload=True, coresident=True))
+            pending.append(self._evaluate_launch(images, targets, max_length, side_upload=True, coresident=True,
+                                                 return_strings=return_strings))
+            pending[-1]["return_statistics"] = return_statistics
             if len(pending) > lookahead:
                 yield self._evaluate_finish(pending.popleft())
         while pending:
@@ -630,16 +637,21 @@ class Predictor:
         if _lib.ids_timed_out(host[:, 9:10]) and h["rows_per_workgroup"] == 0:
             # the timeout fallback of Seq2SeqModel.greedy_ids_host: the row-per-workgroup kernel needs no partner
             raw, targets, max_length = h["raw"]
-            return self._evaluate_finish(self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=1,
-                                                               return_strings=h["return_strings"]))
+            again = self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=1, return_strings=h["return_strings"])
+            again["return_statistics"] = h.get("return_statistics", False)
+            return self._evaluate_finish(again)
         _lib.check_ids(host[:, 9:10])
         if host.shape[1] > 10 and int(host[0, 10]) != 0:
             # string targets at the stream's fixed width and a row was cut: once more with collate's width
             raw, targets, max_length = h["raw"]
-            return self._evaluate_finish(self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=h["rows_per_workgroup"],
-                                                               return_strings=h["return_strings"]))
+            again = self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=h["rows_per_workgroup"],
+                                          return_strings=h["return_strings"])
+            again["return_statistics"] = h.get("return_statistics", False)
+            return self._evaluate_finish(again)
         out = M.metrics_from_packed(host)
         out["pred_ids"], out["pred_len"] = h["p_ids"], h["p_len"]
+        if h.get("return_statistics"):
+            out["statistics"] = host[:, :9].clone()                  # the landing buffer is reused
         if h["text"] is not None:
             out["pred_text"] = DetokenizeTable.strings(*h["text"])
         elif h["return_strings"]:

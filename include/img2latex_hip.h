@@ -560,6 +560,54 @@ int i2l_tokenize(const uint8_t* text, int64_t text_bytes, const int32_t* row_off
                  int32_t* out_ids, int out_stride, int32_t* out_len, int32_t* out_count, int32_t* status,
                  i2l_stream_t stream);
 
+/* Text -> ragged token ids (CSR) on the device: a whole corpus tokenized once, e.g. a data set's formulas file.  Inputs,
+ * token rule, id rule and add_special are i2l_tokenize's (DEVICE text / row_off, the table image, the special ids); the
+ * difference is the row rule: a row is never cut and never padded.  Row r is out_ids[out_off[r] .. out_off[r + 1]),
+ * packed without gaps; with add_special = 1 it is start_id, the row's tokens, end_id (an empty row: those two).
+ * out_off has rows + 1 **int64** entries (the exclusive scan of the row counts, [rows] = the total): the rows of a text
+ * of up to 2^31 - 1 bytes hold up to 2^30 tokens plus two per row, so the total needs no int32 refusal.
+ * *status (device word, cleared by the call) = 0, or I2L_TOKENIZE_PACKED_OVERFLOW (bit 0): the total exceeds
+ * out_capacity (ids) -- out_off is complete all the same (the caller learns the size needed) and no id at or beyond
+ * out_capacity is written; bits 1 and 2 are i2l_tokenize's: some row's offsets were unusable (it reads as an empty row),
+ * the table image does not describe itself (every token is unk_id).
+ * I2L_ERR_UNSUPPORTED before any launch: text_bytes beyond int32; rows > 2^31 - 1025.  rows == 0: only the scan runs
+ * (out_off[0] = 0).  Otherwise three launches on `stream`, no host wait: count per row (a wave per row, lane = byte,
+ * i2l_tokenize's chunk scan without a look-up), scan (one workgroup, chunks of 1024 rows with a running carry: any
+ * number of rows), write (i2l_tokenize's row body: chunk scan, walk, probe, compare).  workspace: rows int32. */
+#define I2L_TOKENIZE_PACKED_OVERFLOW 1
+size_t i2l_tokenize_packed_workspace_bytes(int rows);
+int i2l_tokenize_packed(const uint8_t* text, int64_t text_bytes, const int32_t* row_off, int rows, const void* table,
+                        size_t table_bytes, int unk_id, int start_id, int end_id, int add_special, int32_t* out_ids,
+                        int64_t out_capacity, int64_t* out_off, int32_t* status, void* workspace, size_t workspace_bytes,
+                        i2l_stream_t stream);
+
+/* Im2LatexCollator (dataset.py:59-66) from the CSR store i2l_tokenize_packed wrote: ids (n_ids int32) and off
+ * (rows + 1 int64), DEVICE arrays.  index: B int64 store rows (DEVICE; repeats allowed).  Row b of out (B, out_stride >=
+ * width) int32 is store row index[b] followed by pad_id up to `width`; columns behind `width` are not written.
+ * *status (device word, cleared by the call) = 0, or I2L_COLLATE_ROW_TOO_LONG (bit 0): a store row is longer than
+ * `width`; I2L_COLLATE_BAD_INDEX (bit 1): an index outside [0, rows), or offsets that do not lie inside [0, n_ids].
+ * Such a row is written as pad_id only and no store word outside a row is read.
+ * I2L_ERR_UNSUPPORTED: width <= 0, out_stride < width.  B == 0 is I2L_OK with no launch.  Otherwise one memset and ONE
+ * launch on `stream`: a wave per row, lane = column (neighbouring lanes write neighbouring columns). */
+#define I2L_COLLATE_ROW_TOO_LONG 1
+#define I2L_COLLATE_BAD_INDEX 2
+int i2l_collate_ids(const int32_t* ids, int64_t n_ids, const int64_t* off, int64_t rows, const int64_t* index, int B, int width,
+                    int pad_id, int32_t* out, int out_stride, int32_t* status, i2l_stream_t stream);
+
+/* n byte ranges of a resident buffer -> a compact batch buffer: range i is src[src_off[i] .. src_off[i] + size[i]) and
+ * goes to dst[dst_off[i] ..) (int64 DEVICE arrays; the destinations must not overlap each other or src).  A size of 0 is
+ * legal; any source and any destination alignment works.  src_bytes / dst_bytes are the buffers' sizes: a range that
+ * leaves either (or a negative size / offset) is not copied and sets *status (device word, cleared by the call) to 1.
+ * max_size = the largest size[i] (it sizes the grid: 16 KB tiles, several workgroups per large range; a range beyond it
+ * is still copied whole).  Lanes map to consecutive groups of 16 destination bytes, stored with aligned 16-byte stores;
+ * the source is one 16-byte load when its alignment agrees, else aligned words shifted together; the < 16 bytes at
+ * either end, and the groups at a range's ends whose words would reach outside it, go byte by byte -- no byte outside a
+ * source range is read, none outside a destination range written.
+ * I2L_ERR_UNSUPPORTED: n > 65535.  n == 0 is I2L_OK with no launch.  Otherwise one memset and ONE launch on `stream`. */
+int i2l_gather_ragged_u8(const uint8_t* src, int64_t src_bytes, const int64_t* src_off, const int64_t* size, int n,
+                         int64_t max_size, uint8_t* dst, int64_t dst_bytes, const int64_t* dst_off, int32_t* status,
+                         i2l_stream_t stream);
+
 /* Text -> the fitted vocabulary on the device: LaTeXTokenizer.fit (tokenizer.py:80-117).  text / row_off / rows and the
  * token rule are i2l_tokenize's (DEVICE arrays, str.split() per row; a row boundary separates tokens).  Every distinct
  * token is counted; the tokens are ordered by count descending, ties by first occurrence in the corpus (the smallest
