@@ -136,6 +136,9 @@ _SIGNATURES.update({
                                 c_void_p, c_int, c_void_p, c_void_p]),
     "i2l_gather_ragged_u8": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p,
                                      ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
+    "i2l_png_decode_workspace_bytes": (c_size_t, [c_int, ctypes.c_int64]),
+    "i2l_png_decode": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
     "i2l_vocab_fit_workspace_bytes": (c_size_t, [c_int, ctypes.c_int64]),
     "i2l_vocab_fit": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int,
                       c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t,

@@ -5,9 +5,10 @@
                                                      [--top-k K] [--top-p P] [--device cuda]
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
                                   [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
-                                  [--augment] [--data {auto,native,reference}]
+                                  [--augment] [--data {auto,native,reference}] [--decode {host,device}]
     python -m img2latex_amd evaluate CHECKPOINT DATA_DIR [--split test] [--batch-size 32] [--num-samples N]
                                                          [--beam-size 0] [--device cuda] [--output-dir outputs]
+                                                         [--decode {host,device}]
     python -m img2latex_amd vocab FORMULAS_FILE OUT [--max-sequence-length N] [--device cuda]
 
 ``predict`` is the reference's chain end to end on the device: Predictor.from_checkpoint (predictor.py:61-137) ->
@@ -118,14 +119,15 @@ def _synthetic_batches(config: Dict, steps: int, vocab_size: int, seed: int):
 def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: str = "img2latex_v1",
           checkpoint_path: Optional[str] = None, data_dir: Optional[str] = None, device: Optional[str] = None,
           seed: int = 42, synthetic_steps: int = 0, synthetic_vocab: int = 512, output_dir: str = "outputs",
-          synthetic_val_steps: int = 0, augment: bool = False, data: str = "auto") -> Dict:
+          synthetic_val_steps: int = 0, augment: bool = False, data: str = "auto", decode: Optional[str] = None) -> Dict:
     """cli.py:104-250 reduced to the hot path: model from the config, optional resume, TrainStep over the batches, a
     checkpoint in the reference's layout (trainer.py:209-224) per epoch, and -- with validation batches -- the epoch-end
     validation / LR schedule / best checkpoint / early stop of trainer.py:713-766.  Returns {"loss", "steps",
     "global_step", "checkpoint"}, plus {"best_val_loss", "val_metrics"} when validation ran.  ``augment``: warp each
     training batch with ``data.Augment(seed=seed).tensor`` (keyed by epoch and the sample's position in the epoch); the
     native loaders warp the raw pages with the same keys instead.  ``data``: "auto", "native" or "reference" (see the
-    module docstring)."""
+    module docstring).  ``decode``: where the native loaders decode the page files, "host" (PIL) or "device"
+    (i2l_png_decode); None leaves it to the config key ``data.decode`` (default "host")."""
     import random
     from . import data as D
     from .training import EarlyStopping, PlateauSchedule, TokenTable, TrainStep, save_checkpoint, validate
@@ -172,7 +174,8 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
             native = True
             tokenizer = TokenTable(max_sequence_length=int(config["data"].get("max_seq_length", 150)))
             tokenizer.fit_on_formulas_file(formulas_path, device=dev)
-            loaders = D.create_data_loaders(config, tokenizer, device=dev, augment=D.Augment(seed=seed) if augment else None)
+            loaders = D.create_data_loaders(config, tokenizer, device=dev, augment=D.Augment(seed=seed) if augment else None,
+                                            decode=decode)
             if not loaders:
                 raise SystemExit(f"img2latex_amd train: no samples under {config['data']['data_dir']}")
         max_epochs = int(tcfg.get("epochs", 50))                            # trainer.py:118
@@ -263,7 +266,7 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
 
 def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_size: int = 32,
              num_samples: Optional[int] = None, beam_size: int = 0, device: Optional[str] = None,
-             output_dir: str = "outputs") -> Dict:
+             output_dir: str = "outputs", decode: Optional[str] = None) -> Dict:
     """cli.py:315-518 on the device: returns {"bleu", "levenshtein", "batch_size"} over the whole split -- the means over
     all pairs, as ``calculate_metrics`` on the reference's two lists computes them -- after printing the three result
     lines and writing ``predictions.json``.
@@ -272,7 +275,9 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
     image TENSORS to ``predict_batch``, whose ``_prepare_image`` (predictor.py:464-499) rescales every tensor with a value
     below 0 or above 1 once more, ``x / 255 * 2 - 1`` -- which is every normalised page, but not the zero image of an
     unreadable file.  ``_prepare_image``'s other step, the bilinear resize of a tensor that is not 64 x 800, is not
-    repeated: the loaders are built at the model's own input size, and the reference's encoder cannot run any other."""
+    repeated: the loaders are built at the model's own input size, and the reference's encoder cannot run any other.
+    ``decode``: "host" or "device", where the page files are decoded (``data.PageStore``); None: the checkpoint's
+    config key ``data.decode``, "host" when absent."""
     import json
     import warnings
     from pathlib import Path
@@ -290,7 +295,7 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
     cfg_data.setdefault("data_dir", data_dir)
     cfg_data.setdefault("batch_size", batch_size)
     cfg_data.setdefault("num_workers", 0)
-    loaders = D.create_data_loaders(config, predictor.tokenizer, max_samples=max_samples, device=dev)
+    loaders = D.create_data_loaders(config, predictor.tokenizer, max_samples=max_samples, device=dev, decode=decode)
     if split not in loaders:
         raise SystemExit(f"Invalid split: {split}")
     loader = loaders[split]
@@ -379,6 +384,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     t.add_argument("--data", choices=("auto", "native", "reference"), default="auto",
                    help="(this package) where the batches come from: this package's device-resident data set (native), the "
                         "reference's data loaders (reference), or the reference's when importable and else the native ones (auto)")
+    t.add_argument("--decode", choices=("host", "device"), default=None,
+                   help="(this package, --data native) decode the page files with PIL on the host or with the PNG kernel on "
+                        "the device; default: the config key data.decode, else host")
     e = sub.add_parser("evaluate", help="Evaluate the model on a dataset.")
     e.add_argument("checkpoint_path", help="Path to trained model checkpoint")
     e.add_argument("data_dir", help="Path to data directory")
@@ -388,6 +396,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     e.add_argument("--beam-size", type=int, default=0, help="Beam size for beam search (0 for greedy search)")
     e.add_argument("--device", default=None, help="Device to use for evaluation (cuda)")
     e.add_argument("--output-dir", default="outputs", help="(this package) root of <experiment>/predictions")
+    e.add_argument("--decode", choices=("host", "device"), default=None,
+                   help="(this package) decode the page files with PIL on the host or with the PNG kernel on the device")
     v = sub.add_parser("vocab", help="(this package) Fit the vocabulary of a formulas file on the device and save it.")
     v.add_argument("formulas_file", help="Path to the formulas file, one formula per line")
     v.add_argument("out_path", help="Path to save the vocabulary to (LaTeXTokenizer.save's layout)")
@@ -405,12 +415,12 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     if args.command == "evaluate":
         evaluate(args.checkpoint_path, args.data_dir, args.split, args.batch_size, args.num_samples, args.beam_size,
-                 args.device, args.output_dir)
+                 args.device, args.output_dir, args.decode)
         return 0
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,
               args.synthetic_steps, args.synthetic_vocab, args.output_dir, args.synthetic_val_steps, args.augment,
-              args.data)
+              args.data, args.decode)
     except SystemExit:
         raise
     except Exception as exc:                                                # cli.py:247-250: failure -> exit code 1

@@ -163,44 +163,203 @@ def decode_page(path: str, channels: int) -> Optional[np.ndarray]:
         return None
 
 
+class _PinnedUploader:
+    """Host pages -> device parts through one pinned block of about ``chunk_bytes``: ``add`` places a page at the next
+    multiple of PAGE_ALIGN and returns its offset in the concatenation of ``parts``; the block is uploaded when the next
+    page would not fit.  ``append`` takes a part that is on the device already (pages decoded there)."""
+
+    def __init__(self, dev: torch.device, chunk_bytes: int):
+        self.dev, self.chunk_bytes = dev, chunk_bytes
+        self.parts: List[torch.Tensor] = []                          # one device tensor per uploaded chunk
+        self.pinned, self.used, self.base, self.pending = None, 0, 0, []
+        self.seconds = 0.0
+
+    def add(self, arr: np.ndarray) -> int:
+        size = (arr.size + PAGE_ALIGN - 1) // PAGE_ALIGN * PAGE_ALIGN
+        if self.used and self.used + size > self.chunk_bytes:
+            self.flush()
+        if self.pinned is None or self.pinned.numel() < max(self.chunk_bytes, size):
+            self.pinned = torch.empty((max(self.chunk_bytes, size),), dtype=torch.uint8).pin_memory()
+        offset = self.base + self.used
+        self.pending.append((self.used, arr))
+        self.used += size
+        return offset
+
+    def flush(self) -> None:
+        if self.used == 0:
+            return
+        import time
+        t0 = time.perf_counter()
+        host = self.pinned.numpy()
+        for rel, arr in self.pending:
+            host[rel:rel + arr.size] = arr.reshape(-1)
+        with torch.cuda.device(self.dev):
+            part = torch.empty((self.used,), dtype=torch.uint8, device=self.dev)
+            part.copy_(self.pinned[:self.used], non_blocking=True)
+            torch.cuda.current_stream(self.dev).synchronize()        # the pinned block is filled again right away
+        self.parts.append(part)
+        self.base += self.used
+        self.used, self.pending = 0, []
+        self.seconds += time.perf_counter() - t0
+
+    def append(self, part: torch.Tensor) -> int:
+        """-> the offset of ``part`` (its size a multiple of PAGE_ALIGN) in the concatenation."""
+        self.flush()
+        offset = self.base
+        self.parts.append(part)
+        self.base += part.numel()
+        return offset
+
+    def pixels(self) -> torch.Tensor:
+        self.flush()
+        with torch.cuda.device(self.dev):
+            if len(self.parts) == 1:
+                return self.parts[0]
+            return torch.cat(self.parts) if self.parts else torch.zeros((PAGE_ALIGN,), dtype=torch.uint8, device=self.dev)
+
+
+_PNG_IMAGE = np.dtype([("z_off", "<i8"), ("z_len", "<i8"), ("pal_off", "<i8"), ("out_off", "<i8"), ("width", "<i4"),
+                       ("height", "<i4"), ("colour_type", "<i4"), ("pal_n", "<i4"), ("channels", "<i4"), ("reserved", "<i4")])
+
+
+def _read_png(path: str):
+    """The file's ``PngInfo`` when the device may decode it, else None (unreadable, not a PNG, not eligible)."""
+    from .png import parse_png
+    try:
+        with open(path, "rb") as f:
+            return parse_png(f.read())
+    except OSError:
+        return None
+
+
+def _png_launch(infos, channels: int, dev: torch.device, seconds: Dict[str, float]):
+    """One i2l_png_decode launch over the parsed files ``infos``: ``(part, offsets within part, status)``.  The streams
+    and palettes go up compressed in one block; the pages are laid out at multiples of PAGE_ALIGN from their IHDR."""
+    import time
+    t0 = time.perf_counter()
+    n = len(infos)
+    blobs, cols, z_at, out_at, filtered = [], [], 0, 0, 0
+    for info in infos:
+        z_off, pal_off, pal_n = z_at, -1, 0
+        blobs.append(info.idat)
+        z_at += len(info.idat)
+        if info.colour_type == 3:
+            pal_off, pal_n = z_at, len(info.palette) // 3
+            blobs.append(info.palette)
+            z_at += len(info.palette)
+        oc = info.out_channels(channels)
+        cols.append((z_off, len(info.idat), pal_off, out_at, info.width, info.height, info.colour_type, pal_n, oc, 0))
+        out_at += (info.width * info.height * oc + PAGE_ALIGN - 1) // PAGE_ALIGN * PAGE_ALIGN
+        filtered += info.filtered_bytes
+    desc = np.array(cols, dtype=_PNG_IMAGE)                          # struct i2l_png_image, field for field
+    z_host = torch.frombuffer(bytearray(b"".join(blobs)) or bytearray(1), dtype=torch.uint8)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        z = z_host.to(dev)
+        torch.cuda.current_stream(dev).synchronize()
+        t1 = time.perf_counter()
+        part = torch.empty((out_at,), dtype=torch.uint8, device=dev)
+        status = torch.empty((n,), dtype=torch.int32, device=dev)
+        ws = torch.empty((L.i2l_png_decode_workspace_bytes(n, filtered),), dtype=torch.uint8, device=dev)
+        _lib.check(L.i2l_png_decode(z.data_ptr(), z_at, desc.ctypes.data, n, part.data_ptr(), out_at, status.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "png_decode")
+        status_host = status.cpu().numpy()                           # waits for the launch
+    t2 = time.perf_counter()
+    seconds["upload"] += t1 - t0
+    seconds["launch"] += t2 - t1
+    return part, desc["out_off"].astype(np.int64), status_host
+
+
+def decode_pages_device(paths: Sequence[str], channels: int = 1, device=None, decode_threads: int = 8,
+                        chunk_bytes: int = 64 << 20, seconds: Optional[Dict[str, float]] = None):
+    """The pages of ``paths`` decoded ON THE DEVICE: ``(pixels, offsets, shapes, failed)`` with ``PageStore``'s meaning.
+    The files are read and parsed on ``decode_threads`` host threads (``png.parse_png``); the eligible ones go up
+    compressed and are inflated, unfiltered and converted by i2l_png_decode, one launch per about ``chunk_bytes`` of
+    pages.  Every other file -- and every file whose device status is not 0 -- takes ``decode_page`` and the pinned
+    upload, so ``failed`` is decided by ``decode_page`` alone and every page holds the bytes it returns.
+    ``seconds``: a dict that receives the time spent in "read_parse", "upload", "launch" and "fallback"."""
+    import time
+    dev = _cuda_device(device)
+    paths = list(paths)
+    n = len(paths)
+    shapes = np.ones((n, 3), dtype=np.int64)
+    offsets = np.zeros(n, dtype=np.int64)
+    failed = np.zeros(n, dtype=bool)
+    seconds = seconds if seconds is not None else {}
+    for key in ("read_parse", "upload", "launch", "fallback"):
+        seconds.setdefault(key, 0.0)
+    threads = max(1, int(decode_threads))
+    group = max(threads * 64, 1024)                                  # files read and parsed at a time
+    up = _PinnedUploader(dev, chunk_bytes)
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        for g0 in range(0, n, group):
+            t0 = time.perf_counter()
+            infos = list(pool.map(_read_png, paths[g0:g0 + group]))
+            seconds["read_parse"] += time.perf_counter() - t0
+            rows = [g0 + k for k, info in enumerate(infos) if info is not None]
+            fallback = [g0 + k for k, info in enumerate(infos) if info is None]
+            k0 = 0
+            while k0 < len(rows):                                    # launches of about chunk_bytes of pages
+                k1, size = k0, 0
+                while k1 < len(rows) and (k1 == k0 or size < chunk_bytes):
+                    info = infos[rows[k1] - g0]
+                    size += info.width * info.height * info.out_channels(channels)
+                    k1 += 1
+                chunk = [infos[r - g0] for r in rows[k0:k1]]
+                part, rel, status = _png_launch(chunk, channels, dev, seconds)
+                base = up.append(part)
+                for r, info, o, st in zip(rows[k0:k1], chunk, rel, status):
+                    if st:
+                        fallback.append(r)                           # its room in the part stays unused
+                    else:
+                        shapes[r] = (info.height, info.width, info.out_channels(channels))
+                        offsets[r] = base + int(o)
+                k0 = k1
+            if fallback:
+                fallback.sort()
+                t0 = time.perf_counter()
+                arrays = list(pool.map(lambda r: decode_page(paths[r], channels), fallback))
+                for r, arr in zip(fallback, arrays):
+                    if arr is None:
+                        failed[r] = True
+                        continue
+                    shapes[r] = arr.shape if arr.ndim == 3 else arr.shape + (1,)
+                    offsets[r] = up.add(arr)
+                up.flush()
+                seconds["fallback"] += time.perf_counter() - t0     # PIL and the pinned upload
+    return up.pixels(), offsets, shapes, failed
+
+
 class PageStore:
     """Decoded pages resident on the device: one uint8 buffer ``pixels``, page r the interleaved (h, w, c) image at
     ``offsets[r]`` (a multiple of 256), ``shapes[r] = (h, w, c)``; ``failed[r]`` marks a file that could not be read (it
-    takes no room).  Every path is decoded once, on ``decode_threads`` host threads, and uploaded in chunks of about
-    ``chunk_bytes`` through one pinned block, so the host never holds more than a chunk of decoded pages."""
+    takes no room).  ``decode="host"``: every path is decoded once, on ``decode_threads`` host threads, and uploaded in
+    chunks of about ``chunk_bytes`` through one pinned block, so the host never holds more than a chunk of decoded
+    pages.  ``decode="device"``: ``decode_pages_device`` -- the files go up compressed and i2l_png_decode writes the
+    pages; same ``shapes``, ``failed`` and page bytes, while the offsets may differ."""
 
     def __init__(self, paths: Sequence[str], channels: int = 1, device=None, decode_threads: int = 8,
-                 chunk_bytes: int = 64 << 20):
+                 chunk_bytes: int = 64 << 20, decode: str = "host"):
+        if decode not in ("host", "device"):
+            raise ValueError(f"PageStore: decode={decode!r}: expected \"host\" or \"device\"")
         self.device = dev = _cuda_device(device)
-        self.paths, self.channels = list(paths), channels
+        self.paths, self.channels, self.decode = list(paths), channels, decode
         n = len(self.paths)
+        self.decode_seconds = self.upload_seconds = 0.0
+        if decode == "device":
+            self.seconds: Dict[str, float] = {}
+            self.pixels, self.offsets, self.shapes, self.failed = decode_pages_device(
+                self.paths, channels, dev, decode_threads, chunk_bytes, self.seconds)
+            self.decode_seconds = self.seconds["read_parse"] + self.seconds["launch"] + self.seconds["fallback"]
+            self.upload_seconds = self.seconds["upload"]
+            return
         self.shapes = np.ones((n, 3), dtype=np.int64)
         self.offsets = np.zeros(n, dtype=np.int64)
         self.failed = np.zeros(n, dtype=bool)
-        self.decode_seconds = self.upload_seconds = 0.0
         import time
         threads = max(1, int(decode_threads))
         group = max(threads * 8, 64)                                 # files handed to the pool at a time
-        parts: List[torch.Tensor] = []                               # one device tensor per uploaded chunk
-        pinned, used, base, pending = None, 0, 0, []
-
-        def flush():
-            nonlocal used, base, pending
-            if used == 0:
-                return
-            t0 = time.perf_counter()
-            host = pinned.numpy()
-            for r, rel, arr in pending:
-                host[rel:rel + arr.size] = arr.reshape(-1)
-            with torch.cuda.device(dev):
-                part = torch.empty((used,), dtype=torch.uint8, device=dev)
-                part.copy_(pinned[:used], non_blocking=True)
-                torch.cuda.current_stream(dev).synchronize()         # the pinned block is filled again right away
-            parts.append(part)
-            base += used
-            used, pending = 0, []
-            self.upload_seconds += time.perf_counter() - t0
-
+        up = _PinnedUploader(dev, chunk_bytes)
         with ThreadPoolExecutor(max_workers=threads) as pool:
             for g0 in range(0, n, group):
                 t0 = time.perf_counter()
@@ -210,19 +369,10 @@ class PageStore:
                     if arr is None:
                         self.failed[r] = True
                         continue
-                    size = (arr.size + PAGE_ALIGN - 1) // PAGE_ALIGN * PAGE_ALIGN
-                    if used and used + size > chunk_bytes:
-                        flush()
-                    if pinned is None or pinned.numel() < max(chunk_bytes, size):
-                        pinned = torch.empty((max(chunk_bytes, size),), dtype=torch.uint8).pin_memory()
                     self.shapes[r] = arr.shape if arr.ndim == 3 else arr.shape + (1,)
-                    self.offsets[r] = base + used
-                    pending.append((r, used, arr))
-                    used += size
-            flush()
-        with torch.cuda.device(dev):
-            self.pixels = parts[0] if len(parts) == 1 else (torch.cat(parts) if parts else
-                                                             torch.zeros((PAGE_ALIGN,), dtype=torch.uint8, device=dev))
+                    self.offsets[r] = up.add(arr)
+        self.pixels = up.pixels()
+        self.upload_seconds = up.seconds
 
     def __len__(self) -> int:
         return len(self.paths)
@@ -232,12 +382,14 @@ class DeviceDataset:
     """One split, Im2LatexDataset's samples (dataset.py:94-343).  ``samples`` of the reference are ``image_names`` /
     ``formula_idxs`` here.  ``resident``: pages decoded and uploaded once (``PageStore``); otherwise decoded per batch.
     ``formula_store``: a ``FormulaStore`` of the same formulas file shared between splits (one corpus upload);
-    ``tables``: ``preprocess_batch``'s option (``"host"`` is the Pillow-exact arithmetic)."""
+    ``tables``: ``preprocess_batch``'s option (``"host"`` is the Pillow-exact arithmetic).  ``decode``: where the page
+    files are decoded, ``"host"`` (PIL) or ``"device"`` (``decode_pages_device``), for the resident store and for the
+    per-batch route alike."""
 
     def __init__(self, data_dir: str, split_file: str, formulas_file: str, tokenizer, img_dir: str = "img",
                  img_size: Tuple[int, int] = (64, 800), channels: int = 1, max_samples: Optional[int] = None,
                  resident: bool = True, device=None, formula_store: Optional[FormulaStore] = None, tables: str = "device",
-                 decode_threads: int = 8):
+                 decode_threads: int = 8, decode: str = "host"):
         self.data_dir = str(data_dir)
         self.img_base_dir = os.path.join(self.data_dir, img_dir or "img")
         split_path = os.path.join(self.data_dir, split_file)
@@ -250,6 +402,9 @@ class DeviceDataset:
             raise FileNotFoundError(f"Image directory not found: {self.img_base_dir}")
         self.tokenizer, self.img_size, self.channels = tokenizer, (int(img_size[0]), int(img_size[1])), int(channels)
         self.resident, self.device, self.tables, self.decode_threads = bool(resident), device, tables, int(decode_threads)
+        if decode not in ("host", "device"):
+            raise ValueError(f"DeviceDataset: decode={decode!r}: expected \"host\" or \"device\"")
+        self.decode = decode
         self.formulas = formula_store if formula_store is not None else FormulaStore(formulas_path, tokenizer, device)
         self.image_names, self.formula_idxs = read_split(split_path, len(self.formulas), max_samples)
         # a page that several samples name is stored once
@@ -267,7 +422,7 @@ class DeviceDataset:
         self.device = self.formulas.device
         if self.resident and self.pages is None:
             self.pages = PageStore([os.path.join(self.img_base_dir, p) for p in self.page_paths], self.channels, self.device,
-                                   self.decode_threads)
+                                   self.decode_threads, decode=self.decode)
         return self
 
     def batch(self, indices: Sequence[int], augment=None, first_position: int = 0, epoch: int = 0) -> Dict:
@@ -284,6 +439,11 @@ class DeviceDataset:
             if self.resident:
                 good = np.flatnonzero(~self.pages.failed[rows])
                 part = preprocess_resident(self.pages, rows[good], sample_ids=positions[good], **kw)
+            elif self.decode == "device":                             # the batch's files decoded on the device, then as resident
+                paths = [os.path.join(self.img_base_dir, self.page_paths[r]) for r in rows.tolist()]
+                pages = PageStore(paths, self.channels, self.device, self.decode_threads, decode="device")
+                good = np.flatnonzero(~pages.failed)
+                part = preprocess_resident(pages, good, sample_ids=positions[good], **kw)
             else:
                 paths = [os.path.join(self.img_base_dir, self.page_paths[r]) for r in rows.tolist()]
                 with ThreadPoolExecutor(max_workers=max(1, self.decode_threads)) as pool:
@@ -347,7 +507,8 @@ def loader_settings(config: Dict) -> Dict:
     """The keys and defaults ``create_data_loaders`` reads (dataset.py:415-557), as one dict: file names, ``img_dir``,
     ``img_size`` and ``channels`` by model type, ``batch_size``, ``eval_batch_size`` = min(batch_size *
     eval_batch_size_multiplier, max_eval_batch_size), ``resident`` (``load_in_memory``; true when absent -- the one
-    deliberate difference from the reference, whose default is false)."""
+    deliberate difference from the reference, whose default is false), ``decode`` (this package's key ``data.decode``:
+    "host" or "device", see ``PageStore``)."""
     data, model = config.get("data", {}) or {}, config.get("model", {}) or {}
     name = model.get("name", "cnn_lstm")
     enc = model.get("encoder", {})
@@ -368,21 +529,25 @@ def loader_settings(config: Dict) -> Dict:
             "channels": e.get("channels", default_channels),
             "batch_size": batch_size,
             "eval_batch_size": min(batch_size * data.get("eval_batch_size_multiplier", 2), data.get("max_eval_batch_size", 256)),
-            "resident": bool(data.get("load_in_memory", True))}
+            "resident": bool(data.get("load_in_memory", True)),
+            "decode": data.get("decode", "host")}
 
 
 def create_data_loaders(config: Dict, tokenizer, max_samples: Optional[Dict[str, Optional[int]]] = None, device=None,
-                        tables: str = "device", augment=None) -> Dict[str, DeviceLoader]:
+                        tables: str = "device", augment=None, decode: Optional[str] = None) -> Dict[str, DeviceLoader]:
     """dataset.py:367-557 on the device stores: ``{"train", "val", "test"}`` loaders (``{}`` when all splits are empty),
     ``train`` shuffled with ``drop_last``, the other two at the evaluation batch size.  The three splits share one
     ``FormulaStore``.  No train-time transform unless ``augment`` (an ``Augment``) is given: the reference applies its
-    transform to preloaded images only.  Nothing touches the device before the first batch."""
+    transform to preloaded images only.  ``decode``: "host" or "device" (``PageStore``); None reads the config key
+    ``data.decode`` (default "host").  Nothing touches the device before the first batch."""
     s = loader_settings(config)
+    decode = s["decode"] if decode is None else decode
     max_samples = max_samples or {}
     store = FormulaStore(os.path.join(str(s["data_dir"]), s["formulas_file"]), tokenizer, device) \
         if os.path.exists(os.path.join(str(s["data_dir"]), s["formulas_file"])) else None
     datasets = {split: DeviceDataset(s["data_dir"], s["split_files"][split], s["formulas_file"], tokenizer, s["img_dir"],
-                                     s["img_size"], s["channels"], max_samples.get(split), s["resident"], device, store, tables)
+                                     s["img_size"], s["channels"], max_samples.get(split), s["resident"], device, store, tables,
+                                     decode=decode)
                 for split in ("train", "val", "test")}
     if all(len(ds) == 0 for ds in datasets.values()):
         return {}

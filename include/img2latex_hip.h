@@ -608,6 +608,58 @@ int i2l_gather_ragged_u8(const uint8_t* src, int64_t src_bytes, const int64_t* s
                          int64_t max_size, uint8_t* dst, int64_t dst_bytes, const int64_t* dst_off, int32_t* status,
                          i2l_stream_t stream);
 
+/* PNG pages decoded on the device: inflate (RFC 1950 / 1951), unfilter (PNG 9.2, types 0 .. 4) and conversion to the page
+ * PIL hands the data set (data/dataset.py decode_page), n images in ONE launch, a wave per image.  The container is
+ * parsed on the host (data/png.py): `z` (DEVICE, z_bytes) holds the images' concatenated IDAT payloads -- their zlib
+ * streams, undecompressed -- and the PLTE bytes of palette images.  8-bit, non-interlaced images only.
+ * NOTE, unlike the other batch entry points (i2l_gather_ragged_u8 takes DEVICE lists): `images` is a HOST array of n
+ * descriptors.  The streams are untrusted, so every descriptor is checked against the buffers BEFORE anything is
+ * launched, and that needs them on the host; the call then copies them into the workspace itself.  The copy is from
+ * pageable memory and therefore SYNCHRONOUS: the call blocks the host until `stream` has reached and performed it
+ * (it waits on the stream before it launches), after which the caller's array may be freed or reused.  Not for use
+ * inside a stream capture.
+ *   colour_type 0 (gray):        channels must be 1, the page is (h, w, 1)
+ *   colour_type 2 (RGB):         channels must be 3, the page is (h, w, 3)
+ *   colour_type 4 (gray+alpha):  channels 1: gray; 3: gray three times; alpha dropped
+ *   colour_type 6 (RGBA):        channels 1: L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16 (Pillow); 3: RGB; alpha dropped
+ *   colour_type 3 (palette):     PLTE look-up (pal_n entries of 3 bytes at z + pal_off), then as RGBA without alpha
+ * The page of image i is written interleaved at pixels + out_off; the pages must not overlap.  status[i] (DEVICE, n
+ * int32) = 0 or an I2L_PNG_E_* code: the stream must have a valid zlib header (CM 8, window <= 32 K, no dictionary),
+ * consist of stored / fixed / dynamic blocks up to a final one, inflate to exactly height * (1 + width * bpp) bytes with
+ * every match inside the output so far, carry the right Adler-32 and end with it; every filter byte must be <= 4 and
+ * every palette index below pal_n.  An image with a non-zero status leaves an undefined page of ITS OWN; no byte outside
+ * the n pages is written, no byte outside an image's own stream (and palette) is read, whatever the streams hold.
+ * I2L_ERR_ARG before any launch: a descriptor that does not fit (unknown colour type, channels, a stream, palette or page
+ * outside its buffer, overlapping pages, width or height < 1), a missing pointer, a workspace not 16-byte aligned;
+ * I2L_ERR_UNSUPPORTED: an image of more than 2^27 filtered bytes, n > 2^20; I2L_ERR_WORKSPACE.  n == 0 is I2L_OK with
+ * no launch.  Otherwise two small synchronous copies (above) and ONE launch on `stream`; no state is kept.
+ * workspace: i2l_png_decode_workspace_bytes(n, the sum over the images of height * (1 + width * bpp)). */
+typedef struct i2l_png_image {
+    int64_t z_off, z_len;     /* the zlib stream within z */
+    int64_t pal_off;          /* PLTE bytes within z, -1: none */
+    int64_t out_off;          /* the page within pixels */
+    int32_t width, height, colour_type;
+    int32_t pal_n;            /* palette entries (colour type 3: 1 .. 256) */
+    int32_t channels;         /* of the page: 1 or 3 */
+    int32_t reserved;
+} i2l_png_image;
+#define I2L_PNG_E_HEADER 1
+#define I2L_PNG_E_TRUNCATED 2
+#define I2L_PNG_E_BLOCK_TYPE 3
+#define I2L_PNG_E_STORED_LEN 4
+#define I2L_PNG_E_CODE_LENGTHS 5
+#define I2L_PNG_E_SYMBOL 6
+#define I2L_PNG_E_DISTANCE 7
+#define I2L_PNG_E_TOO_MANY 8
+#define I2L_PNG_E_TOO_FEW 9
+#define I2L_PNG_E_TRAILING 10
+#define I2L_PNG_E_ADLER 11
+#define I2L_PNG_E_FILTER 12
+#define I2L_PNG_E_PALETTE 13
+size_t i2l_png_decode_workspace_bytes(int n, int64_t filtered_bytes_total);
+int i2l_png_decode(const uint8_t* z, int64_t z_bytes, const i2l_png_image* images, int n, uint8_t* pixels,
+                   int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, i2l_stream_t stream);
+
 /* Text -> the fitted vocabulary on the device: LaTeXTokenizer.fit (tokenizer.py:80-117).  text / row_off / rows and the
  * token rule are i2l_tokenize's (DEVICE arrays, str.split() per row; a row boundary separates tokens).  Every distinct
  * token is counted; the tokens are ordered by count descending, ties by first occurrence in the corpus (the smallest
