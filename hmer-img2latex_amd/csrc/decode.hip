@@ -241,6 +241,7 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned row
 #include "decode_group.inc.h"
 #include "decode_group16.inc.h"
 #include "beam_group.inc.h"
+#include "decode_batched.inc.h"
 
 // KR / KL > 0 (fast path for R == 1, L == 1, H <= 256: thread j owns hidden unit j for the whole loop):
 // rows [0,KR) of WhhT stay in the thread's registers and rows [KR,KR+KL) in LDS for all steps, so only
@@ -1038,6 +1039,87 @@ int launch_decode(const i2l_decoder_weights* w, const void* workspace, int rows,
     return I2L_OK;
 }
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// Step-batched greedy decode (decode_batched.inc.h): L + 2 plain launches per step on the caller's stream.
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t i2l_decode_batched_scratch_bytes(int rows, int vocab, int hidden, int layers) {
+    if (!batched_dims_ok(rows, vocab, hidden, layers)) return 0;
+    return batched_layout(rows, i2l_cdiv(vocab, VCHUNK) * VCHUNK, hidden, layers).total;
+}
+
+namespace {
+template <int TB>
+void launch_batched_lstm(const BatchedParams& p, int layer, int t, hipStream_t s) {
+    hipLaunchKernelGGL(lstm_step_mfma_kernel<TB>, dim3(p.w.H / 16, i2l_cdiv(p.B, TB)), dim3(DB_NT), 0, s, p, layer, t);
+}
+template <int TB>
+void launch_batched_logits(const BatchedParams& p, int t, hipStream_t s) {
+    hipLaunchKernelGGL(logits_mfma_kernel<TB>, dim3(p.w.Vp / DB_COLS, i2l_cdiv(p.B, TB)), dim3(DB_NT), 0, s, p, t);
+}
+}  // namespace
+
+extern "C" int i2l_greedy_decode_batched(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                         const int32_t* tok0, const int32_t* forced, const float* h0, const float* c0,
+                                         float temperature, int select, int stop, int end_id, int32_t* ids_out,
+                                         float* logits_out, float* h_out, float* c_out, void* scratch,
+                                         size_t scratch_bytes, int flags, uint32_t* resident_flag,
+                                         uint32_t resident_value, i2l_stream_t stream) {
+    (void)flags;
+    // every refusal is decided here, before the first HIP call
+    int rc = check_weights(w);
+    if (rc != I2L_OK) return rc;
+    if (select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
+    if (!workspace || !tok0 || rows <= 0 || steps <= 0) return I2L_ERR_ARG;
+    if ((h0 == nullptr) != (c0 == nullptr)) return I2L_ERR_ARG;
+    if (stop != I2L_STOP_NONE && stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
+    const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
+    const Layout lo = make_layout(rows, V, E, H, L);
+    const BatchedLayout bl = batched_layout(rows, lo.Vp, H, L);
+    if (!scratch || scratch_bytes < bl.total) return I2L_ERR_WORKSPACE;
+
+    char* sb = static_cast<char*>(scratch);
+    BatchedParams p{};
+    p.w = step_weights(lo, static_cast<const char*>(workspace), V, H, L);
+    p.B = rows; p.T = steps; p.forced = forced;
+    p.h = reinterpret_cast<float*>(sb + bl.h); p.c = reinterpret_cast<float*>(sb + bl.c);
+    p.lg = reinterpret_cast<float*>(sb + bl.lg);
+    p.tok = reinterpret_cast<int*>(sb + bl.tok); p.fin = reinterpret_cast<int*>(sb + bl.fin);
+    p.live = reinterpret_cast<unsigned*>(sb + bl.live);
+    p.ids = ids_out; p.logits_out = logits_out;
+    p.temperature = temperature; p.use_temp = (temperature != 1.0f) ? 1 : 0;
+    p.select = select; p.stop = stop; p.end_id = end_id;
+
+    hipStream_t s = i2l_s(stream);
+    if (resident_flag) {      // nothing here waits for a partner: "resident" is said at once
+        hipLaunchKernelGGL(publish_value32_kernel, dim3(1), dim3(1), 0, s, resident_flag, resident_value);
+        I2L_CHECK_LAUNCH();
+    }
+    const size_t most = (size_t)L * rows * H > (size_t)rows * steps ? (size_t)L * rows * H : (size_t)rows * steps;
+    const size_t copy_blocks = (most + DB_NT - 1) / DB_NT;
+    const int copy_grid = (int)(copy_blocks < 1024 ? copy_blocks : 1024);
+    hipLaunchKernelGGL(init_batched_kernel, dim3(copy_grid), dim3(DB_NT), 0, s, p, tok0, h0, c0);
+    I2L_CHECK_LAUNCH();
+    const int tb_lstm = batched_tile_rows(H / 16, rows), tb_logits = batched_tile_rows(lo.Vp / DB_COLS, rows);
+    const int sel_grid = i2l_cdiv(rows, DB_NT / 64);
+    for (int t = 0; t < steps; ++t) {
+        for (int l = 0; l < L; ++l) {
+            if (tb_lstm == 16) launch_batched_lstm<16>(p, l, t, s);
+            else if (tb_lstm == 32) launch_batched_lstm<32>(p, l, t, s);
+            else launch_batched_lstm<64>(p, l, t, s);
+        }
+        if (tb_logits == 16) launch_batched_logits<16>(p, t, s);
+        else if (tb_logits == 32) launch_batched_logits<32>(p, t, s);
+        else launch_batched_logits<64>(p, t, s);
+        hipLaunchKernelGGL(select_batched_kernel, dim3(sel_grid), dim3(DB_NT), 0, s, p, t);
+        I2L_CHECK_LAUNCH();
+    }
+    if (h_out || c_out) {
+        hipLaunchKernelGGL(state_out_batched_kernel, dim3(copy_grid), dim3(DB_NT), 0, s, p, h_out, c_out);
+        I2L_CHECK_LAUNCH();
+    }
+    return I2L_OK;
+}
 
 namespace {
 

@@ -1,0 +1,318 @@
+// Step-batched greedy decode on the MATRIX CORES for decoders the grouped kernels do not take (the shipped 2 x 512 one):
+// one decoder step of the whole batch is L + 2 short launches and the launch boundary is the only barrier (included by
+// decode.hip inside its anonymous namespace, after decode_group16.inc.h).  Reference decoder.py:247-250,277-280 (LSTM
+// gates, Linear(H -> V)), seq2seq.py:210-221 / predictor.py:283-347 (the arg max loop).
+//
+//   lstm_step_mfma_kernel<TB>   one launch per layer: gates[B x 4H] = (P[tok] + Genc | biasP) + x . WihT + h . WhhT and the
+//                               cell in the epilogue.  A workgroup owns TB batch rows x 64 gate columns (16 hidden units,
+//                               all four gates) and reads only its own 64-column slab of the weights.
+//   logits_mfma_kernel<TB>      logits[B x Vp] = h_top . WoutT + boutP into the scratch, same tiles.
+//   select_batched_kernel       one wave per row: the row kernel's selection rule, ids, next token, finished rows.
+//
+// Products are split-bf16 (bf16_split.inc.h): both operands are split into three bf16 pieces while they are staged into
+// LDS in the matrix cores' operand layout, six partial products v_mfma_f32_16x16x32_bf16, fp32 accumulation, the small
+// terms added first.  The gate columns lie along the MFMA's M and the batch rows along its N: D[m = 4 (l >> 4) + i][n =
+// l & 15] gives lane l the four gates (i) of one hidden unit for one row, so the cell needs no cross-lane traffic.
+//
+// h is double-buffered by step parity (other workgroups of the same launch still read the old h); c is updated in place
+// (each element is read and written by one thread).  Under I2L_STOP_STICKY the selection kernel counts the unfinished rows
+// in one device word; every kernel of a later step reads it first and returns when it is 0.  No polls, no cooperative
+// launch, no exchange: nothing here can time out.
+
+constexpr int DB_NT = 256;       // threads per workgroup: four waves, 16 of the 64 columns each
+constexpr int DB_COLS = 64;      // weight columns per workgroup
+constexpr int DB_KC = 64;        // K rows per staging round: two MFMA k-steps
+constexpr int DB_KG = DB_KC / 8; // 8-element k groups per round (one 16-byte operand fragment each)
+
+struct BatchedParams {
+    StepWeights w;
+    int B, T;
+    const int32_t* forced;
+    float* h;            // [2][L][B][H]
+    float* c;            // [L][B][H]
+    float* lg;           // [B][Vp] logits of the current step
+    int* tok;            // [B] token selected by the previous step
+    int* fin;            // [B] row has produced END
+    unsigned* live;      // rows not finished (only I2L_STOP_STICKY counts it down)
+    int32_t* ids;
+    float* logits_out;
+    float temperature;
+    int use_temp, select, stop, end_id;
+};
+
+// LDS of one staging round: weights [3 pieces][DB_KG][64 columns][8] bf16, activations [3][DB_KG][TB + 1 rows][8] bf16
+// (the odd row count spreads the 16-byte stores of a row's eight k groups over the banks)
+template <int TB>
+struct DbLds {
+    static constexpr int WS = 3 * DB_KG * DB_COLS;          // 16-byte fragments
+    static constexpr int XSTRIDE = TB + 1;
+    static constexpr int XS = 3 * DB_KG * XSTRIDE;
+    static constexpr int XRUNS = (TB * DB_KG + DB_NT - 1) / DB_NT;   // activation runs of 8 floats per thread and round
+};
+
+__device__ __forceinline__ void db_split8(const float (&v)[8], u32x4_t& q0, u32x4_t& q1, u32x4_t& q2) {
+    unsigned s0[4], s1[4], s2[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) split3_pair(v[2 * i], v[2 * i + 1], s0[i], s1[i], s2[i]);
+    q0 = u32x4_t{s0[0], s0[1], s0[2], s0[3]};
+    q1 = u32x4_t{s1[0], s1[1], s1[2], s1[3]};
+    q2 = u32x4_t{s2[0], s2[1], s2[2], s2[3]};
+}
+
+// acc[nt][piece class] += W[0..K)[col0 .. col0 + 63]^T . X[rows row0 .. row0 + TB)[0..K)^T for this workgroup's tile:
+// wave w takes columns col0 + 16 w .. + 15 and all TB / 16 row tiles.  W is [K][ldw] fp32, X is [B][ldx] fp32; rows past
+// B - 1 read row B - 1 (the caller drops them).  K % DB_KC == 0.  The next round's global loads are issued before this
+// round's MFMAs.  Contains __syncthreads(); ends with one, so ws / xs are free on return.
+template <int TB>
+__device__ __forceinline__ void db_slab(f32x4_t (&acc)[TB / 16][3], const float* __restrict__ W, size_t ldw, int col0,
+                                        const float* __restrict__ X, int ldx, int row0, int B, int K, u32x4_t* ws,
+                                        u32x4_t* xs, int tid) {
+    using S = DbLds<TB>;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wcol = tid & 63, wkg = tid >> 6;                    // weights: column wcol, k groups wkg and wkg + 4
+    float wv[2][8];
+    float xv[S::XRUNS][8];
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) wv[q][j] = W[(size_t)(k0 + 8 * (wkg + 4 * q) + j) * ldw + col0 + wcol];
+#pragma unroll
+        for (int q = 0; q < S::XRUNS; ++q) {
+            const int idx = tid + DB_NT * q;                      // run idx: row idx >> 3, k group idx & 7
+            if (idx < TB * DB_KG) {
+                const int row = min(row0 + (idx >> 3), B - 1);
+                const float4* src = reinterpret_cast<const float4*>(X + (size_t)row * ldx + k0 + 8 * (idx & 7));
+                const float4 a = src[0], b = src[1];
+                xv[q][0] = a.x; xv[q][1] = a.y; xv[q][2] = a.z; xv[q][3] = a.w;
+                xv[q][4] = b.x; xv[q][5] = b.y; xv[q][6] = b.z; xv[q][7] = b.w;
+            }
+        }
+    };
+    load(0);
+    for (int k0 = 0; k0 < K; k0 += DB_KC) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            u32x4_t q0, q1, q2;
+            db_split8(wv[q], q0, q1, q2);
+            const int at = (wkg + 4 * q) * DB_COLS + wcol;
+            ws[at] = q0; ws[DB_KG * DB_COLS + at] = q1; ws[2 * DB_KG * DB_COLS + at] = q2;
+        }
+#pragma unroll
+        for (int q = 0; q < S::XRUNS; ++q) {
+            const int idx = tid + DB_NT * q;
+            if (idx < TB * DB_KG) {
+                u32x4_t q0, q1, q2;
+                db_split8(xv[q], q0, q1, q2);
+                const int at = (idx & 7) * S::XSTRIDE + (idx >> 3);
+                xs[at] = q0; xs[DB_KG * S::XSTRIDE + at] = q1; xs[2 * DB_KG * S::XSTRIDE + at] = q2;
+            }
+        }
+        __syncthreads();
+        if (k0 + DB_KC < K) load(k0 + DB_KC);
+#pragma unroll
+        for (int ks = 0; ks < DB_KC / 32; ++ks) {
+            // A (weights): lane l holds A[m = l & 15][k = 8 (l >> 4) + j]; B (activations): B[k = 8 (l >> 4) + j][n = l & 15]
+            const int kg = 4 * ks + (lane >> 4);
+            Frag16 a[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a[c].q = ws[(c * DB_KG + kg) * DB_COLS + 16 * wave + (lane & 15)];
+#pragma unroll
+            for (int nt = 0; nt < TB / 16; ++nt) {
+                Frag16 b[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) b[c].q = xs[(c * DB_KG + kg) * S::XSTRIDE + 16 * nt + (lane & 15)];
+                acc[nt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0].v, b[0].v, acc[nt][0], 0, 0, 0);
+                acc[nt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0].v, b[1].v, acc[nt][1], 0, 0, 0);
+                acc[nt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1].v, b[0].v, acc[nt][1], 0, 0, 0);
+                acc[nt][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0].v, b[2].v, acc[nt][2], 0, 0, 0);
+                acc[nt][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1].v, b[1].v, acc[nt][2], 0, 0, 0);
+                acc[nt][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2].v, b[0].v, acc[nt][2], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Layer `layer` of step t for the whole batch.  grid (H / 16, cdiv(B, TB)).
+template <int TB>
+__global__ __launch_bounds__(DB_NT) void lstm_step_mfma_kernel(BatchedParams p, int layer, int t) {
+    __shared__ u32x4_t ws[DbLds<TB>::WS];
+    __shared__ u32x4_t xs[DbLds<TB>::XS];
+    if (*p.live == 0) return;
+    const StepWeights& w = p.w;
+    const int H = w.H, L = w.L, B = p.B, par = t & 1;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int col0 = blockIdx.x * DB_COLS, row0 = blockIdx.y * TB;
+    const size_t G = 4 * (size_t)H, LBH = (size_t)L * B * H;
+    f32x4_t acc[TB / 16][3];
+#pragma unroll
+    for (int nt = 0; nt < TB / 16; ++nt)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[nt][c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    const float* h_old = p.h + (size_t)par * LBH + (size_t)layer * B * H;
+    float* h_new = p.h + (size_t)(par ^ 1) * LBH + (size_t)layer * B * H;
+    if (layer > 0)      // the layer below, already at step t
+        db_slab<TB>(acc, w.WihT[layer], G, col0, p.h + (size_t)(par ^ 1) * LBH + (size_t)(layer - 1) * B * H, H, row0, B, H,
+                    ws, xs, tid);
+    db_slab<TB>(acc, w.WhhT[layer], G, col0, h_old, H, row0, B, H, ws, xs, tid);
+
+    const int unit = (col0 >> 2) + 4 * wave + (lane >> 4);       // this lane's D rows are the gates i, f, g, o of `unit`
+    float* c_l = p.c + (size_t)layer * B * H;
+#pragma unroll
+    for (int nt = 0; nt < TB / 16; ++nt) {
+        const int row = row0 + 16 * nt + (lane & 15);
+        if (row >= B) continue;
+        float4 add;
+        if (layer == 0) {
+            int tk = p.forced ? p.forced[(size_t)row * p.T + t] : p.tok[row];
+            tk = min(max(tk, 0), w.V - 1);
+            const float4 a = *reinterpret_cast<const float4*>(w.P + (size_t)tk * G + 4 * unit);
+            const float4 e = *reinterpret_cast<const float4*>(w.Genc + (size_t)row * G + 4 * unit);
+            add = make_float4(a.x + e.x, a.y + e.y, a.z + e.z, a.w + e.w);
+        } else {
+            add = *reinterpret_cast<const float4*>(w.biasP[layer] + 4 * unit);
+        }
+        const f32x4_t z = (acc[nt][2] + acc[nt][1]) + acc[nt][0];   // small terms first
+        const float ig = sigmoidf_(z[0] + add.x), fg = sigmoidf_(z[1] + add.y);
+        const float gg = tanhf_(z[2] + add.z), og = sigmoidf_(z[3] + add.w);
+        const size_t ci = (size_t)row * H + unit;
+        const float cn = fg * c_l[ci] + ig * gg;
+        c_l[ci] = cn;
+        h_new[ci] = og * tanhf_(cn);
+    }
+}
+
+// logits of step t (after its LSTM launches): lg[b][v] = boutP[v] + sum_k h_top[b][k] WoutT[k][v].  grid (Vp / 64, cdiv(B, TB)).
+template <int TB>
+__global__ __launch_bounds__(DB_NT) void logits_mfma_kernel(BatchedParams p, int t) {
+    __shared__ u32x4_t ws[DbLds<TB>::WS];
+    __shared__ u32x4_t xs[DbLds<TB>::XS];
+    if (*p.live == 0) return;
+    const StepWeights& w = p.w;
+    const int H = w.H, L = w.L, B = p.B, par = t & 1;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int col0 = blockIdx.x * DB_COLS, row0 = blockIdx.y * TB;
+    f32x4_t acc[TB / 16][3];
+#pragma unroll
+    for (int nt = 0; nt < TB / 16; ++nt)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[nt][c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    const float* h_top = p.h + ((size_t)(par ^ 1) * L + (L - 1)) * B * H;
+    db_slab<TB>(acc, w.WoutT, (size_t)w.Vp, col0, h_top, H, row0, B, H, ws, xs, tid);
+    const int col = col0 + 16 * wave + 4 * (lane >> 4);
+    const float4 bb = *reinterpret_cast<const float4*>(w.boutP + col);   // -inf in the padding columns
+#pragma unroll
+    for (int nt = 0; nt < TB / 16; ++nt) {
+        const int row = row0 + 16 * nt + (lane & 15);
+        if (row >= B) continue;
+        const f32x4_t z = (acc[nt][2] + acc[nt][1]) + acc[nt][0];
+        *reinterpret_cast<float4*>(p.lg + (size_t)row * w.Vp + col) = make_float4(z[0] + bb.x, z[1] + bb.y, z[2] + bb.z, z[3] + bb.w);
+    }
+}
+
+// Token selection of step t, one wave per row.  The rule is decode_kernel's ("output projection + token selection" in
+// decode.hip, the first copy): raw logits out, division by the temperature when it is not 1, first-index arg max, and for
+// I2L_SELECT_SOFTMAX the probabilities evaluated literally (exp(x - max) / sum in fp32, first index wins).
+__global__ __launch_bounds__(DB_NT) void select_batched_kernel(BatchedParams p, int t) {
+    if (*p.live == 0) return;
+    const StepWeights& w = p.w;
+    const int V = w.V, lane = threadIdx.x & 63;
+    const int row = blockIdx.x * (DB_NT / 64) + (threadIdx.x >> 6);
+    if (row >= p.B) return;
+    const float* x = p.lg + (size_t)row * w.Vp;
+    float* lo = p.logits_out ? p.logits_out + ((size_t)row * p.T + t) * V : nullptr;
+    float best = -INFINITY;
+    int besti = 0x7fffffff;
+    for (int v = lane; v < w.Vp; v += 64) {
+        float a = x[v];
+        if (lo && v < V) lo[v] = a;
+        if (p.use_temp) a = a / p.temperature;
+        if (a > best) { best = a; besti = v; }
+    }
+    wave_argmax(best, besti);
+    if (p.select == I2L_SELECT_SOFTMAX) {
+        float s = 0.f;
+        for (int v = lane; v < V; v += 64) {
+            const float a = p.use_temp ? x[v] / p.temperature : x[v];
+            s += expf(a - best);
+        }
+        s = wave_sum(s);
+        float pbest = -1.f;
+        int pbesti = 0x7fffffff;
+        for (int v = lane; v < V; v += 64) {
+            const float a = p.use_temp ? x[v] / p.temperature : x[v];
+            const float pr = expf(a - best) / s;
+            if (pr > pbest) { pbest = pr; pbesti = v; }
+        }
+        wave_argmax(pbest, pbesti);
+        besti = pbesti;
+    }
+    if (lane == 0) {
+        const int sel = besti < V ? besti : 0;
+        const int was_fin = p.fin[row];
+        if (p.ids) p.ids[(size_t)row * p.T + t] = (p.stop == I2L_STOP_STICKY && was_fin) ? -1 : sel;
+        p.tok[row] = sel;
+        if (sel == p.end_id && !was_fin) {
+            p.fin[row] = 1;
+            if (p.stop == I2L_STOP_STICKY) atomicSub(p.live, 1u);
+        }
+    }
+}
+
+// state in, tokens, finished marks, the live-row count and ids = -1 (steps an early end never runs)
+__global__ __launch_bounds__(DB_NT) void init_batched_kernel(BatchedParams p, const int32_t* __restrict__ tok0,
+                                                             const float* __restrict__ h0, const float* __restrict__ c0) {
+    const size_t LBH = (size_t)p.w.L * p.B * p.w.H, BT = (size_t)p.B * p.T;
+    const size_t i0 = (size_t)blockIdx.x * DB_NT + threadIdx.x, stride = (size_t)gridDim.x * DB_NT;
+    for (size_t i = i0; i < LBH; i += stride) {
+        p.h[i] = h0 ? h0[i] : 0.f;
+        p.c[i] = c0 ? c0[i] : 0.f;
+    }
+    if (p.ids)
+        for (size_t i = i0; i < BT; i += stride) p.ids[i] = -1;
+    for (size_t i = i0; i < (size_t)p.B; i += stride) { p.tok[i] = tok0[i]; p.fin[i] = 0; }
+    if (i0 == 0) *p.live = (unsigned)p.B;
+}
+
+// state after the last step (parity T & 1)
+__global__ __launch_bounds__(DB_NT) void state_out_batched_kernel(BatchedParams p, float* __restrict__ h_out,
+                                                                  float* __restrict__ c_out) {
+    const size_t LBH = (size_t)p.w.L * p.B * p.w.H;
+    const float* h = p.h + (size_t)(p.T & 1) * LBH;
+    for (size_t i = (size_t)blockIdx.x * DB_NT + threadIdx.x; i < LBH; i += (size_t)gridDim.x * DB_NT) {
+        if (h_out) h_out[i] = h[i];
+        if (c_out) c_out[i] = p.c[i];
+    }
+}
+
+struct BatchedLayout {
+    size_t h, c, lg, tok, fin, live, total;
+};
+
+BatchedLayout batched_layout(int rows, int Vp, int H, int L) {
+    BatchedLayout o{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t r = off; off += i2l_align(bytes); return r; };
+    const size_t LBH = (size_t)L * rows * H;
+    o.h = take(2 * LBH * sizeof(float));
+    o.c = take(LBH * sizeof(float));
+    o.lg = take((size_t)rows * Vp * sizeof(float));
+    o.tok = take((size_t)rows * sizeof(int));
+    o.fin = take((size_t)rows * sizeof(int));
+    o.live = take(sizeof(unsigned));
+    o.total = off;
+    return o;
+}
+
+inline bool batched_dims_ok(int rows, int V, int H, int L) {
+    return rows > 0 && V > 0 && H > 0 && H % 64 == 0 && H <= 2048 && L > 0 && L <= MAXL;
+}
+
+// rows per tile: the smallest of 16 / 32 / 64 that keeps the grid within the 256 compute units (B = 256, H = 512: TB = 32,
+// 32 x 8 workgroups); larger batches take 64
+inline int batched_tile_rows(int col_tiles, int rows) {
+    for (int tb = 16; tb < 64; tb *= 2)
+        if ((long)col_tiles * i2l_cdiv(rows, tb) <= 256) return tb;
+    return 64;
+}

@@ -66,11 +66,22 @@ def _device(name: Optional[str]) -> torch.device:
     return torch.device(name or "cuda")
 
 
+def _decode_flags(decode_kernel: str) -> int:
+    """--decode-kernel: "auto" = the library's own choice (grouped kernels where the dimensions have them, else a row per
+    workgroup); "batched" = the step-batched matrix-core decode (_lib.FLAG_DECODE_BATCHED), built for decoders the grouped
+    kernels do not take, such as the shipped two-layer, 512-wide one."""
+    from . import _lib
+    if decode_kernel not in ("auto", "batched"):
+        raise SystemExit(f"img2latex_amd: --decode-kernel {decode_kernel}: expected auto or batched")
+    return _lib.FLAG_DECODE_BATCHED if decode_kernel == "batched" else 0
+
+
 def predict(checkpoint_path: str, image_path: str, beam_size: int = 0, max_length: int = 141, temperature: float = 1.0,
-            top_k: int = 0, top_p: float = 0.0, device: Optional[str] = None) -> str:
-    """cli.py:253-308: returns the LaTeX string the command prints."""
+            top_k: int = 0, top_p: float = 0.0, device: Optional[str] = None, decode_kernel: str = "auto") -> str:
+    """cli.py:253-308: returns the LaTeX string the command prints.  ``decode_kernel``: see ``_decode_flags``."""
     from .training import Predictor
-    predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device))
+    predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device),
+                                          decode_flags=_decode_flags(decode_kernel))
     return predictor.predict(image=image_path, beam_size=beam_size, max_length=max_length, temperature=temperature,
                              top_k=top_k, top_p=top_p)
 
@@ -266,7 +277,7 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
 
 def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_size: int = 32,
              num_samples: Optional[int] = None, beam_size: int = 0, device: Optional[str] = None,
-             output_dir: str = "outputs", decode: Optional[str] = None) -> Dict:
+             output_dir: str = "outputs", decode: Optional[str] = None, decode_kernel: str = "auto") -> Dict:
     """cli.py:315-518 on the device: returns {"bleu", "levenshtein", "batch_size"} over the whole split -- the means over
     all pairs, as ``calculate_metrics`` on the reference's two lists computes them -- after printing the three result
     lines and writing ``predictions.json``.
@@ -287,7 +298,8 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
     dev = _device(device)
     experiment_name = Path(checkpoint_path).parent.parent.name              # cli.py:340-349: outputs/<experiment>/checkpoints/<file>
     config = torch.load(checkpoint_path, map_location="cpu", weights_only=False).get("config", {}) or {}
-    predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=dev)
+    predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=dev,
+                                          decode_flags=_decode_flags(decode_kernel))
     max_samples = {"train": None, "val": None, "test": None}
     if num_samples:
         max_samples[split] = num_samples
@@ -364,6 +376,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     p.add_argument("--top-k", type=int, default=0, help="Top-k sampling parameter")
     p.add_argument("--top-p", type=float, default=0.0, help="Top-p (nucleus) sampling parameter")
     p.add_argument("--device", default=None, help="Device to use for inference (cuda)")
+    p.add_argument("--decode-kernel", choices=("auto", "batched"), default="auto",
+                   help="(this package) greedy decode kernel: auto, or the step-batched matrix-core decode")
     t = sub.add_parser("train", help="Train the image-to-LaTeX model.")
     t.add_argument("--config-path", default="img2latex/configs/config.yaml", help="Path to configuration file")
     t.add_argument("--experiment-name", default="img2latex_v1", help="Name of the experiment")
@@ -396,6 +410,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     e.add_argument("--beam-size", type=int, default=0, help="Beam size for beam search (0 for greedy search)")
     e.add_argument("--device", default=None, help="Device to use for evaluation (cuda)")
     e.add_argument("--output-dir", default="outputs", help="(this package) root of <experiment>/predictions")
+    e.add_argument("--decode-kernel", choices=("auto", "batched"), default="auto",
+                   help="(this package) greedy decode kernel: auto, or the step-batched matrix-core decode")
     e.add_argument("--decode", choices=("host", "device"), default=None,
                    help="(this package) decode the page files with PIL on the host or with the PNG kernel on the device")
     v = sub.add_parser("vocab", help="(this package) Fit the vocabulary of a formulas file on the device and save it.")
@@ -406,7 +422,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     args = ap.parse_args(argv)
     if args.command == "predict":
         latex = predict(args.checkpoint_path, args.image_path, args.beam_size, args.max_length, args.temperature,
-                        args.top_k, args.top_p, args.device)
+                        args.top_k, args.top_p, args.device, args.decode_kernel)
         print("Generated LaTeX:")
         print(latex)
         return 0
@@ -415,7 +431,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     if args.command == "evaluate":
         evaluate(args.checkpoint_path, args.data_dir, args.split, args.batch_size, args.num_samples, args.beam_size,
-                 args.device, args.output_dir, args.decode)
+                 args.device, args.output_dir, args.decode, args.decode_kernel)
         return 0
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,

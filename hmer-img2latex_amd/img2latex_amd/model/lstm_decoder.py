@@ -83,7 +83,8 @@ class LSTMDecoder(nn.Module):
         self._ws: Optional[torch.Tensor] = None      # workspace of the CURRENT stream (see _select_workspace)
         self._ws_key = None          # (rows, weight versions) the weight images in _ws were built for
         self._ws_by_stream = {}      # stream handle -> (workspace, key): concurrent decodes must not share one
-        self.kernel_flags = 0        # _lib.FLAG_NO_GROUP / FLAG_EXACT_FP32 (training), FLAG_AGENT_SCOPE_EXCHANGE (all grouped)
+        self.kernel_flags = 0        # _lib.FLAG_NO_GROUP / FLAG_EXACT_FP32 (training), FLAG_AGENT_SCOPE_EXCHANGE (all grouped),
+                                     # FLAG_DECODE_BATCHED (every greedy path through run_steps)
 
     # ------------------------------------------------------------------ plumbing
     def _weights_struct(self):
@@ -200,6 +201,23 @@ class LSTMDecoder(nn.Module):
         if want_state:
             h = torch.empty((self.lstm_layers, rows, self.hidden_dim), dtype=torch.float32, device=dev)
             c = torch.empty_like(h)
+        all_flags = int(flags) | int(self.kernel_flags)
+        res_ptr = None if resident is None else resident[0].data_ptr()
+        res_val = 0 if resident is None else int(resident[1]) & 0xFFFFFFFF
+        if all_flags & _lib.FLAG_DECODE_BATCHED:
+            # step-batched matrix-core path (decode_batched.inc.h): its scratch lives for this call only, on this stream
+            nbytes = _lib.lib().i2l_decode_batched_scratch_bytes(rows, self.vocab_size, self.hidden_dim, self.lstm_layers)
+            if nbytes == 0:
+                raise RuntimeError("img2latex_amd: decoder dimensions not supported by the step-batched decode")
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(_lib.lib().i2l_greedy_decode_batched(
+                ctypes.byref(w), ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(forced), _lib.ptr(h0),
+                _lib.ptr(c0), float(temperature), select, stop, int(end_id), _lib.ptr(ids), _lib.ptr(logits),
+                _lib.ptr(h), _lib.ptr(c), scratch.data_ptr(), nbytes, all_flags, res_ptr, res_val, _lib.stream_ptr()),
+                "greedy_decode_batched")
+            _lib.mark("decode")
+            del keep, scratch      # the caching allocator hands the block out again only in stream order
+            return ids, logits, ((h, c) if want_state else None)
         _lib.check(_lib.lib().i2l_greedy_decode_ex(
             ctypes.byref(w), ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(forced), _lib.ptr(h0),
             _lib.ptr(c0), float(temperature), select, stop, int(end_id), int(rows_per_workgroup), _lib.ptr(ids),

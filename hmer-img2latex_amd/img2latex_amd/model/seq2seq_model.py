@@ -92,20 +92,20 @@ class Seq2SeqModel(nn.Module):
         return ids, logits
 
     def greedy_ids_host(self, encoder_output: torch.Tensor, start_token_id: int, end_token_id: int, max_length: int,
-                        temperature: float = 1.0, stop: int = _lib.STOP_NONE, select: int = _lib.SELECT_LOGITS
-                        ) -> torch.Tensor:
+                        temperature: float = 1.0, stop: int = _lib.STOP_NONE, select: int = _lib.SELECT_LOGITS,
+                        flags: int = 0) -> torch.Tensor:
         """greedy_ids + the ONE device->host copy of the search, with the timeout fallback both callers
         (_greedy_search and Predictor.predict_batch_ids) share: the grouped kernel needs its 4 members resident
         together; on a GPU shared with other work (fewer than 32 free CUs) a bounded wait can expire (ids -3) ->
         run the row-per-workgroup HIP kernel, which needs no partner."""
         ids, _ = self.greedy_ids(encoder_output, start_token_id, end_token_id, max_length, temperature, stop=stop,
-                                 select=select)
+                                 select=select, flags=flags)
         ids = ids.cpu()
         if _lib.ids_timed_out(ids):
             warnings.warn("img2latex_amd: grouped decode timed out (GPU oversubscribed?); "
                           "re-running on the row-per-workgroup kernel", RuntimeWarning)
             ids, _ = self.greedy_ids(encoder_output, start_token_id, end_token_id, max_length, temperature, stop=stop,
-                                     select=select, rows_per_workgroup=1)
+                                     select=select, rows_per_workgroup=1, flags=flags)
             ids = _lib.check_ids(ids.cpu())
         return ids
 

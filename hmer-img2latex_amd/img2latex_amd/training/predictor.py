@@ -241,7 +241,10 @@ def _is_pil(obj) -> bool:
 
 class Predictor:
     def __init__(self, model: Seq2SeqModel, tokenizer, device: Optional[torch.device] = None,
-                 model_type: str = "cnn_lstm"):
+                 model_type: str = "cnn_lstm", decode_flags: int = 0):
+        # decode_flags (_lib.FLAG_DECODE_BATCHED: the step-batched matrix-core decode) are OR-ed into the flags of every
+        # greedy decode this predictor launches; 0 = the automatic kernel choice
+        self.decode_flags = int(decode_flags)
         self.device = torch.device("cuda") if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("img2latex_amd: Predictor runs on a ROCm device only (no CPU fallback)")
@@ -251,7 +254,8 @@ class Predictor:
         self.model.eval()                                                   # predictor.py:55
 
     @classmethod
-    def from_checkpoint(cls, checkpoint_path: str, device: Optional[torch.device] = None) -> "Predictor":
+    def from_checkpoint(cls, checkpoint_path: str, device: Optional[torch.device] = None,
+                        decode_flags: int = 0) -> "Predictor":
         checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
         config = checkpoint.get("config", {})
         tcfg = checkpoint.get("tokenizer_config", {})
@@ -259,7 +263,7 @@ class Predictor:
         model = model_from_checkpoint_config(config, tokenizer.vocab_size)
         model.load_state_dict(checkpoint["model_state_dict"])               # predictor.py:129, strict
         return cls(model=model, tokenizer=tokenizer, device=device,
-                   model_type=config.get("model", {}).get("name", "cnn_lstm"))
+                   model_type=config.get("model", {}).get("name", "cnn_lstm"), decode_flags=decode_flags)
 
     # ------------------------------------------------------------------ predictor.py:396-521
     def _prepare_image(self, image) -> torch.Tensor:
@@ -343,7 +347,7 @@ class Predictor:
                 ids = _lib.check_ids(self._sample_ids(enc, max_length, temperature, top_k, top_p, seed).cpu())
             else:       # same timeout fallback as Seq2SeqModel._greedy_search
                 ids = self.model.greedy_ids_host(enc, start, end, max_length, temperature, stop=_lib.STOP_STICKY,
-                                                 select=_lib.SELECT_SOFTMAX)
+                                                 select=_lib.SELECT_SOFTMAX, flags=self.decode_flags)
         a = ids.numpy()
         stop = (a == end) | (a < 0)                           # first END, or the kernel's "row finished" filler
         lens = np.where(stop.any(axis=1), stop.argmax(axis=1), a.shape[1]).tolist()
@@ -363,6 +367,7 @@ class Predictor:
         of every row comes back with the row offsets."""
         import warnings
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
+        loop = dict(loop, flags=int(loop.get("flags", 0)) | self.decode_flags)
         ids, _ = self.model.greedy_ids(enc, start, end, max_length, temperature, **loop)
         texts, first = table.decode_now(ids, end)
         if _lib.ids_timed_out(first):
@@ -413,7 +418,7 @@ class Predictor:
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
         n_enc = 2 if hasattr(self.model.encoder, "_trunk_train") else 1      # ResNet trunk: two in flight
         pipe = GreedyPipeline(self.model, start, end, max_length, temperature, rows_per_workgroup=0,
-                              decode_flags=_lib.FLAG_DECODE_GROUP16, decode_priority=-1, encoder_streams=n_enc,
+                              decode_flags=_lib.FLAG_DECODE_GROUP16 | self.decode_flags, decode_priority=-1, encoder_streams=n_enc,
                               stop=_lib.STOP_STICKY, select=_lib.SELECT_SOFTMAX, detokenize=table)
 
         def finish(ids_host):
@@ -586,7 +591,8 @@ class Predictor:
             with torch.no_grad():
                 ids, _ = self.model.greedy_ids(enc, tk.start_token_id, tk.end_token_id, T, stop=_lib.STOP_STICKY,
                                                select=_lib.SELECT_SOFTMAX, rows_per_workgroup=rows_per_workgroup,
-                                               flags=_lib.FLAG_DECODE_GROUP16 if coresident else 0, prepared=prepared,
+                                               flags=(_lib.FLAG_DECODE_GROUP16 if coresident else 0) | self.decode_flags,
+                                               prepared=prepared,
                                                resident=(st["resident"], st["n"]) if coresident else None)
             if coresident:
                 decoded = torch.cuda.Event()

@@ -69,6 +69,8 @@ typedef void* i2l_stream_t;
                                           with EIGHT members x EIGHT rows per group -- one wave per SIMD and ~80 KB of LDS
                                           per CU instead of two waves and 140 KB, so that a conv workgroup of the NEXT
                                           batch's encoder fits beside it; same ids                                   */
+#define I2L_FLAG_DECODE_BATCHED 0x2000  /* the Python layer's switch for i2l_greedy_decode_batched (LSTMDecoder.run_steps takes that entry
+                                          instead of i2l_greedy_decode_ex); the C entries ignore it */
 #define I2L_FLAG_DECODE_GROUP16 0x8000 /* i2l_greedy_decode_ex (ids only): the grouped kernel with SIXTEEN members x SIXTEEN rows per
                                           group and the per-step products (LSTM gates, logits) on the matrix cores as split-bf16
                                           v_mfma_f32_16x16x32_bf16 bursts (fp32-grade: 3 bf16 pieces per operand, 6 partial
@@ -369,6 +371,29 @@ int i2l_greedy_decode_ex(const i2l_decoder_weights* w, const void* workspace, in
                          float temperature, int select, int stop, int end_id, int rows_per_workgroup,
                          int32_t* ids_out, float* logits_out, float* h_out, float* c_out, int flags,
                          uint32_t* resident_flag, uint32_t resident_value, i2l_stream_t stream);
+
+/* The same loop (seq2seq.py:210-221, predictor.py:283-347; steps == 1: LSTMDecoder.decode_step, decoder.py:197-284) for
+ * decoders the grouped kernels do not take -- the shipped hidden 512 / 2 layers (configs/config.yaml:38-50) first of all --
+ * STEP-BATCHED on the matrix cores: per step one split-bf16 GEMM + LSTM cell launch per layer (decoder.py:247, 277), one
+ * for the logits (decoder.py:250, 280) and one for the selection, all rows of the batch together, so a weight slab is read
+ * once per row tile instead of once per row.  The launch boundary is the only barrier: nothing polls, nothing can time
+ * out (no -3 ids).  Arguments as i2l_greedy_decode_ex (select: I2L_SELECT_LOGITS / _SOFTMAX, else I2L_ERR_ARG); results
+ * agree with it to fp32 rounding (split-bf16 products: the error class of an fp32 fmaf chain), not bit for bit.
+ *   scratch     i2l_decode_batched_scratch_bytes(rows, vocab, hidden, layers) bytes of device memory, written by the call:
+ *               h (2, L, rows, H), c (L, rows, H), one row of logits per batch row, token / finished / live-row words.
+ *               The size query returns 0 for dimensions the kernels refuse (rows <= 0, hidden % 64 != 0 or > 2048,
+ *               layers > I2L_MAX_LSTM_LAYERS); the call returns I2L_ERR_WORKSPACE when scratch_bytes is smaller.
+ *   stop        I2L_STOP_STICKY: ids are -1 after a row's first END; once every row has ended the remaining launches
+ *               return at once (they are still enqueued: no host read happens inside the call).  h_out / c_out of rows
+ *               that ended are unspecified.
+ *   resident_flag  published at once.  flags: none used.
+ * Every refusal is decided on the host before the first HIP call. */
+size_t i2l_decode_batched_scratch_bytes(int rows, int vocab, int hidden, int layers);
+int i2l_greedy_decode_batched(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                              const int32_t* tok0, const int32_t* forced, const float* h0, const float* c0,
+                              float temperature, int select, int stop, int end_id, int32_t* ids_out,
+                              float* logits_out, float* h_out, float* c_out, void* scratch, size_t scratch_bytes,
+                              int flags, uint32_t* resident_flag, uint32_t resident_value, i2l_stream_t stream);
 
 /* The sampling branch of Predictor.predict_batch (predictor.py:295-331, taken when temperature > 0 and
  * (top_k > 0 or top_p > 0)): probs = softmax(logits/T); top-k keeps p >= k-th largest; top-p drops a
