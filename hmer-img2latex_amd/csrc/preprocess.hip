@@ -191,7 +191,11 @@ __global__ __launch_bounds__(256) void resize_v_norm_kernel(const uint8_t* __res
 }
 
 // torch.nn.functional.interpolate(mode="bilinear", align_corners=False) of fp32 planes (predictor.py:483-491):
-// source index = max(0, (dst + 0.5) * in / out - 0.5), the neighbour clamped to the last sample
+// source index = max(0, (dst + 0.5) * in / out - 0.5), the neighbour clamped to the last sample.  The product and the
+// subtraction are ONE fused multiply-add, as ATen's kernels are compiled (its vectorised CPU build and its GPU build both
+// contract them); rounding the product first would move the index by an ulp at some columns, 1e-5 of the pixel range at
+// index ~128 -- (37, 211) -> (64, 800) has six such columns.  Written as fmaf and not left to the compiler: HIP's
+// __fmul_rn / __fsub_rn are plain * and -, which hipcc contracts or not as it sees fit.
 __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, long planes,
                                                        int ih, int iw, int oh, int ow) {
     const float sh = (float)ih / (float)oh, sw = (float)iw / (float)ow;
@@ -199,8 +203,8 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const int x = (int)(idx % ow), y = (int)((idx / ow) % oh);
         const long p = idx / ((long)ow * oh);
-        const float fy = fmaxf(__fsub_rn(__fmul_rn(sh, (float)y + 0.5f), 0.5f), 0.0f);
-        const float fx = fmaxf(__fsub_rn(__fmul_rn(sw, (float)x + 0.5f), 0.5f), 0.0f);
+        const float fy = fmaxf(fmaf(sh, (float)y + 0.5f, -0.5f), 0.0f);
+        const float fx = fmaxf(fmaf(sw, (float)x + 0.5f, -0.5f), 0.0f);
         const int y0 = min((int)fy, ih - 1), x0 = min((int)fx, iw - 1);
         const int y1 = min(y0 + 1, ih - 1), x1 = min(x0 + 1, iw - 1);
         const float ly = fy - (float)y0, lx = fx - (float)x0;

@@ -390,8 +390,9 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     if (dlogits) {
         float* d = dlogits + row * V;
         const float base = eps / (float)V;
+        // softmax as exp(x - max) / sum, not exp(x - lse): lse is rounded to ulp(|lse|), which at |logits| ~ 1e4 is 1e-3
         for (int v = tid; v < V; v += 256) {
-            float g = expf(x[v] - lse) - base - (v == tg ? (1.f - eps) : 0.f);
+            float g = expf(x[v] - m) / s - base - (v == tg ? (1.f - eps) : 0.f);
             d[v] = keep ? g : 0.f;
         }
     }
@@ -465,20 +466,48 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
     }
 }
 
-// dEmb[tok[bt]] += dX[bt][:E] * mask ;  dEnc[b] = sum_t dX[b,t][E:] * mask
-__global__ __launch_bounds__(256) void emb_scatter_kernel(const float* __restrict__ dX, const int32_t* __restrict__ tok,
-                                                          float* __restrict__ dEmb, size_t BT, int E, int V, float p,
-                                                          unsigned long long seed, int attn_path) {
-    const size_t total = BT * E;
+// dEmb[v] = sum over the rows bt with tok[bt] == v of dX[bt][:E] * mask ;  dEnc[b] = sum_t dX[b,t][E:] * mask
+// A gather in a FIXED order (fp32 atomics added in an order that varied from launch to launch, so two runs of one
+// training differed in a few embedding weights): one workgroup per (vocabulary row, 64 columns).  The tokens are
+// scanned 256 at a time, the hits of a chunk listed in ascending bt (ballot + popcount); wave r adds the chunk's hits
+// r, r + 4, ... for its 64 columns, and the four sums are added in wave order at the end.  Every element of dEmb is
+// written.  Rows after a sequence's end carry exact zeros (and hit ONE row: PAD).
+constexpr int EMB_COLS = 64;
+__global__ __launch_bounds__(256) void emb_gather_kernel(const float* __restrict__ dX, const int32_t* __restrict__ tok,
+                                                         float* __restrict__ dEmb, size_t BT, int E, int V, float p,
+                                                         unsigned long long seed, int attn_path) {
+    __shared__ int hits[256];
+    __shared__ int wave_hits[4];
+    __shared__ float part[4][EMB_COLS];
+    const int v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int e = blockIdx.y * EMB_COLS + lane;
     const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const size_t bt = i / E;
-        const int e = (int)(i - bt * E);
-        const int tk = min(max(tok[bt], 0), V - 1);
-        const float k = keep_scale(seed, DS_X, attn_path ? bt * E + e : bt * 2 * E + e, p, inv_keep);
-        const float v = dX[bt * 2 * E + e] * k;
-        if (v != 0.f) atomicAdd(dEmb + (size_t)tk * E + e, v);   // rows after a sequence's end carry exact zeros (and hit ONE row: PAD)
+    float acc = 0.f;
+    for (size_t bt0 = 0; bt0 < BT; bt0 += 256) {
+        const size_t bt = bt0 + tid;
+        const bool hit = bt < BT && min(max(tok[bt], 0), V - 1) == v;
+        const unsigned long long mask = __ballot(hit);
+        if (lane == 0) wave_hits[wave] = __popcll(mask);
+        __syncthreads();
+        int before = 0, n = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) before += wave_hits[w];
+            n += wave_hits[w];
+        }
+        if (hit) hits[before + __popcll(mask & ((1ull << lane) - 1ull))] = tid;
+        __syncthreads();
+        if (e < E) {
+#pragma unroll 4
+            for (int h = wave; h < n; h += 4) {
+                const size_t b = bt0 + hits[h];
+                acc += dX[b * 2 * E + e] * keep_scale(seed, DS_X, attn_path ? b * E + e : b * 2 * E + e, p, inv_keep);
+            }
+        }
+        __syncthreads();                                 // hits / wave_hits are rewritten by the next chunk
     }
+    part[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && e < E) dEmb[(size_t)v * E + e] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
 }
 // 32 (b, e) outputs x 8 time lanes per workgroup: lane r adds the steps r, r + 8, ..., the eight sums are added in
 // lane order (fixed order: deterministic)
@@ -506,10 +535,6 @@ __global__ __launch_bounds__(256) void denc_reduce_kernel(const float* __restric
         for (int i = 1; i < 8; ++i) t += sm[i][c];
         dEnc[idx] = t;
     }
-}
-
-__global__ void fill_kernel(float* __restrict__ p, size_t n, float v) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
 // out[k][4j+g] = W[(g*H+j)][k]  (same re-layout as decode.hip's prepare)
@@ -929,9 +954,7 @@ extern "C" int i2l_decoder_train_bwd(const i2l_decoder_weights* w, const int32_t
     hipLaunchKernelGGL(denc_reduce_kernel, dim3(i2l_cdiv(B * E, 32)), dim3(256), 0, s, (const float*)F(lo.dX),
                        denc_out, B, T, E, dropout_p, (unsigned long long)seed, attention_path);
     I2L_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fill_kernel, dim3(grid_for((size_t)V * E)), dim3(256), 0, s_e, gr->embedding, (size_t)V * E, 0.f);
-    I2L_CHECK_LAUNCH();
-    hipLaunchKernelGGL(emb_scatter_kernel, dim3(grid_for(BT * E)), dim3(256), 0, s_e, (const float*)F(lo.dX), tokens,
+    hipLaunchKernelGGL(emb_gather_kernel, dim3(V, i2l_cdiv(E, EMB_COLS)), dim3(256), 0, s_e, (const float*)F(lo.dX), tokens,
                        gr->embedding, BT, E, V, dropout_p, (unsigned long long)seed, attention_path);
     I2L_CHECK_LAUNCH();
     return I2L_OK;

@@ -6,6 +6,8 @@
 //   total  = ||g||_2 over all parameters            nn.utils.clip_grad_norm_: coef = min(1, max_norm/(total+1e-6))
 //   g      = g * coef + weight_decay * p            torch.optim.Adam's L2 is coupled (added to the gradient)
 //   m, v, p updated with bias correction            denom = sqrt(v)/sqrt(1-b2^t) + eps ; p -= lr/(1-b1^t) * m/denom
+// lr, the betas, eps, weight_decay and max_norm are taken at their fp32 values; the step coefficients lr / (1 - b1^t) and
+// sqrt(1 - b2^t) are evaluated in double from those and rounded to fp32 once.
 // Three launches, no host synchronisation; the sum of squares is reduced in a fixed order (deterministic).
 // Non-finite total norm (Inf / NaN gradients: an fp16-scaled overflow, or the NaN a grouped training kernel writes
 // when one of its bounded waits expires) => the call is a no-op on p, m, v: stats[3] = 1 and a counter in the
@@ -73,8 +75,9 @@ __global__ __launch_bounds__(256) void norm_final_kernel(const double* __restric
         int applied = step - (int)nskip;                 // optimizer step number among the APPLIED updates
         if (applied < 1) applied = 1;
         coefs[0] = skip ? 0.f : 1.f;
-        coefs[1] = lr / (1.f - powf(b1, (float)applied));
-        coefs[2] = sqrtf(1.f - powf(b2, (float)applied));
+        // in double, rounded to fp32 once: 1 - b^t cancels, and fp32 leaves sqrt(1 - 0.999^t) off by up to 1e-5
+        coefs[1] = (float)((double)lr / (1.0 - pow((double)b1, (double)applied)));
+        coefs[2] = (float)sqrt(1.0 - pow((double)b2, (double)applied));
     }
 }
 

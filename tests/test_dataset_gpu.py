@@ -410,18 +410,11 @@ def test_cli_train_native_runs(tmp_path):
 
 
 def test_cli_train_native_twice_gives_bit_identical_parameters(tmp_path):
-    """The same seed, ``--data native`` run twice: bit-identical parameters.
-
-    FAILS on the MI355X in about every second run, and not because of the loaders: the two runs see the same batches
-    (the loader's order and its warp are functions of the seed alone) and every parameter but one always comes out
-    bit-identical.  The exception is ``decoder.embedding.weight``: the training step's embedding gradient
-    (train_decoder.hip, ``emb_scatter_kernel``) adds with fp32 atomics whose order varies from launch to launch, as
-    tests/test_hip_training.py ``test_side_stream_weight_gradients_are_the_same_numbers`` already records for two runs of
-    ONE step.  Measured on one MI355X, 8 runs of this configuration (4 steps each), each compared with the first: 4 were
-    bit-identical; 3 differed, in 1 or 2 of the 1760 embedding weights, by at most 7.5e-9 (twice 1.2e-10) at a largest
-    weight of 3.27; in the two whole-suite runs the check failed once and passed once.  A scatter with a fixed summation
-    order is a change to the training kernels, not to the data set, and is not part of this change; the check stays as it
-    was asked for."""
+    """The same seed, ``--data native`` run twice: bit-identical parameters.  The two runs see the same batches (the
+    loader's order and its warp are functions of the seed alone), and every sum of the training step has a fixed order:
+    the embedding gradient, once a scatter of fp32 atomics whose order varied from launch to launch (1 or 2 of the 1760
+    embedding weights then differed in about every second pair of runs), is a gather in ascending token position
+    (train_decoder.hip, ``emb_gather_kernel``)."""
     outs = _train_twice(tmp_path)
     cks = [torch.load(o["checkpoint"], map_location="cpu", weights_only=False) for o in outs]
     assert cks[0]["tokenizer_config"]["token_to_id"] == cks[1]["tokenizer_config"]["token_to_id"]
