@@ -45,17 +45,33 @@ def sid(shape, variant=None):
 _MODELS = {}
 
 
-def build(shape, variant=None):
+def model_from_sd(cfg, sd):
+    """(Seq2SeqModel on the device, float64 decoder state dict on the device) of a numpy state dict."""
+    m = Seq2SeqModel("cnn_lstm", cfg["vocab_size"], synth.encoder_params(cfg), synth.decoder_params(cfg))
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    m = m.to(DEV).eval()
+    sd64 = {k: torch.from_numpy(v).to(DEV, torch.float64) for k, v in sd.items() if k.startswith("decoder.")}
+    return m, sd64
+
+
+def shape_config(shape):
+    V, E, H, L, attn = shape
+    return synth.model_config(vocab_size=V, embedding_dim=E, hidden_dim=H, lstm_layers=L, attention=attn,
+                              channels=1, img_height=16, img_width=32, conv_filters=(4, 8, 16))
+
+
+def build(shape, variant=None, seed=None):
     """(Seq2SeqModel on the device, float64 decoder state dict on the device, cfg): synthetic weights; the encoder is a
     tiny one and unused -- every test feeds a synthetic encoder output.  ``variant`` "flat": output weights at
     8/sqrt(H) instead of 12 and no END clock, so that the sampling masks keep tens to hundreds of columns; "negative":
-    output weights at 1/sqrt(H) and the output bias lowered by 20, so that every logit is negative."""
-    key = (shape, variant)
+    output weights at 1/sqrt(H) and the output bias lowered by 20, so that every logit is negative.  ``seed``: of the
+    weights, instead of the one derived from (H, L)."""
+    key = (shape, variant, seed)
     if key not in _MODELS:
         V, E, H, L, attn = shape
-        cfg = synth.model_config(vocab_size=V, embedding_dim=E, hidden_dim=H, lstm_layers=L, attention=attn,
-                                 channels=1, img_height=16, img_width=32, conv_filters=(4, 8, 16))
-        seed = 100 + H // 64 + 17 * L
+        cfg = shape_config(shape)
+        if seed is None:
+            seed = 100 + H // 64 + 17 * L
         if variant == "flat":
             sd = synth.make_state_dict(cfg, seed=seed, out_scale=8.0)
         elif variant == "negative":           # |W_out h| < sqrt(H) < 20
@@ -64,11 +80,7 @@ def build(shape, variant=None):
             sd["decoder.output_layer.bias"] = sd["decoder.output_layer.bias"] - np.float32(20.0)
         else:
             sd = synth.make_state_dict(cfg, seed=seed, out_scale=12.0, end_clock=(0.05, 12.0, 6.0))
-        m = Seq2SeqModel("cnn_lstm", V, synth.encoder_params(cfg), synth.decoder_params(cfg))
-        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-        m = m.to(DEV).eval()
-        sd64 = {k: torch.from_numpy(v).to(DEV, torch.float64) for k, v in sd.items() if k.startswith("decoder.")}
-        _MODELS[key] = (m, sd64, cfg)
+        _MODELS[key] = model_from_sd(cfg, sd) + (cfg,)
     return _MODELS[key]
 
 
