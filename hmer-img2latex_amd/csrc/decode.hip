@@ -242,6 +242,7 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned row
 #include "decode_group16.inc.h"
 #include "beam_group.inc.h"
 #include "decode_batched.inc.h"
+#include "beam_batched.inc.h"
 
 // KR / KL > 0 (fast path for R == 1, L == 1, H <= 256: thread j owns hidden unit j for the whole loop):
 // rows [0,KR) of WhhT stay in the thread's registers and rows [KR,KR+KL) in LDS for all steps, so only
@@ -1081,7 +1082,7 @@ extern "C" int i2l_greedy_decode_batched(const i2l_decoder_weights* w, const voi
     char* sb = static_cast<char*>(scratch);
     BatchedParams p{};
     p.w = step_weights(lo, static_cast<const char*>(workspace), V, H, L);
-    p.B = rows; p.T = steps; p.forced = forced;
+    p.B = rows; p.T = steps; p.genc_div = 1; p.forced = forced;
     p.h = reinterpret_cast<float*>(sb + bl.h); p.c = reinterpret_cast<float*>(sb + bl.c);
     p.lg = reinterpret_cast<float*>(sb + bl.lg);
     p.tok = reinterpret_cast<int*>(sb + bl.tok); p.fin = reinterpret_cast<int*>(sb + bl.fin);
@@ -1231,6 +1232,96 @@ extern "C" int i2l_beam_decode(const i2l_decoder_weights* w, const void* workspa
         case 8: return launch_beam<8>(p, lds, s);
         default: return I2L_ERR_UNSUPPORTED;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Step-batched beam search (beam_batched.inc.h): the images x beam slots are the rows of one batched step, L + 2 plain
+// launches per step on the caller's stream.
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t i2l_beam_batched_scratch_bytes(int images, int beam, int vocab, int hidden, int layers, int steps) {
+    if (!beam_batched_dims_ok(images, beam, vocab, hidden, layers, steps)) return 0;
+    return beam_batched_layout(images, beam, i2l_cdiv(vocab, VCHUNK) * VCHUNK, hidden, layers, steps).total;
+}
+
+namespace {
+template <int K>
+void launch_beam_step_batched(const BeamBatchedParams& p, float* c_cur, float* c_next, int t, hipStream_t s) {
+    hipLaunchKernelGGL(beam_step_batched_kernel<K>, dim3(p.images), dim3(DB_NT), 0, s, p, c_cur, c_next, t);
+}
+}  // namespace
+
+extern "C" int i2l_beam_decode_batched(const i2l_decoder_weights* w, const void* workspace, int images, int beam,
+                                       int steps, int start_id, int end_id, void* scratch, size_t scratch_bytes,
+                                       int32_t* seq_out, int32_t* len_out, double* score_out, int flags,
+                                       i2l_stream_t stream) {
+    (void)flags;
+    // every refusal is decided here, before the first HIP call
+    int rc = check_weights(w);
+    if (rc != I2L_OK) return rc;
+    if (!workspace || !scratch || !seq_out || !len_out || images <= 0 || steps <= 0 || beam <= 0) return I2L_ERR_ARG;
+    const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
+    if (!beam_batched_dims_ok(images, beam, V, H, L, steps)) return I2L_ERR_UNSUPPORTED;
+    const Layout lo = make_layout(images, V, E, H, L);
+    const BeamBatchedLayout bl = beam_batched_layout(images, beam, lo.Vp, H, L, steps);
+    if (scratch_bytes < bl.total) return I2L_ERR_WORKSPACE;
+
+    char* sb = static_cast<char*>(scratch);
+    const int R = images * beam;
+    const size_t LRH = (size_t)L * R * H;
+    BeamBatchedParams bp{};
+    bp.images = images; bp.T = steps; bp.V = V; bp.Vp = lo.Vp; bp.H = H; bp.L = L;
+    bp.start_id = start_id; bp.end_id = end_id;
+    bp.tokhist = reinterpret_cast<int32_t*>(sb + bl.hist);
+    bp.parhist = bp.tokhist + (size_t)images * steps * beam;
+    bp.h = reinterpret_cast<float*>(sb + bl.h); bp.c = reinterpret_cast<float*>(sb + bl.c);
+    bp.lg = reinterpret_cast<float*>(sb + bl.lg);
+    bp.score = reinterpret_cast<double*>(sb + bl.score);
+    bp.last = reinterpret_cast<int*>(sb + bl.last); bp.slot_live = reinterpret_cast<int*>(sb + bl.slot_live);
+    bp.img = reinterpret_cast<BeamImage*>(sb + bl.img);
+    bp.live = reinterpret_cast<unsigned*>(sb + bl.live);
+    bp.seq_out = seq_out; bp.len_out = len_out; bp.score_out = score_out;
+
+    // the GEMM launches of decode_batched.inc.h on the R rows: the slot's last token, the image's Genc row, parity 0
+    BatchedParams p{};
+    p.w = step_weights(lo, static_cast<const char*>(workspace), V, H, L);
+    p.B = R; p.T = steps; p.genc_div = beam; p.forced = nullptr;
+    p.h = bp.h; p.lg = reinterpret_cast<float*>(sb + bl.lg);
+    p.tok = bp.last; p.live = bp.live;
+    p.temperature = 1.0f; p.select = I2L_SELECT_LOGITS; p.stop = I2L_STOP_NONE; p.end_id = end_id;
+
+    hipStream_t s = i2l_s(stream);
+    const size_t init_blocks = (2 * LRH + DB_NT - 1) / DB_NT;
+    hipLaunchKernelGGL(beam_init_batched_kernel, dim3((unsigned)(init_blocks < 1024 ? init_blocks : 1024)), dim3(DB_NT), 0,
+                       s, bp, beam);
+    I2L_CHECK_LAUNCH();
+    const int tb_lstm = batched_tile_rows(H / 16, R), tb_logits = batched_tile_rows(lo.Vp / DB_COLS, R);
+    for (int t = 0; t < steps; ++t) {
+        float* c_cur = bp.c + (size_t)(t & 1) * LRH;
+        float* c_next = bp.c + (size_t)((t + 1) & 1) * LRH;
+        p.c = c_cur;
+        for (int l = 0; l < L; ++l) {
+            if (tb_lstm == 16) launch_batched_lstm<16>(p, l, 0, s);
+            else if (tb_lstm == 32) launch_batched_lstm<32>(p, l, 0, s);
+            else launch_batched_lstm<64>(p, l, 0, s);
+        }
+        if (tb_logits == 16) launch_batched_logits<16>(p, 0, s);
+        else if (tb_logits == 32) launch_batched_logits<32>(p, 0, s);
+        else launch_batched_logits<64>(p, 0, s);
+        switch (beam) {
+            case 1: launch_beam_step_batched<1>(bp, c_cur, c_next, t, s); break;
+            case 2: launch_beam_step_batched<2>(bp, c_cur, c_next, t, s); break;
+            case 3: launch_beam_step_batched<3>(bp, c_cur, c_next, t, s); break;
+            case 4: launch_beam_step_batched<4>(bp, c_cur, c_next, t, s); break;
+            case 5: launch_beam_step_batched<5>(bp, c_cur, c_next, t, s); break;
+            case 6: launch_beam_step_batched<6>(bp, c_cur, c_next, t, s); break;
+            case 7: launch_beam_step_batched<7>(bp, c_cur, c_next, t, s); break;
+            default: launch_beam_step_batched<8>(bp, c_cur, c_next, t, s); break;
+        }
+        I2L_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(beam_final_batched_kernel, dim3(i2l_cdiv(images, DB_NT)), dim3(DB_NT), 0, s, bp, beam);
+    I2L_CHECK_LAUNCH();
+    return I2L_OK;
 }
 
 extern "C" size_t i2l_decoder_group_status_offset(int rows, int vocab, int embed, int hidden, int layers) {

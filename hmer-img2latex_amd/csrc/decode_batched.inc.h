@@ -27,6 +27,7 @@ constexpr int DB_KG = DB_KC / 8; // 8-element k groups per round (one 16-byte op
 struct BatchedParams {
     StepWeights w;
     int B, T;
+    int genc_div;        // row r reads Genc row r / genc_div: 1, or the beam width (beam_batched.inc.h: K rows per image)
     const int32_t* forced;
     float* h;            // [2][L][B][H]
     float* c;            // [L][B][H]
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(DB_NT) void lstm_step_mfma_kernel(BatchedParams p, 
             int tk = p.forced ? p.forced[(size_t)row * p.T + t] : p.tok[row];
             tk = min(max(tk, 0), w.V - 1);
             const float4 a = *reinterpret_cast<const float4*>(w.P + (size_t)tk * G + 4 * unit);
-            const float4 e = *reinterpret_cast<const float4*>(w.Genc + (size_t)row * G + 4 * unit);
+            const float4 e = *reinterpret_cast<const float4*>(w.Genc + (size_t)(row / p.genc_div) * G + 4 * unit);
             add = make_float4(a.x + e.x, a.y + e.y, a.z + e.z, a.w + e.w);
         } else {
             add = *reinterpret_cast<const float4*>(w.biasP[layer] + 4 * unit);

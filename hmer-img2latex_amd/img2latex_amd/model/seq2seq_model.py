@@ -143,13 +143,36 @@ class Seq2SeqModel(nn.Module):
                           max_length: int, beam_size: int, return_scores: bool = False, flags: int = 0):
         """N independent batch-1 beam searches in one launch (BASELINE config 3): element j
         equals ``inference(image[j:j+1], beam_size=k)`` of the reference.  ``flags``: _lib.FLAG_NO_GROUP selects
-        the one-workgroup-per-image kernel (the automatic fallback when the grouped kernel times out)."""
+        the one-workgroup-per-image kernel (the automatic fallback when the grouped kernel times out);
+        _lib.FLAG_BEAM_BATCHED (here or in ``decoder.kernel_flags``) the step-batched matrix-core search
+        (i2l_beam_decode_batched: the images x beam slots as rows of one batched step; nothing in it can time out)."""
         if beam_size > _lib.MAX_BEAM:
             raise NotImplementedError(f"img2latex_amd: beam_size <= {_lib.MAX_BEAM} (got {beam_size})")
         dec = self.decoder
         w, keep, enc = dec.prepare(encoder_output)
         n, dev = enc.shape[0], enc.device
         L = _lib.lib()
+        if (int(flags) | int(dec.kernel_flags)) & _lib.FLAG_BEAM_BATCHED:
+            # its scratch lives for this call only, on this stream
+            nbytes = L.i2l_beam_batched_scratch_bytes(n, beam_size, dec.vocab_size, dec.hidden_dim, dec.lstm_layers,
+                                                      max_length)
+            if nbytes == 0:
+                raise RuntimeError("img2latex_amd: dimensions not supported by the step-batched beam search")
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            seq = torch.empty((n, max_length + 1), dtype=torch.int32, device=dev)
+            ln = torch.empty((n,), dtype=torch.int32, device=dev)
+            score = torch.empty((n,), dtype=torch.float64, device=dev)
+            _lib.check(L.i2l_beam_decode_batched(ctypes.byref(w), dec._ws.data_ptr(), n, beam_size, max_length,
+                                                 int(start_token_id), int(end_token_id), scratch.data_ptr(), nbytes,
+                                                 seq.data_ptr(), ln.data_ptr(), score.data_ptr(),
+                                                 int(flags) | int(dec.kernel_flags), _lib.stream_ptr()),
+                       "beam_decode_batched")
+            seq_h, lens = seq.cpu(), ln.cpu().tolist()
+            del keep, scratch
+            out = [row[:ln_j] for row, ln_j in zip(seq_h.tolist(), lens)]
+            if return_scores:
+                return out, score.cpu().tolist()
+            return out
         nbytes = L.i2l_beam_workspace_bytes(n, beam_size, dec.hidden_dim, dec.lstm_layers, max_length)
         bws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
         seq = torch.empty((n, max_length + 1), dtype=torch.int32, device=dev)

@@ -71,6 +71,8 @@ typedef void* i2l_stream_t;
                                           batch's encoder fits beside it; same ids                                   */
 #define I2L_FLAG_DECODE_BATCHED 0x2000  /* the Python layer's switch for i2l_greedy_decode_batched (LSTMDecoder.run_steps takes that entry
                                           instead of i2l_greedy_decode_ex); the C entries ignore it */
+#define I2L_FLAG_BEAM_BATCHED 0x80000   /* the Python layer's switch for i2l_beam_decode_batched, as I2L_FLAG_DECODE_BATCHED is for the greedy entry
+                                          (Seq2SeqModel.beam_search_batch takes that entry instead of i2l_beam_decode); the C entries ignore it */
 #define I2L_FLAG_DECODE_GROUP16 0x8000 /* i2l_greedy_decode_ex (ids only): the grouped kernel with SIXTEEN members x SIXTEEN rows per
                                           group and the per-step products (LSTM gates, logits) on the matrix cores as split-bf16
                                           v_mfma_f32_16x16x32_bf16 bursts (fp32-grade: 3 bf16 pieces per operand, 6 partial
@@ -424,6 +426,31 @@ int i2l_beam_decode(const i2l_decoder_weights* w, const void* workspace, int ima
                     int steps, int start_id, int end_id, void* beam_workspace,
                     size_t beam_workspace_bytes, int32_t* seq_out, int32_t* len_out,
                     double* score_out, int flags, i2l_stream_t stream);
+
+/* The same search (seq2seq.py:234-298 per image: log_softmax in fp32 and top-k :266-267, fp64 scores and the stable
+ * descending selection :268-280, ended beams retire one iteration later :258-260, `completed.extend(beams); break`
+ * :282-284, max(completed) else beams[0] :286-297) for decoders the grouped beam kernel does not take -- the shipped
+ * hidden 512 / 2 layers at the reference's default beam_size 2 (configs/config.yaml:45-50,76) first of all -- STEP-BATCHED
+ * on the matrix cores: the images x beam slots are the rows of one step, row r = slot r % beam of image r / beam.  Per
+ * step: the split-bf16 GEMM + LSTM cell launch of i2l_greedy_decode_batched per layer, its logits launch, and one launch
+ * (a workgroup per image) that ranks the image's candidates, writes the histories, gathers h and c of the new slots from
+ * their parents and retires ended slots.  One device word counts the images still searching; once it is 0 the remaining
+ * launches return at once (they are still enqueued: no host read happens inside the call).  Nothing polls, nothing can
+ * time out: len_out is never -3.  Outputs and semantics as i2l_beam_decode (workspace prepared for rows == images);
+ * sequences agree with it wherever the ranking has no fp32 near-tie, scores to fp32 rounding.
+ *   scratch  i2l_beam_batched_scratch_bytes(images, beam, vocab, hidden, layers, steps) bytes of device memory, written
+ *            by the call: the token / parent histories (images, steps, beam), h and c as (2, L, images * beam, H) each,
+ *            one padded row of logits per slot, per slot the fp64 score, last token and live flag, per image the beam
+ *            count, the best completed beam and the done flag, and the live-image word.
+ * Accepted: hidden % 64 == 0 and <= 2048, layers <= I2L_MAX_LSTM_LAYERS, 1 <= beam <= I2L_MAX_BEAM, beam <= vocab,
+ * vocab <= 2048 (the top-k scan marks taken columns in 32 bits per lane).  For other dimensions, images <= 0 or steps <= 0
+ * the size query returns 0; the call returns I2L_ERR_ARG for NULL or non-positive arguments, I2L_ERR_UNSUPPORTED for
+ * refused dimensions, I2L_ERR_WORKSPACE when scratch_bytes is smaller.  flags: none used.  Every refusal is decided on
+ * the host before the first HIP call. */
+size_t i2l_beam_batched_scratch_bytes(int images, int beam, int vocab, int hidden, int layers, int steps);
+int i2l_beam_decode_batched(const i2l_decoder_weights* w, const void* workspace, int images, int beam, int steps,
+                            int start_id, int end_id, void* scratch, size_t scratch_bytes, int32_t* seq_out,
+                            int32_t* len_out, double* score_out, int flags, i2l_stream_t stream);
 
 /* Additive attention, general source length S (Attention.forward, decoder.py:312-343):
  * context[b] = softmax_s(v . tanh(W [hidden[b] ; enc[b,s]] + b_a)) @ enc[b].
