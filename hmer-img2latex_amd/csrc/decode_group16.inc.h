@@ -32,10 +32,7 @@
 // Tags, two buffers by step parity, bounded polls, placement measurement, failure marking (ids -3), residency signal:
 // exactly as decode_group_kernel<8>.  Supported: ids out (both stop rules, temperature, arg max of logits / of softmax);
 // no logits output, no forced tokens, no initial / returned state.
-#include "bf16_split.inc.h"
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+#include "mfma_slab.inc.h"      // bf16_split.inc.h, f32x4_t / u32x4_t, Frag16
 
 constexpr int G16Q = 16;                   // members = rows per group
 constexpr int G16NT = 256;                 // threads per workgroup
@@ -48,11 +45,6 @@ constexpr int G16_HP_PIECE = 32 * 16 * 8;  // bf16 elements of one piece image
 constexpr size_t GRP16_LDS = (size_t)2 * 3 * G16_HP_PIECE * 2 + (size_t)2 * 64 * 16 + (size_t)2 * 16 * 8 + 8 * sizeof(int);
 constexpr size_t GROUP16_XCHG_PER_GROUP = (size_t)2 * G16Q * G16GRAN * 8;
 
-union Frag16 {
-    bf16x8_t v;
-    u32x4_t q;
-    unsigned short s[8];
-};
 // 16 bytes = two granules, L1 bypassed like load_granule's sc1 polls (each 8-byte half is one peer store: no tearing)
 __device__ __forceinline__ void load_run64(const u64_t* src, u32x4_t (&g)[4]) {
     asm volatile(

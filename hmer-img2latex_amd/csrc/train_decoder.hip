@@ -11,7 +11,8 @@
 //             BPTT over t (reverse), rows partitioned                 lstm_train_bwd_kernel (persistent)
 //             dW_ih, dW_hh, db (all layers), dX                       MFMA GEMMs over all B*T rows at once
 //             dEmb (scatter-add by token), dEnc (sum over t)          small kernels
-// Only the two recurrences are sequential; every weight gradient is one large GEMM.
+// Only the two recurrences are sequential; every weight gradient is one large GEMM.  I2L_FLAG_TRAIN_BATCHED swaps both
+// for one launch per (step, layer) on the matrix cores (train_batched.inc.h); everything around them stays.
 // Dropout masks come from a counter-based hash of (seed, stream, element index), so backward
 // regenerates them instead of storing them.  With the reference's Attention over a length-1
 // source the context equals enc (see decode.hip), and the attention parameters receive an
@@ -357,6 +358,8 @@ __global__ __launch_bounds__(NT) void lstm_train_bwd_kernel(BwdBuf p) {
     }
 }
 
+#include "train_batched.inc.h"
+
 // ------------------------------------------------------------------ cross entropy with label smoothing
 // One workgroup per (b,t) row.  row_loss = keep * ((1-eps)*nll + eps*(-mean_v logp));
 // dlogits = keep * (softmax - (1-eps)*onehot - eps/V)   [gradient of the SUM over rows; the mean's 1/count
@@ -621,10 +624,19 @@ TLayout make_tlayout(int B, int T, int V, int E, int H, int L) {
     return o;
 }
 
-int check_w(const i2l_decoder_weights* w) {
+// I2L_FLAG_TRAIN_BATCHED is a request: honoured where the step-batched recurrences take the dimensions and the caller has
+// not asked for exact fp32 products (their products are split-bf16)
+bool train_batched_on(int V, int E, int H, int L, int flags) {
+    return (flags & I2L_FLAG_TRAIN_BATCHED) && !(flags & I2L_FLAG_EXACT_FP32) && train_batched_dims_ok(V, E, H, L);
+}
+
+int check_w(const i2l_decoder_weights* w, int flags) {
     if (!w || !w->embedding || !w->w_ih || !w->w_hh || !w->b_ih || !w->b_hh || !w->w_out || !w->b_out) return I2L_ERR_ARG;
     if (w->vocab <= 0 || w->embed <= 0 || w->hidden <= 0 || w->layers <= 0) return I2L_ERR_ARG;
-    if (w->layers > MAXL || w->hidden % 64 != 0 || w->hidden > 1024 || w->embed % 4 != 0) return I2L_ERR_UNSUPPORTED;
+    // the row kernels keep their state in LDS (hidden <= 1024); the step-batched recurrences keep it in global memory
+    if (!train_batched_on(w->vocab, w->embed, w->hidden, w->layers, flags) &&
+        (w->layers > MAXL || w->hidden % 64 != 0 || w->hidden > 1024 || w->embed % 4 != 0))
+        return I2L_ERR_UNSUPPORTED;
     for (int l = 0; l < w->layers; ++l)
         if (!w->w_ih[l] || !w->w_hh[l] || !w->b_ih[l] || !w->b_hh[l]) return I2L_ERR_ARG;
     return I2L_OK;
@@ -660,15 +672,20 @@ extern "C" size_t i2l_decoder_train_workspace_bytes(int B, int T, int vocab, int
     return make_tlayout(B, T, vocab, embed, hidden, layers).total;
 }
 
+extern "C" int i2l_decoder_train_batched_ok(int vocab, int embed, int hidden, int layers) {
+    return train_batched_dims_ok(vocab, embed, hidden, layers) ? 1 : 0;
+}
+
 extern "C" int i2l_decoder_train_fwd(const i2l_decoder_weights* w, const float* enc, const int32_t* tokens, int B, int T,
                                       float dropout_p, uint64_t seed, int attention_path, void* workspace,
                                       size_t workspace_bytes, float* logits_out, int flags, i2l_stream_t stream) {
-    int rc = check_w(w);
+    int rc = check_w(w, flags);
     if (rc != I2L_OK) return rc;
     const int split = (flags & I2L_FLAG_EXACT_FP32) ? 0 : 1;
     const bool group_on = !(flags & I2L_FLAG_NO_GROUP);
     if (!enc || !tokens || !logits_out || B <= 0 || T <= 0 || dropout_p < 0.f || dropout_p >= 1.f) return I2L_ERR_ARG;
     const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
+    const bool batched = train_batched_on(V, E, H, L, flags);
     const TLayout lo = make_tlayout(B, T, V, E, H, L);
     if (!workspace || workspace_bytes < lo.total) return I2L_ERR_WORKSPACE;
     char* base = static_cast<char*>(workspace);
@@ -709,7 +726,12 @@ extern "C" int i2l_decoder_train_fwd(const i2l_decoder_weights* w, const float* 
         p.WhhT[l] = F(lo.WhhT[l]); p.WihT[l] = l ? F(lo.WihT[l]) : nullptr; p.biasP[l] = l ? F(lo.biasP[l]) : nullptr;
         p.ACT[l] = F(lo.ACT[l]); p.C[l] = F(lo.C[l]); p.Hout[l] = F(lo.Hout[l]); p.Hprev[l] = F(lo.Hprev[l]);
     }
-    {
+    if (batched) {      // one launch per (step, layer) on the matrix cores (train_batched.inc.h)
+        float* drop[MAXL] = {};
+        for (int l = 0; l < L; ++l) drop[l] = F(lo.DG[l]);      // dead until the backward writes it
+        rc = train_batched_forward(p, drop, s);
+        if (rc != I2L_OK) return rc;
+    } else {
         const size_t per_row = (size_t)4 * L * H * sizeof(float);
         const int R = rows_per_wg(B, per_row, 0);
         const size_t lds = R * per_row;
@@ -789,13 +811,14 @@ extern "C" int i2l_decoder_train_bwd(const i2l_decoder_weights* w, const int32_t
                                       uint64_t seed, int attention_path, void* workspace, size_t workspace_bytes,
                                       const float* dlogits, const i2l_decoder_grads* gr, float* denc_out,
                                       int flags, i2l_lanes* lanes, i2l_stream_t stream) {
-    int rc = check_w(w);
+    int rc = check_w(w, flags);
     if (rc != I2L_OK) return rc;
     const int split = (flags & I2L_FLAG_EXACT_FP32) ? 0 : 1;
     const bool group_on = !(flags & I2L_FLAG_NO_GROUP);
     if (!tokens || !dlogits || !gr || !denc_out || B <= 0 || T <= 0) return I2L_ERR_ARG;
     if (!gr->embedding || !gr->w_ih || !gr->w_hh || !gr->b_ih || !gr->b_hh || !gr->w_out || !gr->b_out) return I2L_ERR_ARG;
     const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
+    const bool batched = train_batched_on(V, E, H, L, flags);
     const TLayout lo = make_tlayout(B, T, V, E, H, L);
     if (!workspace || workspace_bytes < lo.total) return I2L_ERR_WORKSPACE;
     char* base = static_cast<char*>(workspace);
@@ -849,7 +872,10 @@ extern "C" int i2l_decoder_train_bwd(const i2l_decoder_weights* w, const int32_t
         p.ACT[l] = F(lo.ACT[l]); p.C[l] = F(lo.C[l]); p.DG[l] = F(lo.DG[l]);
         p.Whh[l] = w->w_hh[l]; p.Wih[l] = l ? w->w_ih[l] : nullptr;
     }
-    {
+    if (batched) {      // GX is the forward's: dc_next and the K slices of dh live there (train_batched.inc.h)
+        rc = train_batched_backward(p, F(lo.GX), s);
+        if (rc != I2L_OK) return rc;
+    } else {
         const int NG = bwd_row_groups(H);
         if (NG <= 0) return I2L_ERR_UNSUPPORTED;
         const size_t per_row = ((size_t)2 * L * H + H + G + (size_t)NG * H) * sizeof(float);

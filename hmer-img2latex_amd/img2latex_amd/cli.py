@@ -76,6 +76,16 @@ def _decode_flags(decode_kernel: str) -> int:
     return _lib.FLAG_DECODE_BATCHED if decode_kernel == "batched" else 0
 
 
+def _train_flags(train_kernel: str) -> int:
+    """--train-kernel: "auto" = the library's own choice (grouped recurrences at one layer of 256 units, else a row per
+    workgroup); "batched" = the step-batched matrix-core recurrences (_lib.FLAG_TRAIN_BATCHED), built for decoders the
+    grouped kernels do not take, such as the shipped two-layer, 512-wide one, and the only ones above 1024 units."""
+    from . import _lib
+    if train_kernel not in ("auto", "batched"):
+        raise SystemExit(f"img2latex_amd: --train-kernel {train_kernel}: expected auto or batched")
+    return _lib.FLAG_TRAIN_BATCHED if train_kernel == "batched" else 0
+
+
 def predict(checkpoint_path: str, image_path: str, beam_size: int = 0, max_length: int = 141, temperature: float = 1.0,
             top_k: int = 0, top_p: float = 0.0, device: Optional[str] = None, decode_kernel: str = "auto") -> str:
     """cli.py:253-308: returns the LaTeX string the command prints.  ``decode_kernel``: see ``_decode_flags``."""
@@ -130,7 +140,8 @@ def _synthetic_batches(config: Dict, steps: int, vocab_size: int, seed: int):
 def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: str = "img2latex_v1",
           checkpoint_path: Optional[str] = None, data_dir: Optional[str] = None, device: Optional[str] = None,
           seed: int = 42, synthetic_steps: int = 0, synthetic_vocab: int = 512, output_dir: str = "outputs",
-          synthetic_val_steps: int = 0, augment: bool = False, data: str = "auto", decode: Optional[str] = None) -> Dict:
+          synthetic_val_steps: int = 0, augment: bool = False, data: str = "auto", decode: Optional[str] = None,
+          train_kernel: str = "auto") -> Dict:
     """cli.py:104-250 reduced to the hot path: model from the config, optional resume, TrainStep over the batches, a
     checkpoint in the reference's layout (trainer.py:209-224) per epoch, and -- with validation batches -- the epoch-end
     validation / LR schedule / best checkpoint / early stop of trainer.py:713-766.  Returns {"loss", "steps",
@@ -138,7 +149,8 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
     training batch with ``data.Augment(seed=seed).tensor`` (keyed by epoch and the sample's position in the epoch); the
     native loaders warp the raw pages with the same keys instead.  ``data``: "auto", "native" or "reference" (see the
     module docstring).  ``decode``: where the native loaders decode the page files, "host" (PIL) or "device"
-    (i2l_png_decode); None leaves it to the config key ``data.decode`` (default "host")."""
+    (i2l_png_decode); None leaves it to the config key ``data.decode`` (default "host").  ``train_kernel``: see
+    ``_train_flags`` (training and the epoch-end validation follow it)."""
     import random
     from . import data as D
     from .training import EarlyStopping, PlateauSchedule, TokenTable, TrainStep, save_checkpoint, validate
@@ -194,6 +206,7 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
     if resume is not None:
         model.load_state_dict(resume["model_state_dict"])                   # trainer.py:253
     model = model.to(dev)
+    model.decoder.kernel_flags |= _train_flags(train_kernel)
     ts = TrainStep(model, lr=float(tcfg.get("learning_rate", 1e-3)), weight_decay=float(tcfg.get("weight_decay", 1e-4)),
                    clip_grad_norm=float(tcfg.get("clip_grad_norm", 5.0)), pad_token_id=tokenizer.pad_token_id,
                    label_smoothing=0.1, seed=seed)                          # trainer.py:91-93,111-115
@@ -401,6 +414,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     t.add_argument("--decode", choices=("host", "device"), default=None,
                    help="(this package, --data native) decode the page files with PIL on the host or with the PNG kernel on "
                         "the device; default: the config key data.decode, else host")
+    t.add_argument("--train-kernel", choices=("auto", "batched"), default="auto",
+                   help="(this package) decoder recurrences of a training step: auto, or the step-batched matrix-core ones")
     e = sub.add_parser("evaluate", help="Evaluate the model on a dataset.")
     e.add_argument("checkpoint_path", help="Path to trained model checkpoint")
     e.add_argument("data_dir", help="Path to data directory")
@@ -436,7 +451,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,
               args.synthetic_steps, args.synthetic_vocab, args.output_dir, args.synthetic_val_steps, args.augment,
-              args.data, args.decode)
+              args.data, args.decode, args.train_kernel)
     except SystemExit:
         raise
     except Exception as exc:                                                # cli.py:247-250: failure -> exit code 1

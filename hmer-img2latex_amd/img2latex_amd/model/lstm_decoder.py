@@ -85,7 +85,9 @@ class LSTMDecoder(nn.Module):
         self._ws_by_stream = {}      # stream handle -> (workspace, key): concurrent decodes must not share one
         self.kernel_flags = 0        # _lib.FLAG_NO_GROUP / FLAG_EXACT_FP32 (training), FLAG_AGENT_SCOPE_EXCHANGE (all grouped),
                                      # FLAG_DECODE_BATCHED (every greedy path through run_steps),
-                                     # FLAG_BEAM_BATCHED (Seq2SeqModel.beam_search_batch, inference(beam_size=k))
+                                     # FLAG_BEAM_BATCHED (Seq2SeqModel.beam_search_batch, inference(beam_size=k)),
+                                     # FLAG_TRAIN_BATCHED (training forward / backward and training.validate: the
+                                     # step-batched matrix-core recurrences; the inference entries ignore it)
 
     # ------------------------------------------------------------------ plumbing
     def _weights_struct(self):

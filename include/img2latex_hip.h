@@ -73,6 +73,12 @@ typedef void* i2l_stream_t;
                                           instead of i2l_greedy_decode_ex); the C entries ignore it */
 #define I2L_FLAG_BEAM_BATCHED 0x80000   /* the Python layer's switch for i2l_beam_decode_batched, as I2L_FLAG_DECODE_BATCHED is for the greedy entry
                                           (Seq2SeqModel.beam_search_batch takes that entry instead of i2l_beam_decode); the C entries ignore it */
+#define I2L_FLAG_TRAIN_BATCHED 0x100000 /* i2l_decoder_train_fwd / _bwd: the step-batched recurrences on the matrix cores -- one plain launch per
+                                          (step, layer) over the whole batch, split-bf16 products, state in global memory -- where
+                                          i2l_decoder_train_batched_ok says 1 and I2L_FLAG_EXACT_FP32 is clear (also at layers 1 / hidden 256,
+                                          instead of the grouped recurrences: A/B); a request, ignored elsewhere; default off.  Every other
+                                          entry that takes decoder flags ignores it.  (Bits 20-23 are also I2L_FLAG_RESNET_PATCH_SHAPE's field:
+                                          that one is read by i2l_conv_bn_act_bf16_fwd alone, which never sees decoder flags.) */
 #define I2L_FLAG_DECODE_GROUP16 0x8000 /* i2l_greedy_decode_ex (ids only): the grouped kernel with SIXTEEN members x SIXTEEN rows per
                                           group and the per-step products (LSTM gates, logits) on the matrix cores as split-bf16
                                           v_mfma_f32_16x16x32_bf16 bursts (fp32-grade: 3 bf16 pieces per operand, 6 partial
@@ -478,10 +484,17 @@ typedef struct i2l_decoder_grads {
  * (B,T) int32 [= formulas[:, :-1], seq2seq.py:115-120]; keeps what BPTT needs in `workspace`.
  * dropout_p: nn.Dropout p (masks from a counter-based hash of `seed`; 0 disables);
  * attention_path: 0 = decoder.py:121-143 (dropout on cat[emb,enc]), 1 = :144-193 (dropout on emb).
- * logits_out (B,T,V).  flags: I2L_FLAG_NO_GROUP (row-per-workgroup recurrences), I2L_FLAG_EXACT_FP32 (GEMMs);
- * pass the same flags to the backward call.  If a bounded wait of the grouped recurrence expires its outputs are
- * NaN (the loss and every gradient become NaN; i2l_grad_clip_adam_step then skips the update). */
+ * logits_out (B,T,V).  flags: I2L_FLAG_NO_GROUP (row-per-workgroup recurrences), I2L_FLAG_EXACT_FP32 (GEMMs),
+ * I2L_FLAG_TRAIN_BATCHED (step-batched recurrences); the caller MUST pass the same flags to the backward call: forward
+ * and backward of one step have to agree on the path (the step-batched backward keeps its scratch where the forward kept
+ * GX, and accepts dimensions the row kernels refuse).  If a bounded wait of the grouped recurrence expires its outputs are
+ * NaN (the loss and every gradient become NaN; i2l_grad_clip_adam_step then skips the update).
+ * Accepted: embed % 4 == 0, hidden % 64 == 0, layers <= I2L_MAX_LSTM_LAYERS, hidden <= 1024 -- with
+ * I2L_FLAG_TRAIN_BATCHED honoured, hidden <= 2048.  i2l_decoder_train_batched_ok (pure host code) returns 1 for the
+ * dimensions at which the flag is honoured (I2L_FLAG_EXACT_FP32 clear) and 0 otherwise.  The workspace size does not
+ * depend on the flag. */
 size_t i2l_decoder_train_workspace_bytes(int B, int T, int vocab, int embed, int hidden, int layers);
+int i2l_decoder_train_batched_ok(int vocab, int embed, int hidden, int layers);
 int i2l_decoder_train_fwd(const i2l_decoder_weights* w, const float* enc, const int32_t* tokens, int B, int T,
                           float dropout_p, uint64_t seed, int attention_path, void* workspace,
                           size_t workspace_bytes, float* logits_out, int flags, i2l_stream_t stream);
