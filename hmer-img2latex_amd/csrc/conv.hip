@@ -8,7 +8,8 @@
 //
 // (1) conv3x3_mfma_kernel -- implicit GEMM on the fp32 matrix cores (Cout % 32 == 0).
 //     v_mfma_f32_32x32x2_f32 is bit-for-bit a k-ordered fp32 fmaf chain, so this keeps
-//     exact fp32 numerics at up to 2.3x the VALU rate.
+//     exact fp32 numerics at up to 2.3x the VALU rate.  One chain per chunk of
+//     CI_BLK input channels; the chunks' sums are added in chunk order.
 //       M (32 rows of an MFMA tile) = 2 conv rows x 16 conv cols, ordered (pooled x, dy, dx):
 //         row i = 4*pp + 2*dy + dx.  In the 32x32 C/D layout a lane then holds, for ITS output
 //         channel, whole 2x2 pooling quads in consecutive registers: pooling is 3 v_max per
@@ -154,7 +155,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(
         commit();
         __syncthreads();
         if (chunk + 1 < n_chunks) fetch(chunk + 1);                // in flight during the MFMAs below
-        // ---- (CI_BLK/2) x 9 k-steps, 2*NTL MFMAs each
+        // ---- (CI_BLK/2) x 9 k-steps, 2*NTL MFMAs each.  A chunk is summed on its own (a k-ordered fmaf chain from zero)
+        // and joins the running sum in one addition: one chain over all of Cin rounds every step at the size of the
+        // whole sum -- 144 products left 2^-21.5 of sum |x||w| + |b| over 12.6 M outputs, per chunk 2^-22.4
+        // (tests/test_conv_block_paths.py)
+        f32x16 part[2][NTL];
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n = 0; n < NTL; ++n)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) part[m][n][r] = 0.f;
 #pragma unroll
         for (int cp = 0; cp < CI_BLK / 2; ++cp) {
 #pragma unroll
@@ -167,11 +178,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(
 #pragma unroll
                 for (int n = 0; n < NTL; ++n) {
                     const float bn = w_s[b_base + boff + 32 * n];
-                    acc[0][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bn, acc[0][n], 0, 0, 0);
-                    acc[1][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bn, acc[1][n], 0, 0, 0);
+                    part[0][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bn, part[0][n], 0, 0, 0);
+                    part[1][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bn, part[1][n], 0, 0, 0);
                 }
             }
         }
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n = 0; n < NTL; ++n) acc[m][n] += part[m][n];
     }
 
     // ---- epilogue.  C/D layout: col = lane&31 (channel), row = (r&3) + 8*(r>>2) + 4*(lane>>5):

@@ -97,7 +97,7 @@ __global__ void conv_pack3_kernel(const float* __restrict__ w, bf16_t* __restric
 
 // FULL: plain full-resolution convolution (no bias / ReLU / pooling): the data gradient of a block, y is (B,Cout,H,W)
 // AM: also write the pooling arg max (training forward); a template parameter so that the inference kernel is unchanged
-// NT: 32-channel MFMA column tiles per wave (2 = a 64-channel block; 1 = Cout == 32, FULL only: block 1's data gradient)
+// NT: 32-channel MFMA column tiles per wave (2 = a 64-channel block per workgroup; 1 = a 32-channel block, FULL only)
 template <int WX, bool FULL = false, bool AM = false, int NT = 2>
 __global__ __launch_bounds__(256, 2) void conv3x3_bf16x3_kernel(
     const float* __restrict__ x, const bf16_t* __restrict__ wpack, const float* __restrict__ bias,
@@ -105,6 +105,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x3_kernel(
     int tiles_x, int n_chunks, int tiles_per_img, int n_items, int items_per_wg, unsigned* __restrict__ fix) {
     typedef Tile3<WX> TL;
     constexpr int PR = TL::TR / 2, PC = TL::TC / 2;
+    // LO (the data gradient, which runs NT = 1): the five small partial products of every k-step go to an accumulator
+    // pair of their own, which joins the main one in the epilogue.  All six in one chain round each k-step six times at
+    // the size of the running sum; the un-pooled gradient is 7/8 zeros, so an output is the sum of few products and that
+    // sum is large against them from the first k-step on: 2^-20.5 of sum |dyp||w| over 216 MFMAs, 2^-22.9 with the large
+    // products in a chain of their own (tests/test_conv_block_paths.py).  With 64 channels per workgroup (NT = 2, 64
+    // accumulator registers, 256 in all and spilling) there is no room for the pair and the single chain measured 2^-20.96
+    // at 128 -> 64 channels, so every data gradient takes 32-channel blocks: twice the staging per MFMA.  Registers: the
+    // 16x16 and 8x32 tiles had the 32 to spare (224 -> 256); the 4x64 tile was at 256 already and keeps 4 dwords per
+    // lane in scratch
+    constexpr bool LO = FULL && NT == 1;
     __shared__ __attribute__((aligned(16))) uint4 in_s[TL::IN_U4];
     __shared__ __attribute__((aligned(16))) uint4 w_s[W_PHASE_U4];             // the 3 taps of one filter row
     __shared__ float out_s[CO_BLK * 65];                                       // fp32 staging of the pooled tile
@@ -115,7 +125,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x3_kernel(
     // XCD-aware ids: workgroups are placed round-robin over the 8 XCDs (id mod 8), each with its own L2.  The
     // 64-channel blocks of ONE tile walk read the same input patches, so they get ids 8 apart (same XCD, dispatched
     // together, same pace): the second block's reads hit that XCD's L2 instead of going to HBM again.
-    const int co_blocks_g = (Cout + CO_BLK - 1) / CO_BLK;
+    constexpr int CO_W = 32 * NT;                                  // output channels of a workgroup
+    const int co_blocks_g = (Cout + CO_W - 1) / CO_W;
     const int lin = blockIdx.x, within = lin % (8 * co_blocks_g);
     const int cb = within >> 3;
     const int walk = (lin / (8 * co_blocks_g)) * 8 + (within & 7);
@@ -123,8 +134,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x3_kernel(
     const int dx = i & 1, dy = (i >> 1) & 1, pp = i >> 2;
     // operand bases in 16-byte pieces
     const int a_base = ((wy * 4 + dy) * 2 + h) * TL::ICP + wx * 16 + 2 * pp + dx;
-    const int b_base = h * CO_BLK + i;
-    const uint4* wp_cb = reinterpret_cast<const uint4*>(wpack) + (size_t)cb * n_chunks * W_SLAB_U4;
+    // NT == 1: block cb is half (cb & 1) of the packed 64-channel filter block cb >> 1
+    const int b_base = h * CO_BLK + i + (NT == 1 ? (cb & 1) * 32 : 0);
+    const uint4* wp_cb = reinterpret_cast<const uint4*>(wpack) + (size_t)(NT == 1 ? cb >> 1 : cb) * n_chunks * W_SLAB_U4;
     const int HW = H * W;
 
     // staging plan: piece e of this thread = 8 consecutive channels (half lh) of patch position (r, col)
@@ -214,12 +226,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x3_kernel(
         const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
         const int y0 = ty * TL::TR, x0 = tx * TL::TC;
         f32x16 acc[2][NT];
+        f32x16 acc_lo[LO ? 2 : 1];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int n = 0; n < NT; ++n)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
+        if constexpr (LO) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc_lo[m][r] = 0.f;
+        }
 
         for (int chunk = 0; chunk < n_chunks; ++chunk) {
 #pragma unroll
@@ -258,18 +277,28 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x3_kernel(
 #pragma unroll
                         for (int m = 0; m < 2; ++m)
 #pragma unroll
-                            for (int n = 0; n < NT; ++n)
-                                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][TI[t]], bw[n][TJ[t]], acc[m][n], 0, 0, 0);
+                            for (int n = 0; n < NT; ++n) {
+                                if constexpr (LO) {
+                                    f32x16& dst = t < 5 ? acc_lo[m] : acc[m][n];
+                                    dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][TI[t]], bw[n][TJ[t]], dst, 0, 0, 0);
+                                } else {
+                                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][TI[t]], bw[n][TJ[t]], acc[m][n], 0, 0, 0);
+                                }
+                            }
                 }
             }
         }
 
         // ---- epilogue (same lane layout as conv.hip): registers 4q..4q+3 = the 2x2 quad of pooled column 2q + h
         const int py0 = y0 >> 1, px0 = x0 >> 1;
+        if constexpr (LO) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m) acc[m][0] += acc_lo[m];
+        }
         if constexpr (FULL) {
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
-                const int co = cb * CO_BLK + n * 32 + i;
+                const int co = cb * CO_W + n * 32 + i;
                 if (co >= Cout) continue;
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
@@ -473,6 +502,11 @@ __global__ __launch_bounds__(256, 4) void conv3x3_smallk_bf16x3_kernel(
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            // the five small partial products of all three k-steps first, then the three large ones: the sum of the
+            // small products is in place before the first large one, so only the last three of the 18 additions round
+            // at the size of the result (in k-step order all 18 did: 2^-20.97 of sum |x||w| + |b| at Cin = 1)
+            constexpr int TI[5] = {0, 1, 2, 0, 1}, TJ[5] = {2, 1, 0, 1, 0};
+            i16x8_t a0[3];
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
                 i16x8_t a[3];
@@ -483,11 +517,13 @@ __global__ __launch_bounds__(256, 4) void conv3x3_smallk_bf16x3_kernel(
                     const uint4 t = make_uint4(t0.x, t0.y, t1.x, t1.y);
                     a[sp] = *reinterpret_cast<const i16x8_t*>(&t);
                 }
-                constexpr int TI[6] = {0, 1, 2, 0, 1, 0}, TJ[6] = {2, 1, 0, 1, 0, 0};
+                a0[s] = a[0];
 #pragma unroll
-                for (int t = 0; t < 6; ++t)
+                for (int t = 0; t < 5; ++t)
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[TI[t]], bw[s][TJ[t]], acc, 0, 0, 0);
             }
+#pragma unroll
+            for (int s = 0; s < 3; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[s], bw[s][0], acc, 0, 0, 0);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int pos = (wy * 2 + m) * 16 + wx * 8 + 2 * q + h;
@@ -641,20 +677,20 @@ int i2l_conv_bf16x3_run(const float* x, const float* w, const float* bias, float
     const long long n_items_ll = (long long)tiles_per_img * B;
     if (n_items_ll > 0x7fffffffll) return I2L_ERR_UNSUPPORTED;
     const int n_items = (int)n_items_ll;
-    int items_per_wg = (int)((n_items_ll * co_blocks + 511) / 512);
+    // workgroup blocks of the launch: 64 output channels, 32 in the data-gradient flavour (NT = 1; two of them share a
+    // packed 64-channel filter block)
+    const int wg_blocks = full ? (Cout + 31) / 32 : co_blocks;
+    int items_per_wg = (int)((n_items_ll * wg_blocks + 511) / 512);
     // a launch with little more than one resident round of single tiles (block 3 of a 64-image training batch: 640):
     // one tile per workgroup fills the CUs more evenly than 320 walks of two (86 -> 73 us); measured worse above that
-    if (n_items_ll * co_blocks <= 768) items_per_wg = 1;
+    if (n_items_ll * wg_blocks <= 768) items_per_wg = 1;
     if (items_per_wg < 1) items_per_wg = 1;
     const int walks = i2l_cdiv(n_items, items_per_wg);
-    dim3 grid((unsigned)(i2l_cdiv(walks, 8) * 8 * co_blocks));       // ids decoded in the kernel (XCD-aware)
+    dim3 grid((unsigned)(i2l_cdiv(walks, 8) * 8 * wg_blocks));       // ids decoded in the kernel (XCD-aware)
 #define I2L_LAUNCH3(WXV)                                                                                              \
     do {                                                                                                              \
-        if (full && Cout == 32)                                                                                       \
+        if (full)                                                                                                     \
             hipLaunchKernelGGL((conv3x3_bf16x3_kernel<WXV, true, false, 1>), grid, dim3(256), 0, s, x, (const bf16_t*)wp, bias, y, \
-                               amax, Cin, H, W, Cout, Hp, Wp, tiles_x, n_chunks, tiles_per_img, n_items, items_per_wg, fix); \
-        else if (full)                                                                                                \
-            hipLaunchKernelGGL((conv3x3_bf16x3_kernel<WXV, true>), grid, dim3(256), 0, s, x, (const bf16_t*)wp, bias, y,  \
                                amax, Cin, H, W, Cout, Hp, Wp, tiles_x, n_chunks, tiles_per_img, n_items, items_per_wg, fix); \
         else if (amax)                                                                                                \
             hipLaunchKernelGGL((conv3x3_bf16x3_kernel<WXV, false, true>), grid, dim3(256), 0, s, x, (const bf16_t*)wp, bias, y, \
