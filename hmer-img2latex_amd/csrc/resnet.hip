@@ -810,6 +810,9 @@ extern "C" int i2l_conv_bn_act_bf16_fwd(const void* x, int x_is_nchw_f32, const 
         g.conv = 1; g.iH = H; g.iW = W; g.Cin = Cin; g.Ho = Ho; g.Wo = Wo; g.kw = kw; g.stride = stride; g.pad = pad;
         g.A = static_cast<const bf16_t*>(x); g.lda = 0;
     } else {
+        // the size query does not know x_is_nchw_f32: fp32 images with Cin % 64 == 0 (or a 1x1 / stride 1 conv) are sized there
+        // as the gathering paths, which take NHWC bf16 only -- refuse rather than write the column image past the workspace
+        if (workspace_bytes < i2l_align(M * Kp * sizeof(bf16_t))) return I2L_ERR_WORKSPACE;
         const size_t stem_lds = (size_t)Cin * kh * ((STEM_TW - 1) * stride + kw) * sizeof(float);
         if (x_is_nchw_f32 && stem_lds <= 48 * 1024 && Ho <= 65535 && B <= 65535)
             hipLaunchKernelGGL(im2col_stem_kernel, dim3(i2l_cdiv(Wo, STEM_TW), Ho, B), dim3(256), stem_lds, s,

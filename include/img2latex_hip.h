@@ -188,7 +188,11 @@ int i2l_linear_bias_act_bwd(const float* x, const float* w, const float* y, cons
  * Kernel choice: K = kh*kw*Cin a multiple of 64 with NHWC bf16 input runs the ring-buffered direct-to-LDS GEMM
  * (I2L_FLAG_RESNET_NO_RING: the single-buffered kernel); the 7x7 / stride 2 / pad 3 / 3 -> 64 stem on fp32 images runs
  * the fused stem kernel and needs no workspace (I2L_FLAG_RESNET_IM2COL_STEM: im2col image + GEMM); every other
- * shape goes through an im2col image in the workspace.  All paths compute the same bf16 x bf16 -> fp32 sums. */
+ * shape goes through an im2col image in the workspace.  All paths compute the same bf16 x bf16 -> fp32 sums.
+ * The size query is made for NHWC bf16 input and for the stem: fp32 images always go through the column image
+ * (B*Ho*Wo rows of kh*kw*Cin bf16, padded to 8, rounded up to 256 bytes) unless the fused stem takes them, and the
+ * call returns I2L_ERR_WORKSPACE when the workspace is smaller than that (Cin % 64 == 0, or a 1x1 / stride 1 conv
+ * with Cin % 8 == 0, where the query answers 256 bytes). */
 size_t i2l_conv_bf16_packed_bytes(int Cout, int Cin, int kh, int kw);
 int i2l_conv_bn_bf16_pack(const float* w, const float* bn_weight, const float* bn_bias, const float* bn_mean,
                           const float* bn_var, float bn_eps, void* packed, size_t packed_bytes, int Cout,
