@@ -750,7 +750,7 @@ constexpr GroupVariant grouped_variant(int flag) {
 constexpr GroupVariant group_variant(int i) {
     constexpr GroupVariant table[GROUP_VARIANTS] = {
         // sixteen members x sixteen rows, the per-step products on the matrix cores (decode_group16.inc.h)
-        {decode_group16_kernel, I2L_FLAG_DECODE_GROUP16, G16Q, G16NT, GRP16_LDS, GROUP16_XCHG_PER_GROUP},
+        {decode_group16_kernel<1>, I2L_FLAG_DECODE_GROUP16, G16Q, G16NT, GRP16_LDS, GROUP16_XCHG_PER_GROUP},
         // eight members x eight rows: one wave per SIMD and ~80 KB of LDS per CU, i.e. room for a conv workgroup beside it
         grouped_variant<8>(I2L_FLAG_DECODE_GROUP8),
         // four members x four rows (decode_group.inc.h)
@@ -760,7 +760,7 @@ constexpr GroupVariant group_variant(int i) {
 }
 
 struct Layout {
-    size_t P, Genc, WhhT[MAXL], WihT[MAXL], biasP[MAXL], WoutT, boutP, wpack16, gemm_ws, xchg, xchg_bytes, total;
+    size_t P, Genc, WhhT[MAXL], WihT[MAXL], biasP[MAXL], WoutT, boutP, wpack16, gemm_ws, xchg, xchg_bytes, state, state_bytes, total;
     int Vp;
 };
 
@@ -791,8 +791,15 @@ Layout make_layout(int rows, int V, int E, int H, int L) {
             const size_t x = group_xchg_bytes(i2l_cdiv(rows, g.rows), g.xchg_per_group);
             most = x > most ? x : most;
         }
+        // ... and of the two-tile launch (i2l_greedy_decode_halves), whose members exchange twice the granules
+        const size_t x2 = group_xchg_bytes(i2l_cdiv(rows, G16Q), G16Shape<2>::XCHG_PER_GROUP);
+        most = x2 > most ? x2 : most;
         o.xchg_bytes = GROUP_STATUS_BYTES + most;
         off += i2l_align(o.xchg_bytes);
+        // what this batch's rows carry from the launch of their first steps to the launch of the others (G16State)
+        o.state = off;
+        o.state_bytes = group16_state_bytes(rows);
+        off += i2l_align(o.state_bytes);
     }
     o.total = off;
     return o;
@@ -1040,6 +1047,82 @@ int launch_decode(const i2l_decoder_weights* w, const void* workspace, int rows,
     return I2L_OK;
 }
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// Two batches per 16-member grouped launch, a range of the steps of each (decode_group16_kernel<2>).
+// ---------------------------------------------------------------------------------------------
+namespace {
+int check_half(const i2l_decode_half* h) {
+    if (!h) return I2L_OK;
+    if (!h->workspace || !h->tok0 || !h->ids_out || h->rows <= 0 || h->steps <= 0) return I2L_ERR_ARG;
+    if (h->first_step < 0 || h->n_steps < 0 || h->first_step > h->steps - h->n_steps) return I2L_ERR_ARG;
+    if (h->steps > 65000) return I2L_ERR_UNSUPPORTED;         // the candidate granule carries step + 1 in 16 bits
+    return I2L_OK;
+}
+}  // namespace
+
+extern "C" int i2l_greedy_decode_halves(const i2l_decoder_weights* w, const i2l_decode_half* older,
+                                        const i2l_decode_half* newer, float temperature, int select, int stop, int end_id,
+                                        int flags, uint32_t* resident_flag, uint32_t resident_value, i2l_stream_t stream) {
+    // every refusal is decided here, before the first HIP call
+    int rc = check_weights(w);
+    if (rc != I2L_OK) return rc;
+    if (select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
+    if (stop != I2L_STOP_NONE && stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
+    if ((rc = check_half(older)) != I2L_OK || (rc = check_half(newer)) != I2L_OK) return rc;
+    const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
+    // with a sticky stop a range of steps has no fixed length; other dimensions have no 16-member kernel
+    if (stop != I2L_STOP_NONE || !group_shape_ok(V, H, L)) return I2L_ERR_UNSUPPORTED;
+    const i2l_decode_half* half[2] = {older && older->n_steps > 0 ? older : nullptr, newer && newer->n_steps > 0 ? newer : nullptr};
+    hipStream_t s = i2l_s(stream);
+    if (!half[0] && !half[1]) {                               // no step to run: nothing waits for a partner
+        if (resident_flag) {
+            hipLaunchKernelGGL(publish_value32_kernel, dim3(1), dim3(1), 0, s, resident_flag, resident_value);
+            I2L_CHECK_LAUNCH();
+        }
+        return I2L_OK;
+    }
+    // weights, status block and exchange region: the newer batch's workspace (the one a pipeline has just prepared and
+    // cleared), the older one's when there is no newer batch; the region must hold the groups of BOTH
+    const i2l_decode_half* home = half[1] ? half[1] : half[0];
+    const Layout lo = make_layout(home->rows, V, E, H, L);
+    int n_groups = 0, most_steps = 0;
+    for (int k = 0; k < 2; ++k)
+        if (half[k]) {
+            n_groups = std::max(n_groups, i2l_cdiv(half[k]->rows, G16Q));
+            most_steps = std::max(most_steps, half[k]->n_steps);
+        }
+    if (!lo.wpack16 || GROUP_STATUS_BYTES + group_xchg_bytes(n_groups, G16Shape<2>::XCHG_PER_GROUP) > lo.xchg_bytes)
+        return I2L_ERR_UNSUPPORTED;
+    char* base = static_cast<char*>(const_cast<void*>(home->workspace));
+
+    GroupParams gp{};
+    gp.w = step_weights(lo, base, V, H, L);
+    gp.n_groups = n_groups;
+    gp.temperature = temperature; gp.use_temp = (temperature != 1.0f) ? 1 : 0; gp.stop = stop; gp.end_id = end_id;
+    char* xb = base + lo.xchg;
+    gp.status = reinterpret_cast<unsigned*>(xb);
+    gp.xchg = reinterpret_cast<u64_t*>(xb + GROUP_STATUS_BYTES);
+    gp.opts = group_opts(most_steps, flags);
+    gp.resident_flag = resident_flag; gp.resident_value = resident_value;
+    for (int k = 0; k < 2; ++k) {
+        HalfTile& t = gp.tile[k];
+        if (!half[k]) continue;                               // n = 0: absent
+        const i2l_decode_half& h = *half[k];
+        const Layout hl = make_layout(h.rows, V, E, H, L);
+        char* hb = static_cast<char*>(const_cast<void*>(h.workspace));
+        t.Genc = reinterpret_cast<const float*>(hb + hl.Genc);
+        t.tok0 = h.tok0; t.ids = h.ids_out; t.B = h.rows; t.T = h.steps; t.t0 = h.first_step; t.n = h.n_steps;
+        t.state_in = h.first_step > 0 ? hb + hl.state : nullptr;
+        t.state_out = h.first_step + h.n_steps < h.steps ? hb + hl.state : nullptr;
+    }
+    static std::atomic<unsigned> attr{};
+    if (!i2l_lds_attr(reinterpret_cast<const void*>(decode_group16_kernel<2>), G16Shape<2>::LDS, attr)) return I2L_ERR_UNSUPPORTED;
+    if (!(flags & I2L_FLAG_DECODE_REGION_CLEARED) && hipMemsetAsync(xb, 0, lo.xchg_bytes, s) != hipSuccess) return I2L_ERR_LAUNCH;
+    hipLaunchKernelGGL(decode_group16_kernel<2>, dim3(group_grid(n_groups, G16Q)), dim3(G16NT), G16Shape<2>::LDS, s, gp);
+    I2L_CHECK_LAUNCH();
+    return I2L_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Step-batched greedy decode (decode_batched.inc.h): L + 2 plain launches per step on the caller's stream.
@@ -1333,6 +1416,13 @@ extern "C" size_t i2l_decoder_group_status_offset(int rows, int vocab, int embed
 // kernel -- or the caller, earlier and on another stream, with I2L_FLAG_DECODE_REGION_CLEARED.
 extern "C" size_t i2l_decoder_group_region_bytes(int rows, int vocab, int embed, int hidden, int layers) {
     return make_layout(rows, vocab, embed, hidden, layers).xchg_bytes;
+}
+// The state block of i2l_greedy_decode_halves inside the workspace: 0 bytes where these dimensions have no such launch.
+extern "C" size_t i2l_decoder_group_state_offset(int rows, int vocab, int embed, int hidden, int layers) {
+    return make_layout(rows, vocab, embed, hidden, layers).state;
+}
+extern "C" size_t i2l_decoder_group_state_bytes(int rows, int vocab, int embed, int hidden, int layers) {
+    return make_layout(rows, vocab, embed, hidden, layers).state_bytes;
 }
 
 #ifdef I2L_GROUP_STAMPS

@@ -64,6 +64,18 @@ struct GroupShape {
     static constexpr size_t XCHG_PER_GROUP = (size_t)2 * M * GRAN * 8;   // [2 parities][M][GRAN]
 };
 
+// One row tile of decode_group16_kernel<2> (i2l_greedy_decode_halves): 16 rows per group of ITS OWN batch, a range of
+// that batch's steps.  n == 0: the tile is absent (it still takes part in the exchanges, see the kernel).
+struct HalfTile {
+    const float* Genc;    // that batch's image-side gate rows
+    const int32_t* tok0;
+    int32_t* ids;         // [B][T]
+    int B, T;             // rows and steps of the whole batch
+    int t0, n;            // this launch runs steps t0 .. t0 + n - 1
+    const void* state_in; // t0 > 0: the state block the launch of the earlier steps saved (group16_state_bytes)
+    void* state_out;      // t0 + n < T: where to save it
+};
+
 struct GroupParams {
     StepWeights w;
     int B, T, n_groups;
@@ -78,6 +90,7 @@ struct GroupParams {
     GroupOpts opts;       // poll limits, exchange flavour (group_common.inc.h)
     unsigned* resident_flag;   // may be null: receives resident_value once every group of the launch is resident
     unsigned resident_value;
+    HalfTile tile[2];     // decode_group16_kernel<2> only (it ignores B, T, tok0, ids and w.Genc above)
 };
 
 constexpr int DPP_SHL12 = 0x10C;

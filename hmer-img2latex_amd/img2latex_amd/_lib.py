@@ -54,6 +54,12 @@ class DecoderWeights(ctypes.Structure):
                 ("b_out", c_void_p), ("vocab", c_int), ("embed", c_int), ("hidden", c_int), ("layers", c_int)]
 
 
+class DecodeHalf(ctypes.Structure):
+    """struct i2l_decode_half: one batch's share of an i2l_greedy_decode_halves launch."""
+    _fields_ = [("workspace", c_void_p), ("rows", c_int), ("steps", c_int), ("first_step", c_int), ("n_steps", c_int),
+                ("tok0", c_void_p), ("ids_out", c_void_p)]
+
+
 class DecoderGrads(ctypes.Structure):
     """struct i2l_decoder_grads."""
     _fields_ = [("embedding", c_void_p), ("w_ih", POINTER(c_void_p)), ("w_hh", POINTER(c_void_p)),
@@ -98,6 +104,8 @@ _SIGNATURES = {
     "i2l_greedy_decode_ex": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_int, c_void_p, ctypes.c_uint32, c_void_p]),
+    "i2l_greedy_decode_halves": (c_int, [POINTER(DecoderWeights), POINTER(DecodeHalf), POINTER(DecodeHalf), c_float, c_int,
+                                         c_int, c_int, c_int, c_void_p, ctypes.c_uint32, c_void_p]),
     "i2l_decode_batched_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "i2l_greedy_decode_batched": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -179,6 +187,8 @@ _SIGNATURES.update({
     "i2l_global_avgpool_bwd_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "i2l_decoder_group_status_offset": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "i2l_decoder_group_region_bytes": (c_size_t, [c_int] * 5),
+    "i2l_decoder_group_state_offset": (c_size_t, [c_int] * 5),
+    "i2l_decoder_group_state_bytes": (c_size_t, [c_int] * 5),
     "i2l_resample_ksize": (c_int, [c_int, c_int, c_int]),
     "i2l_resample_coeffs": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
     "i2l_resample_coeffs_batch": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),

@@ -9,7 +9,7 @@ step math runs in libimg2latex_hip.so (csrc/decode.hip).
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -44,6 +44,20 @@ class Attention(nn.Module):
             self.attn.bias.detach().data_ptr(), self.v.weight.detach().contiguous().data_ptr(), ctx.data_ptr(),
             B, S, self.hidden_dim, E, _lib.stream_ptr()), "attention_context_fwd")
         return ctx
+
+
+class DecodeHalf(NamedTuple):
+    """One batch's share of ``LSTMDecoder.decode_halves``: the workspace ``prepare`` built for its rows (``ws``, with
+    ``version`` = the weights it was built for, ``LSTMDecoder._ws_key[2]`` right after that prepare), the batch's shape,
+    the range of steps to run and where the ids go."""
+    ws: torch.Tensor
+    version: tuple
+    rows: int
+    steps: int
+    first_step: int
+    n_steps: int
+    tok0: torch.Tensor
+    ids: torch.Tensor
 
 
 class LSTMDecoder(nn.Module):
@@ -230,6 +244,43 @@ class LSTMDecoder(nn.Module):
         _lib.mark("decode")
         del keep
         return ids, logits, ((h, c) if want_state else None)
+
+    def halves_supported(self, stop: int = _lib.STOP_NONE) -> bool:
+        """True where ``decode_halves`` has a kernel: the 16-member grouped decode's dimensions, no sticky stop."""
+        return stop == _lib.STOP_NONE and _lib.lib().i2l_decoder_group_state_bytes(
+            16, self.vocab_size, self.embedding_dim, self.hidden_dim, self.lstm_layers) != 0
+
+    def decode_halves(self, older: Optional["DecodeHalf"], newer: Optional["DecodeHalf"], temperature: float = 1.0,
+                      select: int = _lib.SELECT_LOGITS, stop: int = _lib.STOP_NONE, end_id: int = -1, flags: int = 0,
+                      resident=None) -> None:
+        """One 16-member grouped launch over TWO batches (i2l_greedy_decode_halves): ``older`` and ``newer`` each name a
+        prepared workspace, a range of that batch's steps and the (rows, steps) ids tensor the range is written to; either
+        may be None.  A batch is run as steps [0, n) in one call and [n, steps) in the next one on the same stream; its ids
+        equal ``run_steps(flags=FLAG_DECODE_GROUP16)`` bit for bit.  The launch takes the weight images, the status words
+        (``group_status`` after a ``prepare`` of that slot) and the exchange region from ``newer``'s workspace -- ``older``'s
+        when there is no newer batch -- so the two workspaces must hold images of the SAME weights: refused otherwise."""
+        halves = [h for h in (older, newer) if h is not None]
+        if not halves:
+            raise RuntimeError("img2latex_amd: decode_halves needs at least one batch")
+        if len({h.version for h in halves}) != 1 or halves[0].version != self._weights_version():
+            raise RuntimeError("img2latex_amd: decode_halves: the two workspaces were prepared for different weights")
+        w, keep = self._weights_struct()
+        structs = []
+        for h in (older, newer):
+            if h is None:
+                structs.append(None)
+                continue
+            if tuple(h.ids.shape) != (h.rows, h.steps) or h.ids.dtype != torch.int32 or not h.ids.is_contiguous():
+                raise RuntimeError(f"decode_halves: ids must be contiguous int32 ({h.rows},{h.steps})")
+            structs.append(_lib.DecodeHalf(h.ws.data_ptr(), h.rows, h.steps, h.first_step, h.n_steps,
+                                           _lib.require_gpu(h.tok0, "tok0", torch.int32).data_ptr(), h.ids.data_ptr()))
+        _lib.check(_lib.lib().i2l_greedy_decode_halves(
+            ctypes.byref(w), None if structs[0] is None else ctypes.byref(structs[0]),
+            None if structs[1] is None else ctypes.byref(structs[1]), float(temperature), select, stop, int(end_id),
+            int(flags) | int(self.kernel_flags), None if resident is None else resident[0].data_ptr(),
+            0 if resident is None else int(resident[1]) & 0xFFFFFFFF, _lib.stream_ptr()), "greedy_decode_halves")
+        _lib.mark("decode")
+        del keep
 
     def sample_steps(self, encoder_output: torch.Tensor, steps: int, tok0: torch.Tensor, temperature: float,
                      top_k: int, top_p: float, seed: int, stop: int = _lib.STOP_STICKY, end_id: int = -1,

@@ -14,6 +14,11 @@ persistent decode loop of batch i runs on another.  Two ways of sharing the chip
 * by compute-unit count (r01, ``rows_per_workgroup = 2``): a row-per-workgroup decode on 128 units, the encoder on the
   other 128.  2.6x slower than the grouped kernels; kept for decoders the grouped kernels do not cover.
 
+Split decode (``split_decode``, on by default where it applies): the 16-member grouped launch of submit(j) runs the SECOND
+half of the steps of batch j - 1 and the FIRST half of the steps of batch j as two row tiles of one kernel
+(LSTMDecoder.decode_halves) -- the per-step exchange chain, which bounds the decode, is paid once for 32 rows per group, and
+every launch is half as many steps long.  Same streams, slots and depth; a batch's ids come one launch later.
+
 Nothing is skipped: every batch still runs the full encoder, decoder prepare, decode loop
 and id copy; results equal ``Seq2SeqModel._greedy_search`` batch by batch.
 """
@@ -25,6 +30,17 @@ from typing import Deque, List, Optional, Tuple
 import torch
 
 from . import _lib
+from .model.lstm_decoder import DecodeHalf
+
+
+class _Batch:
+    """One submitted batch until it is collected.  ``done`` is None while the launch of its last steps is still to come
+    (split decode): ``half`` then holds what that launch needs."""
+    __slots__ = ("no", "done", "host", "enc", "text", "half", "slot", "ids")
+
+    def __init__(self, no, host, enc, slot):
+        self.no, self.host, self.enc, self.slot = no, host, enc, slot
+        self.done = self.text = self.half = self.ids = None
 
 
 class GreedyPipeline:
@@ -40,7 +56,8 @@ class GreedyPipeline:
                  decode_flags: int = 0, encoder_flags: int = 0, decode_priority: int = 0, encoder_streams: int = 1,
                  encoder_priority: int = 0, hold_encoder: Optional[bool] = None, wait_timeout_us: float = 20000.0,
                  clear_early: bool = True,
-                 stop: int = _lib.STOP_NONE, select: int = _lib.SELECT_LOGITS, detokenize=None):
+                 stop: int = _lib.STOP_NONE, select: int = _lib.SELECT_LOGITS, detokenize=None,
+                 split_decode: Optional[bool] = None):
         self.model = model
         self.start, self.end, self.max_length, self.temperature = start_token_id, end_token_id, max_length, temperature
         dev = next(model.parameters()).device
@@ -92,7 +109,23 @@ class GreedyPipeline:
         self.trace: Optional[list] = None
         self.trace_every = 1         # with `trace`: batches j and j + 1 for every j that is a multiple of this (1 = every batch); a timing
                                      # event is a marker packet in the queue, and four per batch cost the pipeline ~1 % (r04)
-        self._inflight: Deque[Tuple[torch.cuda.Event, torch.Tensor, torch.Tensor]] = deque()
+        self._inflight: Deque[_Batch] = deque()
+        # split decode: None = on exactly where it applies -- the 16-member grouped decode (as i2l_greedy_decode_ex picks it: no
+        # rows-per-workgroup request, at least 8 steps, not the step-batched route), no sticky stop (a half would have no fixed
+        # length), one decode stream (the two halves of a batch are ordered by it), dimensions the library has the kernel for.
+        # Everything else runs the code path below untouched.
+        dec = model.decoder
+        can_split = (bool(self.decode_flags & _lib.FLAG_DECODE_GROUP16) and self.stop == _lib.STOP_NONE
+                     and len(self.dec_streams) == 1 and self.rows_per_workgroup == 0 and max_length >= 8
+                     and not (int(getattr(dec, "kernel_flags", 0)) & _lib.FLAG_DECODE_BATCHED)
+                     and hasattr(dec, "halves_supported") and dec.halves_supported(self.stop))
+        if split_decode and not can_split:
+            raise RuntimeError("img2latex_amd: GreedyPipeline(split_decode=True) needs decode_flags with FLAG_DECODE_GROUP16, "
+                               "rows_per_workgroup=0, stop=STOP_NONE, one decode stream, max_length >= 8 and a decoder the "
+                               "16-member grouped kernel takes")
+        self.split_decode = can_split if split_decode is None else bool(split_decode)
+        self._open: Optional[_Batch] = None          # split decode: the batch whose second half the next launch runs
+        self._tok0: dict = {}                        # split decode: the START column per batch size
         self.copy_stream = torch.cuda.Stream(device=dev)     # the ids' device -> host copies (off the decode stream: +1 %)
         self._batch_no = 0
         self._slots = self.depth + 1                 # decoder workspaces in rotation: a slot is rewritten only after its batch was collected
@@ -161,6 +194,9 @@ class GreedyPipeline:
                 enc.record_stream(dec_stream)
                 if rec is not None:
                     rec["dec_start"].record(dec_stream)
+                if self.split_decode:
+                    self._submit_split(enc, prepared, slot, seq, dflags, rec, dec_stream)
+                    return
                 ids, _ = self.model.greedy_ids(enc, self.start, self.end, self.max_length, self.temperature,
                                                stop=self.stop, select=self.select,
                                                rows_per_workgroup=self.rows_per_workgroup, flags=dflags,
@@ -168,35 +204,95 @@ class GreedyPipeline:
                                                resident=(self._resident, seq) if self.hold_encoder else None)
                 if rec is not None:
                     rec["dec_end"].record(dec_stream)
-                host = self._host_buffer(ids.shape)
-                text = dev_text = None
-                if self.detok is not None:
-                    key = (slot, tuple(ids.shape))
-                    if key not in self._text_dev:
-                        self._text_dev = {k: v for k, v in self._text_dev.items() if k[0] != slot}
-                        self._text_dev[key] = self.detok.buffers(*ids.shape)
-                    dev_text = self.detok.launch(ids, self.end, self._text_dev[key])
-                    text = self._text_buffer(dev_text)
-                if self.copy_stream is None:
-                    host.copy_(ids, non_blocking=True)
-                    if text is not None:
-                        text[0].copy_(dev_text[0], non_blocking=True)
-                        text[1].copy_(dev_text[1], non_blocking=True)
-                    done = torch.cuda.Event()
-                    done.record(dec_stream)
-                else:                                              # the id copy leaves the decode stream: decode(i + 1) need not wait for it
-                    decoded = torch.cuda.Event()
-                    decoded.record(dec_stream)
-                    self.copy_stream.wait_event(decoded)
-                    with torch.cuda.stream(self.copy_stream):
-                        host.copy_(ids, non_blocking=True)
-                        if text is not None:
-                            text[0].copy_(dev_text[0], non_blocking=True)
-                            text[1].copy_(dev_text[1], non_blocking=True)
-                        done = torch.cuda.Event()
-                        done.record(self.copy_stream)
-                    ids.record_stream(self.copy_stream)
-        self._inflight.append((done, host, enc, text))
+                b = _Batch(seq - 1, self._host_buffer(ids.shape), enc, slot)
+                b.ids = ids
+                self._finish(b, dec_stream)
+        self._inflight.append(b)
+
+    def _finish(self, b: _Batch, dec_stream) -> None:
+        """Behind the launch that wrote the batch's last ids, on the decode stream: detokenize, the copies to pinned memory
+        (on the copy stream) and the batch's `done` event."""
+        ids, host, slot = b.ids, b.host, b.slot
+        text = dev_text = None
+        if self.detok is not None:
+            key = (slot, tuple(ids.shape))
+            if key not in self._text_dev:
+                self._text_dev = {k: v for k, v in self._text_dev.items() if k[0] != slot}
+                self._text_dev[key] = self.detok.buffers(*ids.shape)
+            dev_text = self.detok.launch(ids, self.end, self._text_dev[key])
+            text = self._text_buffer(dev_text)
+        if self.copy_stream is None:
+            host.copy_(ids, non_blocking=True)
+            if text is not None:
+                text[0].copy_(dev_text[0], non_blocking=True)
+                text[1].copy_(dev_text[1], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(dec_stream)
+        else:                                              # the id copy leaves the decode stream: decode(i + 1) need not wait for it
+            decoded = torch.cuda.Event()
+            decoded.record(dec_stream)
+            self.copy_stream.wait_event(decoded)
+            with torch.cuda.stream(self.copy_stream):
+                host.copy_(ids, non_blocking=True)
+                if text is not None:
+                    text[0].copy_(dev_text[0], non_blocking=True)
+                    text[1].copy_(dev_text[1], non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(self.copy_stream)
+            ids.record_stream(self.copy_stream)
+        b.text, b.done, b.half, b.ids = text, done, None, None
+
+    def _submit_split(self, enc, prepared, slot, seq, dflags, rec, dec_stream) -> None:
+        """The decode side of submit() with split decode (the decode stream is current): ONE launch runs the second half of
+        the steps of the batch before this one, if it is still waiting for it, and the first half of this batch's.
+        Slot lifetime: that launch reads the older batch's slot workspace (Genc, state block) and this batch's (weights,
+        exchange region); the launch of submit(j + 1) reads batch j's again.  A slot is rewritten by the batch `depth + 1`
+        submits later, and submit() admits a batch only while fewer than `depth` are in flight, so by then the slot's
+        earlier batch has been collected -- behind the launch that ran its last steps."""
+        dec = self.model.decoder
+        no, T = seq - 1, self.max_length
+        assert not self._inflight or self._inflight[0].no > no - self._slots, "a slot workspace is still in use"
+        w, keep, enc_c, ws = prepared
+        rows = enc_c.shape[0]
+        if rows not in self._tok0:
+            self._tok0[rows] = torch.full((rows,), int(self.start), dtype=torch.int32, device=self.device)
+        ids = torch.empty((rows, T), dtype=torch.int32, device=self.device)
+        first = (T + 1) // 2
+        b = _Batch(no, self._host_buffer(ids.shape), enc, slot)
+        b.ids = ids
+        newer = DecodeHalf(ws, dec._ws_key[2], rows, T, 0, first, self._tok0[rows], ids)
+        older, prev = None, self._open
+        if prev is not None:
+            dims = (dec.vocab_size, dec.embedding_dim, dec.hidden_dim, dec.lstm_layers)
+            nb = _lib.lib().i2l_decoder_group_region_bytes
+            if prev.half.version == newer.version and nb(prev.half.rows, *dims) <= nb(rows, *dims):
+                older = prev.half
+            else:                   # other weights, or more groups than this batch's exchange region holds: its half alone, first
+                self._launch_tail(prev, dec_stream)
+        kw = dict(temperature=self.temperature, select=self.select, stop=self.stop, end_id=self.end)
+        dec.decode_halves(older, newer, flags=dflags, resident=(self._resident, seq) if self.hold_encoder else None, **kw)
+        if rec is not None:
+            rec["dec_end"].record(dec_stream)
+        if older is not None:
+            self._finish(prev, dec_stream)
+        self._open = None
+        if first < T:
+            b.half = newer._replace(first_step=first, n_steps=T - first)
+            self._open = b
+        else:
+            self._finish(b, dec_stream)
+        self._inflight.append(b)
+
+    def _launch_tail(self, b: _Batch, dec_stream) -> None:
+        """The second half of a batch ALONE (the other tile absent): no later submit came -- drain, an odd count, a
+        generator's last batch -- or the next batch cannot share a launch with it.  Its slot's exchange region was used by
+        the launch of its first half, so the launch clears it itself."""
+        flags = self.decode_flags & ~_lib.FLAG_DECODE_REGION_CLEARED
+        self.model.decoder.decode_halves(b.half, None, temperature=self.temperature, select=self.select, stop=self.stop,
+                                         end_id=self.end, flags=flags)
+        self._finish(b, dec_stream)
+        if self._open is b:
+            self._open = None
 
     def close(self) -> None:
         """Give the decoder workspaces of this pipeline's slots back (they live in the decoder's cache under this
@@ -210,6 +306,7 @@ class GreedyPipeline:
             # submit), behind that batch's `done`: the streams themselves are synchronised, after the batches are dropped,
             # so that close() leaves every one of them idle
             inflight.clear()
+            self._open = None                        # (split decode: a first half without its second is dropped like the rest)
             for s in self.enc_streams + self.dec_streams + [self.copy_stream]:
                 if s is not None:
                     s.synchronize()
@@ -269,7 +366,11 @@ class GreedyPipeline:
         """(ids in pinned host memory, pinned (bytes, offsets) or None) of the oldest batch: the ONE host wait per batch."""
         if not self._inflight:
             return None
-        done, host, enc, text = self._inflight.popleft()
+        b = self._inflight.popleft()
+        if b.done is None:                           # split decode: no later submit has launched this batch's second half
+            with torch.no_grad(), torch.cuda.stream(self.dec_streams[0]):
+                self._launch_tail(b, self.dec_streams[0])
+        done, host, enc, text = b.done, b.host, b.enc, b.text
         done.synchronize()
         if _lib.ids_timed_out(host):
             # a grouped decode needs its members resident together; on a GPU shared with other work a bounded wait can

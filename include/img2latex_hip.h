@@ -807,6 +807,42 @@ int i2l_teacher_forced_eval(const float* logits, const int32_t* targets, int bat
 size_t i2l_decoder_group_status_offset(int rows, int vocab, int embed, int hidden, int layers);
 size_t i2l_decoder_group_region_bytes(int rows, int vocab, int embed, int hidden, int layers);   /* bytes of that region (status + exchange granules) */
 
+/* TWO batches in one 16-member grouped launch, a range of the steps of each (GreedyPipeline's split decode): the rows of
+ * both are row tiles of the same matrix-core operands and share the launch's per-step exchanges, so a launch of n steps
+ * advances two batches by n steps for much less than two launches would take.  A batch is decoded by two such calls on
+ * one stream: steps [0, n) -- which leaves the LSTM state, the last token and the stop mask of every row in a state block
+ * inside the batch's workspace (i2l_decoder_group_state_offset / _bytes) -- then steps [n, steps), which resumes from it;
+ * the ids of a batch are bit-equal to i2l_greedy_decode_ex with I2L_FLAG_DECODE_GROUP16 however its steps are cut and
+ * whatever batch sits in the other tile.
+ *   workspace    of i2l_decoder_prepare() for this batch's `rows` (Genc, state block); alive and unchanged until the
+ *                call that runs the batch's last steps has completed
+ *   rows, steps  of the whole batch; ids_out is (rows, steps) int32, the call writes columns first_step .. + n_steps - 1
+ *   first_step, n_steps   the range run by this call; n_steps == 0: as if the half were absent
+ *   tok0         (rows) int32 first input tokens (read when first_step == 0)
+ * `older` / `newer`: either may be NULL (a launch with one tile: the first or the last of a sequence).  The weights, the
+ * status words and the exchange region are those of `newer`'s workspace (of `older`'s when newer is absent): both batches
+ * must belong to the SAME weights, which the caller guarantees, and that region must be large enough for the groups of
+ * both (I2L_ERR_UNSUPPORTED otherwise: equal row counts always are).  temperature, select (I2L_SELECT_LOGITS / _SOFTMAX),
+ * end_id, flags (I2L_FLAG_AGENT_SCOPE_EXCHANGE, I2L_FLAG_DECODE_REGION_CLEARED, the test hooks) and the residency signal:
+ * as i2l_greedy_decode_ex.  Supported where that entry runs the 16-member kernel (layers 1, hidden 256, vocab <= 512)
+ * and only with stop == I2L_STOP_NONE -- under a sticky stop a range of steps has no fixed length --; everything else
+ * returns I2L_ERR_UNSUPPORTED before anything is enqueued and callers keep i2l_greedy_decode_ex.  If a bounded wait
+ * expires, every id of the affected rows of BOTH batches is -3; a batch whose first range failed gets -3 from the call
+ * that was to resume it, which then runs the other batch alone. */
+typedef struct {
+    const void* workspace;
+    int rows, steps;
+    int first_step, n_steps;
+    const int32_t* tok0;
+    int32_t* ids_out;
+} i2l_decode_half;
+int i2l_greedy_decode_halves(const i2l_decoder_weights* w, const i2l_decode_half* older, const i2l_decode_half* newer,
+                             float temperature, int select, int stop, int end_id, int flags,
+                             uint32_t* resident_flag, uint32_t resident_value, i2l_stream_t stream);
+/* The state block of i2l_greedy_decode_halves inside the decoder workspace (bytes 0: these dimensions have no such launch). */
+size_t i2l_decoder_group_state_offset(int rows, int vocab, int embed, int hidden, int layers);
+size_t i2l_decoder_group_state_bytes(int rows, int vocab, int embed, int hidden, int layers);
+
 /* ------------------------------------------------------------------------
  * Image preprocessing (reference img2latex/data/utils.py:18-90, data/transforms.py:26-56), SURVEY section 8(f)-3
  * ---------------------------------------------------------------------- */
