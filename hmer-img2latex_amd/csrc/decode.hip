@@ -242,6 +242,7 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned row
 #include "decode_group16.inc.h"
 #include "beam_group.inc.h"
 #include "decode_batched.inc.h"
+#include "sample_batched.inc.h"
 #include "beam_batched.inc.h"
 
 // KR / KL > 0 (fast path for R == 1, L == 1, H <= 256: thread j owns hidden unit j for the whole loop):
@@ -1141,19 +1142,14 @@ template <int TB>
 void launch_batched_logits(const BatchedParams& p, int t, hipStream_t s) {
     hipLaunchKernelGGL(logits_mfma_kernel<TB>, dim3(p.w.Vp / DB_COLS, i2l_cdiv(p.B, TB)), dim3(DB_NT), 0, s, p, t);
 }
-}  // namespace
 
-extern "C" int i2l_greedy_decode_batched(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
-                                         const int32_t* tok0, const int32_t* forced, const float* h0, const float* c0,
-                                         float temperature, int select, int stop, int end_id, int32_t* ids_out,
-                                         float* logits_out, float* h_out, float* c_out, void* scratch,
-                                         size_t scratch_bytes, int flags, uint32_t* resident_flag,
-                                         uint32_t resident_value, i2l_stream_t stream) {
-    (void)flags;
-    // every refusal is decided here, before the first HIP call
-    int rc = check_weights(w);
-    if (rc != I2L_OK) return rc;
-    if (select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
+// the loop of both step-batched entries; `sample` != null: sample_batched_kernel selects (select is I2L_SELECT_SAMPLE).
+// The caller has checked the weights and its own arguments; every other refusal is decided here, before the first HIP call.
+int launch_batched(const i2l_decoder_weights* w, const void* workspace, int rows, int steps, const int32_t* tok0,
+                   const int32_t* forced, const float* h0, const float* c0, float temperature, int select, int stop,
+                   int end_id, const SampleRule* sample, int32_t* ids_out, float* logits_out, float* h_out, float* c_out,
+                   void* scratch, size_t scratch_bytes, uint32_t* resident_flag, uint32_t resident_value,
+                   i2l_stream_t stream) {
     if (!workspace || !tok0 || rows <= 0 || steps <= 0) return I2L_ERR_ARG;
     if ((h0 == nullptr) != (c0 == nullptr)) return I2L_ERR_ARG;
     if (stop != I2L_STOP_NONE && stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
@@ -1195,13 +1191,63 @@ extern "C" int i2l_greedy_decode_batched(const i2l_decoder_weights* w, const voi
         if (tb_logits == 16) launch_batched_logits<16>(p, t, s);
         else if (tb_logits == 32) launch_batched_logits<32>(p, t, s);
         else launch_batched_logits<64>(p, t, s);
-        hipLaunchKernelGGL(select_batched_kernel, dim3(sel_grid), dim3(DB_NT), 0, s, p, t);
+        if (sample) hipLaunchKernelGGL(sample_batched_kernel, dim3(rows), dim3(NT), 0, s, p, *sample, t);
+        else hipLaunchKernelGGL(select_batched_kernel, dim3(sel_grid), dim3(DB_NT), 0, s, p, t);
         I2L_CHECK_LAUNCH();
     }
     if (h_out || c_out) {
         hipLaunchKernelGGL(state_out_batched_kernel, dim3(copy_grid), dim3(DB_NT), 0, s, p, h_out, c_out);
         I2L_CHECK_LAUNCH();
     }
+    return I2L_OK;
+}
+}  // namespace
+
+extern "C" int i2l_greedy_decode_batched(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                         const int32_t* tok0, const int32_t* forced, const float* h0, const float* c0,
+                                         float temperature, int select, int stop, int end_id, int32_t* ids_out,
+                                         float* logits_out, float* h_out, float* c_out, void* scratch,
+                                         size_t scratch_bytes, int flags, uint32_t* resident_flag,
+                                         uint32_t resident_value, i2l_stream_t stream) {
+    (void)flags;
+    int rc = check_weights(w);
+    if (rc != I2L_OK) return rc;
+    if (select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
+    return launch_batched(w, workspace, rows, steps, tok0, forced, h0, c0, temperature, select, stop, end_id, nullptr,
+                          ids_out, logits_out, h_out, c_out, scratch, scratch_bytes, resident_flag, resident_value, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Step-batched sampling (sample_batched.inc.h): the same loop, sample_batched_kernel as the last launch of a step.
+// ---------------------------------------------------------------------------------------------
+extern "C" int i2l_sample_decode_batched(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                         const int32_t* tok0, const float* h0, const float* c0, float temperature,
+                                         int top_k, float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out,
+                                         float* probs_out, float* h_out, float* c_out, void* scratch,
+                                         size_t scratch_bytes, int flags, i2l_stream_t stream) {
+    (void)flags;
+    // every refusal is decided on the host, here and in launch_batched, before the first HIP call
+    int rc = check_weights(w);
+    if (rc != I2L_OK) return rc;
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || (top_k == 0 && top_p == 0.f)) return I2L_ERR_ARG;
+    if (rows <= 0 || steps <= 0) return I2L_ERR_ARG;
+    if (w->vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
+    const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
+    return launch_batched(w, workspace, rows, steps, tok0, nullptr, h0, c0, temperature, I2L_SELECT_SAMPLE, stop, end_id,
+                          &rule, ids_out, nullptr, h_out, c_out, scratch, scratch_bytes, nullptr, 0, stream);
+}
+
+extern "C" int i2l_sample_logits(const float* logits, int ld, int rows, int vocab, float temperature, int top_k,
+                                 float top_p, uint64_t seed, int step, int32_t* ids_out, float* probs_out,
+                                 i2l_stream_t stream) {
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || (top_k == 0 && top_p == 0.f)) return I2L_ERR_ARG;
+    if (rows <= 0 || vocab <= 0 || ld < vocab || step < 0) return I2L_ERR_ARG;
+    if (vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
+    if (!logits || !ids_out) return I2L_ERR_ARG;
+    const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
+    hipLaunchKernelGGL(sample_logits_kernel, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab, temperature,
+                       (temperature != 1.0f) ? 1 : 0, rule, (unsigned)step, ids_out);
+    I2L_CHECK_LAUNCH();
     return I2L_OK;
 }
 

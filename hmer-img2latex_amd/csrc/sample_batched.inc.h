@@ -1,0 +1,233 @@
+// Top-k / top-p sampling for the step-batched decode (included by decode.hip inside its anonymous namespace, after
+// decode_batched.inc.h).  Reference predictor.py:295-331; the rule is decode_kernel<R, 0, 0, true>'s, restated so that
+// no column walks the whole vocabulary:
+//
+//   sample_row            one 256-thread workgroup, one row: softmax(x / T) in fp32, the top-k mask from a RADIX SELECTION
+//                         of the k-th largest probability (four 8-bit digits of the bit pattern, a 256-bin count each),
+//                         the top-p mask from a BITONIC SORT of (bit pattern, index) keys and a scan of the sorted
+//                         masses, the draw from a scan of the final distribution in index order.
+//   sample_batched_kernel the last launch of a step of i2l_sample_decode_batched, in select_batched_kernel's place.
+//   sample_logits_kernel  the same row function over a caller's logits (i2l_sample_logits).
+//
+// Probabilities are >= 0, so their bit patterns order as the values do.  A key is (pattern << 32) | ~index: descending
+// keys are descending values with the lower index first among equal ones, and no two keys are equal.  Every sum is a
+// fixed tree (per-thread run, wave scan or butterfly, the four waves in order); the only atomics count integers in LDS.
+// So a call is bitwise reproducible.  One workgroup per row, not one wave: at V = 500 a wave would hold 8 keys per lane
+// and walk 45 compare-exchange rounds of 4 pairs each, the workgroup walks them with one pair per thread -- and this
+// launch is on the serial chain of every step, where its latency counts, not its throughput.
+
+constexpr int SB_MAXV = 8 * NT;          // 2048: i2l_sample_decode's limit
+
+struct SampleRule {
+    int top_k;
+    float top_p;
+    unsigned long long seed;
+    float* probs;        // (B, T, V) or null
+};
+
+struct SampleLds {
+    unsigned long long key[SB_MAXV];     // sort keys
+    float q[SB_MAXV];                    // scaled logits, then the distribution
+    unsigned hist[NT];                   // digit counts of the radix selection
+    float redv[NT / 64];
+    int redi[NT / 64];
+    unsigned sel[2];                     // selected digit, rank left inside it
+};
+
+// Exclusive scan over the workgroup in thread order; *total gets the sum.  Fixed order: the wave's lanes by doubling
+// steps, then the waves one after the other.  Two __syncthreads().
+__device__ __forceinline__ float block_scan_excl(float v, float* red, int tid, float* total) {
+    const int lane = tid & 63, wave = tid >> 6;
+    float incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const float o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    float excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.f;
+    if (lane == 63) red[wave] = incl;
+    __syncthreads();
+    float base = 0.f, run = 0.f;
+#pragma unroll
+    for (int wv = 0; wv < NT / 64; ++wv) {
+        if (wv == wave) base = run;
+        run += red[wv];
+    }
+    __syncthreads();
+    *total = run;
+    return base + excl;
+}
+
+__device__ __forceinline__ unsigned block_scan_incl_u32(unsigned v, unsigned* red, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned o = __shfl_up(v, off, 64);
+        if (lane >= off) v += o;
+    }
+    if (lane == 63) red[wave] = v;
+    __syncthreads();
+    unsigned base = 0;
+#pragma unroll
+    for (int wv = 0; wv < NT / 64; ++wv)
+        if (wv < wave) base += red[wv];
+    __syncthreads();
+    return base + v;
+}
+
+// smallest of the workgroup's values (every thread gets it); two __syncthreads()
+__device__ __forceinline__ int block_min(int v, int* red, int tid) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    int m = red[0];
+#pragma unroll
+    for (int wv = 1; wv < NT / 64; ++wv) m = min(m, red[wv]);
+    __syncthreads();
+    return m;
+}
+
+// The kk-th largest (1 <= kk <= V) of q[0, V), q >= 0: most significant digit first, the digit's bin is the one in which
+// the count of larger values passes kk.  Thread tid looks after bin 255 - tid, so that a scan in thread order runs from
+// the largest digit down.
+__device__ __forceinline__ float radix_kth(SampleLds& s, int V, int kk, int tid) {
+    unsigned prefix = 0, mask = 0, need = (unsigned)kk;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        s.hist[tid] = 0;
+        __syncthreads();
+        for (int v = tid; v < V; v += NT) {
+            const unsigned b = __float_as_uint(s.q[v]);
+            if ((b & mask) == prefix) atomicAdd(&s.hist[(b >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        const unsigned bin = 255u - (unsigned)tid, c = s.hist[bin];
+        const unsigned incl = block_scan_incl_u32(c, reinterpret_cast<unsigned*>(s.redi), tid);   // values in bins >= bin
+        if (incl - c < need && need <= incl) { s.sel[0] = bin; s.sel[1] = need - (incl - c); }     // one thread
+        __syncthreads();
+        prefix |= s.sel[0] << shift;
+        mask |= 255u << shift;
+        need = s.sel[1];
+    }
+    return __uint_as_float(prefix);
+}
+
+// s.key[0, N) into descending order, N a power of two >= NT.  One compare-exchange per pair and round.  (Rounds of
+// distance <= 64 stay inside one wave's 128 keys and could do without the workgroup barrier; measured at the shipped
+// shape that gains nothing -- 19.0 against 18.7 us a launch -- so every round ends in the plain barrier.)
+__device__ __forceinline__ void bitonic_desc(unsigned long long* key, int N, int tid) {
+    for (int k = 2; k <= N; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < (N >> 1); i += NT) {
+                const int a = ((i & ~(j - 1)) << 1) | (i & (j - 1)), b = a | j;
+                const unsigned long long ka = key[a], kb = key[b];
+                if ((ka < kb) == ((a & k) == 0)) { key[a] = kb; key[b] = ka; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// One row: x[0, V) raw logits, u the row's uniform of this step.  Every thread returns the pick; po (V floats or null)
+// receives the final distribution.  V <= SB_MAXV, blockDim.x == NT.
+__device__ __forceinline__ int sample_row(const float* __restrict__ x, int V, float temperature, int use_temp, int top_k,
+                                          float top_p, float u, float* __restrict__ po, SampleLds& s, int tid) {
+    float best[1] = {-INFINITY};
+    int besti[1] = {0x7fffffff};
+    for (int v = tid; v < V; v += NT) {
+        float a = x[v];
+        if (use_temp) a = a / temperature;
+        s.q[v] = a;
+        if (a > best[0]) { best[0] = a; besti[0] = v; }
+    }
+    block_argmax<1>(best, besti, s.redv, s.redi, tid);
+    float sm = 0.f;
+    for (int v = tid; v < V; v += NT) sm += expf(s.q[v] - best[0]);
+    sm = block_sum(sm, s.redv, tid);
+    for (int v = tid; v < V; v += NT) s.q[v] = expf(s.q[v] - best[0]) / sm;
+    __syncthreads();
+    if (top_k > 0) {
+        const float kth = radix_kth(s, V, min(top_k, V), tid);
+        float s2 = 0.f;
+        for (int v = tid; v < V; v += NT) { const float q = s.q[v] < kth ? 0.f : s.q[v]; s.q[v] = q; s2 += q; }
+        s2 = block_sum(s2, s.redv, tid);
+        if (s2 > 0.f) for (int v = tid; v < V; v += NT) s.q[v] = s.q[v] / s2;
+        __syncthreads();
+    }
+    if (top_p > 0.f) {
+        int N = NT;
+        while (N < V) N <<= 1;
+        for (int v = tid; v < N; v += NT)       // padding: value 0 behind every column
+            s.key[v] = ((unsigned long long)(v < V ? __float_as_uint(s.q[v]) : 0u) << 32) | (unsigned)~v;
+        __syncthreads();
+        bitonic_desc(s.key, N, tid);
+        const int CH = N / NT;                  // thread tid owns sorted places [tid * CH, (tid + 1) * CH)
+        float part = 0.f;
+        for (int j = tid * CH; j < (tid + 1) * CH; ++j) part += __uint_as_float((unsigned)(s.key[j] >> 32));
+        float total;
+        float before = block_scan_excl(part, s.redv, tid, &total);   // mass sorted ahead of the place
+        for (int j = tid * CH; j < (tid + 1) * CH; ++j) {
+            const unsigned long long kj = s.key[j];
+            const int v = (int)~(unsigned)kj;
+            const float pv = __uint_as_float((unsigned)(kj >> 32));
+            if (v < V) s.q[v] = before > top_p ? 0.f : pv;           // the first place has nothing ahead of it: it stays
+            before += pv;
+        }
+        __syncthreads();
+        float s2 = 0.f;
+        for (int v = tid; v < V; v += NT) s2 += s.q[v];
+        s2 = block_sum(s2, s.redv, tid);
+        if (s2 > 0.f) for (int v = tid; v < V; v += NT) s.q[v] = s.q[v] / s2;
+        __syncthreads();
+    }
+    if (po)
+        for (int v = tid; v < V; v += NT) po[v] = s.q[v];
+    // inverse CDF over index order: thread tid owns the columns [tid * CH, (tid + 1) * CH)
+    const int CH = (V + NT - 1) / NT, v0 = min(V, tid * CH), v1 = min(V, (tid + 1) * CH);
+    float part = 0.f;
+    for (int v = v0; v < v1; ++v) part += s.q[v];
+    float total;
+    float run = block_scan_excl(part, s.redv, tid, &total);
+    const float target = u * total;
+    int pick = 0x7fffffff;
+    for (int v = v0; v < v1; ++v) {
+        const float q = s.q[v];
+        run += q;
+        if (q > 0.f && run > target && pick == 0x7fffffff) pick = v;
+    }
+    pick = block_min(pick, s.redi, tid);        // the cdf does not fall: the first crossing is the smallest one
+    return pick < V ? pick : besti[0];          // rounding corner: fall back to the arg max
+}
+
+// Token selection of step t by sampling, one workgroup per row.  ids, next token, finished rows and the live-row count as
+// select_batched_kernel.
+__global__ __launch_bounds__(NT) void sample_batched_kernel(BatchedParams p, SampleRule r, int t) {
+    __shared__ SampleLds s;
+    if (*p.live == 0) return;
+    const int V = p.w.V, row = blockIdx.x, tid = threadIdx.x;
+    float* po = r.probs ? r.probs + ((size_t)row * p.T + t) * V : nullptr;
+    const int pick = sample_row(p.lg + (size_t)row * p.w.Vp, V, p.temperature, p.use_temp, r.top_k, r.top_p,
+                                uniform01(r.seed, (unsigned)row, (unsigned)t), po, s, tid);
+    if (tid == 0) {
+        const int was_fin = p.fin[row];
+        if (p.ids) p.ids[(size_t)row * p.T + t] = (p.stop == I2L_STOP_STICKY && was_fin) ? -1 : pick;
+        p.tok[row] = pick;
+        if (pick == p.end_id && !was_fin) {
+            p.fin[row] = 1;
+            if (p.stop == I2L_STOP_STICKY) atomicSub(p.live, 1u);
+        }
+    }
+}
+
+// i2l_sample_logits: the rule applied once to (rows, ld) logits of the caller, one workgroup per row.
+__global__ __launch_bounds__(NT) void sample_logits_kernel(const float* __restrict__ logits, int ld, int V, float temperature,
+                                                           int use_temp, SampleRule r, unsigned step,
+                                                           int32_t* __restrict__ ids) {
+    __shared__ SampleLds s;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    float* po = r.probs ? r.probs + (size_t)row * V : nullptr;
+    const int pick = sample_row(logits + (size_t)row * ld, V, temperature, use_temp, r.top_k, r.top_p,
+                                uniform01(r.seed, (unsigned)row, step), po, s, tid);
+    if (tid == 0) ids[row] = pick;
+}

@@ -32,7 +32,7 @@ FLAG_RESNET_WIDE_TILES = 0x40000      # i2l_conv_bn_act_bf16_fwd: 128-column til
 FLAG_RESNET_NO_PATCH = 0x20000       # i2l_conv_bn_act_bf16_fwd: 3x3 convs on the implicit-GEMM ring kernel (A/B switch)
 FLAG_DECODE_GROUP16 = 0x8000         # greedy decode: 16 members x 16 rows per group, per-step products on the matrix cores (split-bf16 MFMA)
 FLAG_DECODE_GROUP8 = 0x1000          # greedy decode: 8 members x 8 rows per group (co-resident with a conv workgroup)
-FLAG_DECODE_BATCHED = 0x2000         # greedy decode: LSTMDecoder.run_steps takes i2l_greedy_decode_batched (step-batched split-bf16 MFMA GEMMs)
+FLAG_DECODE_BATCHED = 0x2000         # greedy decode: LSTMDecoder.run_steps takes i2l_greedy_decode_batched (step-batched split-bf16 MFMA GEMMs); sampling: sample_steps takes i2l_sample_decode_batched
 FLAG_BEAM_BATCHED = 0x80000          # beam search: Seq2SeqModel.beam_search_batch takes i2l_beam_decode_batched (the images x beam slots as rows of the step-batched GEMMs)
 FLAG_TRAIN_BATCHED = 0x100000        # training: i2l_decoder_train_fwd / _bwd take the step-batched matrix-core recurrences where i2l_decoder_train_batched_ok
 FLAG_TEST_SHORT_TIMEOUT, FLAG_TEST_DROP_MEMBER = 0x40, 0x80       # test hooks of the grouped kernels
@@ -113,6 +113,11 @@ _SIGNATURES = {
     "i2l_sample_decode": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
                                   c_int, c_float, c_uint64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),
+    "i2l_sample_decode_batched": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_float, c_int, c_float, c_uint64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "i2l_sample_logits": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_float, c_uint64, c_int, c_void_p,
+                                  c_void_p, c_void_p]),
     "i2l_beam_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "i2l_beam_decode": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                 c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -69,7 +69,8 @@ def _device(name: Optional[str]) -> torch.device:
 def _decode_flags(decode_kernel: str) -> int:
     """--decode-kernel: "auto" = the library's own choice (grouped kernels where the dimensions have them, else a row per
     workgroup); "batched" = the step-batched matrix-core decode (_lib.FLAG_DECODE_BATCHED), built for decoders the grouped
-    kernels do not take, such as the shipped two-layer, 512-wide one."""
+    kernels do not take, such as the shipped two-layer, 512-wide one.  It covers the greedy loop and, with --top-k /
+    --top-p, the sampling loop (i2l_sample_decode_batched)."""
     from . import _lib
     if decode_kernel not in ("auto", "batched"):
         raise SystemExit(f"img2latex_amd: --decode-kernel {decode_kernel}: expected auto or batched")
@@ -390,7 +391,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     p.add_argument("--top-p", type=float, default=0.0, help="Top-p (nucleus) sampling parameter")
     p.add_argument("--device", default=None, help="Device to use for inference (cuda)")
     p.add_argument("--decode-kernel", choices=("auto", "batched"), default="auto",
-                   help="(this package) greedy decode kernel: auto, or the step-batched matrix-core decode")
+                   help="(this package) decode kernel, greedy and --top-k / --top-p sampling: auto, or the step-batched matrix-core decode")
     t = sub.add_parser("train", help="Train the image-to-LaTeX model.")
     t.add_argument("--config-path", default="img2latex/configs/config.yaml", help="Path to configuration file")
     t.add_argument("--experiment-name", default="img2latex_v1", help="Name of the experiment")
@@ -426,7 +427,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     e.add_argument("--device", default=None, help="Device to use for evaluation (cuda)")
     e.add_argument("--output-dir", default="outputs", help="(this package) root of <experiment>/predictions")
     e.add_argument("--decode-kernel", choices=("auto", "batched"), default="auto",
-                   help="(this package) greedy decode kernel: auto, or the step-batched matrix-core decode")
+                   help="(this package) decode kernel, greedy and --top-k / --top-p sampling: auto, or the step-batched matrix-core decode")
     e.add_argument("--decode", choices=("host", "device"), default=None,
                    help="(this package) decode the page files with PIL on the host or with the PNG kernel on the device")
     v = sub.add_parser("vocab", help="(this package) Fit the vocabulary of a formulas file on the device and save it.")

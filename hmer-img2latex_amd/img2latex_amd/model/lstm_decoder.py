@@ -284,8 +284,10 @@ class LSTMDecoder(nn.Module):
 
     def sample_steps(self, encoder_output: torch.Tensor, steps: int, tok0: torch.Tensor, temperature: float,
                      top_k: int, top_p: float, seed: int, stop: int = _lib.STOP_STICKY, end_id: int = -1,
-                     hidden: Optional[Hidden] = None, want_probs: bool = False):
-        """prepare + one i2l_sample_decode launch (predictor.py:295-331).  Returns (ids, probs or None)."""
+                     hidden: Optional[Hidden] = None, want_probs: bool = False, flags: int = 0, want_state: bool = False):
+        """prepare + one i2l_sample_decode launch (predictor.py:295-331), or with ``(flags | self.kernel_flags) &
+        FLAG_DECODE_BATCHED`` the step-batched i2l_sample_decode_batched.  Returns (ids, probs or None), with
+        ``want_state`` (ids, probs or None, (h, c))."""
         w, keep, enc = self.prepare(encoder_output)
         rows, dev = enc.shape[0], enc.device
         tok0 = _lib.require_gpu(tok0, "tok0", torch.int32)
@@ -294,11 +296,52 @@ class LSTMDecoder(nn.Module):
             h0, c0 = _lib.require_gpu(hidden[0], "h0"), _lib.require_gpu(hidden[1], "c0")
         ids = torch.empty((rows, steps), dtype=torch.int32, device=dev)
         probs = torch.empty((rows, steps, self.vocab_size), dtype=torch.float32, device=dev) if want_probs else None
-        _lib.check(_lib.lib().i2l_sample_decode(
-            ctypes.byref(w), self._ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
-            float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, stop, int(end_id),
-            ids.data_ptr(), _lib.ptr(probs), None, None, _lib.stream_ptr()), "sample_decode")
+        h = c = None
+        if want_state:
+            h = torch.empty((self.lstm_layers, rows, self.hidden_dim), dtype=torch.float32, device=dev)
+            c = torch.empty_like(h)
+        all_flags = int(flags) | int(self.kernel_flags)
+        if all_flags & _lib.FLAG_DECODE_BATCHED:
+            # step-batched matrix-core path (sample_batched.inc.h): its scratch lives for this call only, on this stream
+            nbytes = _lib.lib().i2l_decode_batched_scratch_bytes(rows, self.vocab_size, self.hidden_dim, self.lstm_layers)
+            if nbytes == 0:
+                raise RuntimeError("img2latex_amd: decoder dimensions not supported by the step-batched decode")
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(_lib.lib().i2l_sample_decode_batched(
+                ctypes.byref(w), self._ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
+                float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, stop, int(end_id),
+                ids.data_ptr(), _lib.ptr(probs), _lib.ptr(h), _lib.ptr(c), scratch.data_ptr(), nbytes, all_flags,
+                _lib.stream_ptr()), "sample_decode_batched")
+            del scratch            # the caching allocator hands the block out again only in stream order
+        else:
+            _lib.check(_lib.lib().i2l_sample_decode(
+                ctypes.byref(w), self._ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
+                float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, stop, int(end_id),
+                ids.data_ptr(), _lib.ptr(probs), _lib.ptr(h), _lib.ptr(c), _lib.stream_ptr()), "sample_decode")
         del keep
+        return (ids, probs, (h, c)) if want_state else (ids, probs)
+
+    @staticmethod
+    def sample_logits(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, seed: int, step: int = 0,
+                      want_probs: bool = False):
+        """The sampling rule of ``sample_steps`` applied once to (rows, V) fp32 logits on the device (i2l_sample_logits;
+        a row may be a strided view with unit column stride).  Row r draws at uniform01(seed, r, step).  Returns
+        (ids (rows) int32, probs (rows, V) or None)."""
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+            raise RuntimeError("img2latex_amd: sample_logits needs a (rows, V) tensor")
+        if not logits.is_cuda:
+            raise RuntimeError("img2latex_amd: logits must be on the ROCm device (no CPU fallback)")
+        if logits.dtype != torch.float32:
+            raise TypeError(f"logits must be torch.float32, got {logits.dtype}")
+        rows, V = logits.shape
+        if logits.stride(1) != 1 or (rows > 1 and logits.stride(0) < V):
+            logits = logits.contiguous()
+        ld = max(V, logits.stride(0))
+        ids = torch.empty((rows,), dtype=torch.int32, device=logits.device)
+        probs = torch.empty((rows, V), dtype=torch.float32, device=logits.device) if want_probs else None
+        _lib.check(_lib.lib().i2l_sample_logits(
+            logits.data_ptr(), int(ld), rows, V, float(temperature), int(top_k), float(top_p),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), ids.data_ptr(), _lib.ptr(probs), _lib.stream_ptr()), "sample_logits")
         return ids, probs
 
     # ------------------------------------------------------------------ reference surface

@@ -243,7 +243,7 @@ class Predictor:
     def __init__(self, model: Seq2SeqModel, tokenizer, device: Optional[torch.device] = None,
                  model_type: str = "cnn_lstm", decode_flags: int = 0):
         # decode_flags (_lib.FLAG_DECODE_BATCHED: the step-batched matrix-core decode) are OR-ed into the flags of every
-        # greedy decode this predictor launches; 0 = the automatic kernel choice
+        # greedy and every sampling decode this predictor launches; 0 = the automatic kernel choice
         self.decode_flags = int(decode_flags)
         self.device = torch.device("cuda") if device is None else torch.device(device)
         if self.device.type != "cuda":
@@ -359,7 +359,8 @@ class Predictor:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         tok0 = torch.full((enc.shape[0],), int(self.tokenizer.start_token_id), dtype=torch.int32, device=enc.device)
         ids, _ = self.model.decoder.sample_steps(enc, max_length, tok0, temperature, top_k, top_p, seed,
-                                                 stop=_lib.STOP_STICKY, end_id=self.tokenizer.end_token_id)
+                                                 stop=_lib.STOP_STICKY, end_id=self.tokenizer.end_token_id,
+                                                 flags=self.decode_flags)
         return ids
 
     def _greedy_strings(self, table: DetokenizeTable, enc, max_length, temperature, **loop) -> List[str]:

@@ -70,7 +70,8 @@ typedef void* i2l_stream_t;
                                           per CU instead of two waves and 140 KB, so that a conv workgroup of the NEXT
                                           batch's encoder fits beside it; same ids                                   */
 #define I2L_FLAG_DECODE_BATCHED 0x2000  /* the Python layer's switch for i2l_greedy_decode_batched (LSTMDecoder.run_steps takes that entry
-                                          instead of i2l_greedy_decode_ex); the C entries ignore it */
+                                          instead of i2l_greedy_decode_ex) and i2l_sample_decode_batched (LSTMDecoder.sample_steps
+                                          takes that entry instead of i2l_sample_decode); the C entries ignore it */
 #define I2L_FLAG_BEAM_BATCHED 0x80000   /* the Python layer's switch for i2l_beam_decode_batched, as I2L_FLAG_DECODE_BATCHED is for the greedy entry
                                           (Seq2SeqModel.beam_search_batch takes that entry instead of i2l_beam_decode); the C entries ignore it */
 #define I2L_FLAG_TRAIN_BATCHED 0x100000 /* i2l_decoder_train_fwd / _bwd: the step-batched recurrences on the matrix cores -- one plain launch per
@@ -417,6 +418,32 @@ int i2l_sample_decode(const i2l_decoder_weights* w, const void* workspace, int r
                       const int32_t* tok0, const float* h0, const float* c0, float temperature, int top_k,
                       float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out, float* probs_out,
                       float* h_out, float* c_out, i2l_stream_t stream);
+
+/* i2l_sample_decode for decoders the grouped kernels do not take, STEP-BATCHED on the matrix cores: the loop, the scratch
+ * (i2l_decode_batched_scratch_bytes), the dimension rules and the sticky stop of i2l_greedy_decode_batched, with a sampling
+ * launch in the place of its selection launch -- one workgroup per row: softmax(logits / T) in fp32; the top-k threshold by
+ * a radix selection on the probabilities' bit patterns; the top-p cut by a sort of (bit pattern, index) keys, descending
+ * with the lower index first among equal values, and a scan of the sorted masses; one draw by inverse CDF over index order
+ * at uniform01(seed, row, step) * total, the first column with a non-zero probability whose cdf exceeds it (the arg max if
+ * rounding leaves none).  No column walks the vocabulary: O(V log V) per row and step where i2l_sample_decode is O(V^2).
+ * A seed draws the same uniforms as in i2l_sample_decode; the logits agree with its logits to fp32 rounding, so the ids
+ * agree wherever no mask and no draw sits on a near-tie.  Bitwise reproducible from call to call.
+ *   temperature > 0, top_k >= 0, top_p >= 0, not both 0, rows > 0, steps > 0, else I2L_ERR_ARG; vocab > 2048 and the
+ *   dimensions i2l_greedy_decode_batched refuses: I2L_ERR_UNSUPPORTED; scratch_bytes too small: I2L_ERR_WORKSPACE.
+ *   probs_out (rows, steps, V) or NULL; h_out / c_out (L, rows, H) or NULL.  flags: none used.
+ * Every refusal is decided on the host before the first HIP call. */
+int i2l_sample_decode_batched(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                              const int32_t* tok0, const float* h0, const float* c0, float temperature, int top_k,
+                              float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out, float* probs_out,
+                              float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
+                              i2l_stream_t stream);
+
+/* One application of the same device code to the caller's logits: (rows, ld) fp32, ld >= vocab, columns >= vocab are not
+ * read.  Row r draws at uniform01(seed, r, step).  ids_out (rows) int32; probs_out (rows, vocab) or NULL receives the
+ * masked, renormalised distribution.  Needs no decoder and no workspace.  Argument rules as above (step >= 0, ld >= vocab
+ * else I2L_ERR_ARG; vocab > 2048: I2L_ERR_UNSUPPORTED), decided on the host before the first HIP call. */
+int i2l_sample_logits(const float* logits, int ld, int rows, int vocab, float temperature, int top_k, float top_p,
+                      uint64_t seed, int step, int32_t* ids_out, float* probs_out, i2l_stream_t stream);
 
 /* Beam search for `images` independent images, `beam` beams each (<= I2L_MAX_BEAM):
  * per image exactly Seq2SeqModel._beam_search at batch 1 (seq2seq.py:234-298) --
