@@ -23,11 +23,13 @@
 
 struct BeamImage {       // per image: `completed` reduced to its best entry, the beam count, the end of the search
     double best_c;
-    int has_c, best_t, best_q;
+    int has_c, best_t, best_q;   // (the N-best search keeps a list instead and counts its entries in has_c)
     int nb;              // beams in the slots 0 .. nb - 1
     int t_last;          // last history row written
     int done;
 };
+
+struct NbestEntry;        // beam_nbest.inc.h
 
 struct BeamBatchedParams {
     int images, T, V, Vp, H, L, start_id, end_id;
@@ -44,6 +46,10 @@ struct BeamBatchedParams {
     int32_t* seq_out;    // [images][T+1]
     int32_t* len_out;    // [images]
     double* score_out;   // [images] or null
+    // the N-best search (beam_nbest.inc.h) keeps every completed beam instead of the best one; unused here
+    int N;                   // rows per image
+    const double* norm;      // [T + 1] length divisors, or null = all ones
+    NbestEntry* list;        // [images][N], the first img[i].has_c in use, keys non-increasing
 };
 
 // (a) of step `t` for one image: slots whose last token is END retire into the best-completed record, in slot order,
@@ -84,9 +90,15 @@ __global__ __launch_bounds__(DB_NT) void beam_init_batched_kernel(BeamBatchedPar
     if (i0 == 0) *p.live = ended ? 0u : (unsigned)p.images;
 }
 
-// Ranking, gather and retirement of step t (after its logits launch).  grid images; c_cur: the buffer the step's LSTM
-// launches updated, c_next: the one the next step's get.
+// The ending of a step of the N-best search (beam_nbest.inc.h): retiring beams go into the image's list.  One thread.
 template <int K>
+__device__ __forceinline__ void nb_step_end(const BeamBatchedParams& p, BeamImage& rec, const int* ntok, const double* nscore,
+                                            int* slot_live, bool all_end, int img, int t);
+
+// Ranking, gather and retirement of step t (after its logits launch).  grid images; c_cur: the buffer the step's LSTM
+// launches updated, c_next: the one the next step's get.  NBEST: the same step with nb_step_end in place of the
+// best-completed record (the kernel of i2l_beam_decode_nbest).
+template <int K, bool NBEST = false>
 __global__ __launch_bounds__(DB_NT) void beam_step_batched_kernel(BeamBatchedParams p, float* __restrict__ c_cur,
                                                                   float* __restrict__ c_next, int t) {
     __shared__ double nscore[K];
@@ -195,7 +207,9 @@ __global__ __launch_bounds__(DB_NT) void beam_step_batched_kernel(BeamBatchedPar
         }
         rec.nb = nb;
         rec.t_last = t;
-        if (all_end) {
+        if constexpr (NBEST) {
+            nb_step_end<K>(p, rec, ntok, nscore, slot_live, all_end, img, t);
+        } else if (all_end) {
             for (int q = 0; q < nb; ++q)
                 if (!rec.has_c || nscore[q] > rec.best_c) { rec.has_c = 1; rec.best_c = nscore[q]; rec.best_t = t; rec.best_q = q; }
             rec.done = 1;

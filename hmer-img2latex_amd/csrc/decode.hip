@@ -244,6 +244,7 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned row
 #include "decode_batched.inc.h"
 #include "sample_batched.inc.h"
 #include "beam_batched.inc.h"
+#include "beam_nbest.inc.h"
 
 // KR / KL > 0 (fast path for R == 1, L == 1, H <= 256: thread j owns hidden unit j for the whole loop):
 // rows [0,KR) of WhhT stay in the thread's registers and rows [KR,KR+KL) in LDS for all steps, so only
@@ -1373,9 +1374,81 @@ extern "C" size_t i2l_beam_batched_scratch_bytes(int images, int beam, int vocab
 }
 
 namespace {
+// nbest: the step that keeps every completed beam (beam_nbest.inc.h)
 template <int K>
-void launch_beam_step_batched(const BeamBatchedParams& p, float* c_cur, float* c_next, int t, hipStream_t s) {
-    hipLaunchKernelGGL(beam_step_batched_kernel<K>, dim3(p.images), dim3(DB_NT), 0, s, p, c_cur, c_next, t);
+void launch_beam_step_batched(const BeamBatchedParams& p, bool nbest, float* c_cur, float* c_next, int t, hipStream_t s) {
+    if (nbest) hipLaunchKernelGGL((beam_step_batched_kernel<K, true>), dim3(p.images), dim3(DB_NT), 0, s, p, c_cur, c_next, t);
+    else hipLaunchKernelGGL((beam_step_batched_kernel<K, false>), dim3(p.images), dim3(DB_NT), 0, s, p, c_cur, c_next, t);
+}
+
+// The launches of both step-batched beam entries, arguments already checked: init, per step the GEMM launches of
+// decode_batched.inc.h on the images * beam rows and the step kernel, then the final kernel.  `nb` (the outputs of the
+// n-best entry; bp then carries N, norm and list) selects the n-best kernels (beam_nbest.inc.h).
+int beam_batched_enqueue(const i2l_decoder_weights* w, const void* workspace, const Layout& lo, const BeamBatchedLayout& bl,
+                         int images, int beam, int steps, int start_id, int end_id, char* sb, BeamBatchedParams bp,
+                         const BeamNbestOut* nb, hipStream_t s) {
+    const int V = w->vocab, H = w->hidden, L = w->layers;
+    const int R = images * beam;
+    const size_t LRH = (size_t)L * R * H;
+    bp.images = images; bp.T = steps; bp.V = V; bp.Vp = lo.Vp; bp.H = H; bp.L = L;
+    bp.start_id = start_id; bp.end_id = end_id;
+    bp.tokhist = reinterpret_cast<int32_t*>(sb + bl.hist);
+    bp.parhist = bp.tokhist + (size_t)images * steps * beam;
+    bp.h = reinterpret_cast<float*>(sb + bl.h); bp.c = reinterpret_cast<float*>(sb + bl.c);
+    bp.lg = reinterpret_cast<float*>(sb + bl.lg);
+    bp.score = reinterpret_cast<double*>(sb + bl.score);
+    bp.last = reinterpret_cast<int*>(sb + bl.last); bp.slot_live = reinterpret_cast<int*>(sb + bl.slot_live);
+    bp.img = reinterpret_cast<BeamImage*>(sb + bl.img);
+    bp.live = reinterpret_cast<unsigned*>(sb + bl.live);
+
+    // the GEMM launches of decode_batched.inc.h on the R rows: the slot's last token, the image's Genc row, parity 0
+    BatchedParams p{};
+    p.w = step_weights(lo, static_cast<const char*>(workspace), V, H, L);
+    p.B = R; p.T = steps; p.genc_div = beam; p.forced = nullptr;
+    p.h = bp.h; p.lg = reinterpret_cast<float*>(sb + bl.lg);
+    p.tok = bp.last; p.live = bp.live;
+    p.temperature = 1.0f; p.select = I2L_SELECT_LOGITS; p.stop = I2L_STOP_NONE; p.end_id = end_id;
+
+    const size_t init_blocks = (2 * LRH + DB_NT - 1) / DB_NT;
+    hipLaunchKernelGGL(beam_init_batched_kernel, dim3((unsigned)(init_blocks < 1024 ? init_blocks : 1024)), dim3(DB_NT), 0,
+                       s, bp, beam);
+    I2L_CHECK_LAUNCH();
+    if (nb && start_id == end_id) {
+        hipLaunchKernelGGL(beam_nbest_init_kernel, dim3(i2l_cdiv(images, DB_NT)), dim3(DB_NT), 0, s, bp);
+        I2L_CHECK_LAUNCH();
+    }
+    const int tb_lstm = batched_tile_rows(H / 16, R), tb_logits = batched_tile_rows(lo.Vp / DB_COLS, R);
+    for (int t = 0; t < steps; ++t) {
+        float* c_cur = bp.c + (size_t)(t & 1) * LRH;
+        float* c_next = bp.c + (size_t)((t + 1) & 1) * LRH;
+        p.c = c_cur;
+        for (int l = 0; l < L; ++l) {
+            if (tb_lstm == 16) launch_batched_lstm<16>(p, l, 0, s);
+            else if (tb_lstm == 32) launch_batched_lstm<32>(p, l, 0, s);
+            else launch_batched_lstm<64>(p, l, 0, s);
+        }
+        if (tb_logits == 16) launch_batched_logits<16>(p, 0, s);
+        else if (tb_logits == 32) launch_batched_logits<32>(p, 0, s);
+        else launch_batched_logits<64>(p, 0, s);
+        switch (beam) {
+            case 1: launch_beam_step_batched<1>(bp, nb != nullptr, c_cur, c_next, t, s); break;
+            case 2: launch_beam_step_batched<2>(bp, nb != nullptr, c_cur, c_next, t, s); break;
+            case 3: launch_beam_step_batched<3>(bp, nb != nullptr, c_cur, c_next, t, s); break;
+            case 4: launch_beam_step_batched<4>(bp, nb != nullptr, c_cur, c_next, t, s); break;
+            case 5: launch_beam_step_batched<5>(bp, nb != nullptr, c_cur, c_next, t, s); break;
+            case 6: launch_beam_step_batched<6>(bp, nb != nullptr, c_cur, c_next, t, s); break;
+            case 7: launch_beam_step_batched<7>(bp, nb != nullptr, c_cur, c_next, t, s); break;
+            default: launch_beam_step_batched<8>(bp, nb != nullptr, c_cur, c_next, t, s); break;
+        }
+        I2L_CHECK_LAUNCH();
+    }
+    if (nb)
+        hipLaunchKernelGGL(beam_nbest_final_kernel, dim3((unsigned)(((size_t)images * bp.N + DB_NT - 1) / DB_NT)), dim3(DB_NT),
+                           0, s, bp, *nb, beam);
+    else
+        hipLaunchKernelGGL(beam_final_batched_kernel, dim3(i2l_cdiv(images, DB_NT)), dim3(DB_NT), 0, s, bp, beam);
+    I2L_CHECK_LAUNCH();
+    return I2L_OK;
 }
 }  // namespace
 
@@ -1394,63 +1467,48 @@ extern "C" int i2l_beam_decode_batched(const i2l_decoder_weights* w, const void*
     const BeamBatchedLayout bl = beam_batched_layout(images, beam, lo.Vp, H, L, steps);
     if (scratch_bytes < bl.total) return I2L_ERR_WORKSPACE;
 
-    char* sb = static_cast<char*>(scratch);
-    const int R = images * beam;
-    const size_t LRH = (size_t)L * R * H;
     BeamBatchedParams bp{};
-    bp.images = images; bp.T = steps; bp.V = V; bp.Vp = lo.Vp; bp.H = H; bp.L = L;
-    bp.start_id = start_id; bp.end_id = end_id;
-    bp.tokhist = reinterpret_cast<int32_t*>(sb + bl.hist);
-    bp.parhist = bp.tokhist + (size_t)images * steps * beam;
-    bp.h = reinterpret_cast<float*>(sb + bl.h); bp.c = reinterpret_cast<float*>(sb + bl.c);
-    bp.lg = reinterpret_cast<float*>(sb + bl.lg);
-    bp.score = reinterpret_cast<double*>(sb + bl.score);
-    bp.last = reinterpret_cast<int*>(sb + bl.last); bp.slot_live = reinterpret_cast<int*>(sb + bl.slot_live);
-    bp.img = reinterpret_cast<BeamImage*>(sb + bl.img);
-    bp.live = reinterpret_cast<unsigned*>(sb + bl.live);
     bp.seq_out = seq_out; bp.len_out = len_out; bp.score_out = score_out;
+    return beam_batched_enqueue(w, workspace, lo, bl, images, beam, steps, start_id, end_id, static_cast<char*>(scratch), bp,
+                                nullptr, i2l_s(stream));
+}
 
-    // the GEMM launches of decode_batched.inc.h on the R rows: the slot's last token, the image's Genc row, parity 0
-    BatchedParams p{};
-    p.w = step_weights(lo, static_cast<const char*>(workspace), V, H, L);
-    p.B = R; p.T = steps; p.genc_div = beam; p.forced = nullptr;
-    p.h = bp.h; p.lg = reinterpret_cast<float*>(sb + bl.lg);
-    p.tok = bp.last; p.live = bp.live;
-    p.temperature = 1.0f; p.select = I2L_SELECT_LOGITS; p.stop = I2L_STOP_NONE; p.end_id = end_id;
+// ---------------------------------------------------------------------------------------------
+// N-best beam search with length-normalised ranking (beam_nbest.inc.h): the search above, every completed beam kept
+// in a per-image list sorted by score / norm[length] instead of the best raw score alone.
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t i2l_beam_nbest_scratch_bytes(int images, int beam, int nbest, int vocab, int hidden, int layers,
+                                               int steps) {
+    if (!beam_nbest_dims_ok(images, beam, nbest, vocab, hidden, layers, steps)) return 0;
+    return beam_nbest_layout(images, beam, nbest, i2l_cdiv(vocab, VCHUNK) * VCHUNK, hidden, layers, steps).total;
+}
 
-    hipStream_t s = i2l_s(stream);
-    const size_t init_blocks = (2 * LRH + DB_NT - 1) / DB_NT;
-    hipLaunchKernelGGL(beam_init_batched_kernel, dim3((unsigned)(init_blocks < 1024 ? init_blocks : 1024)), dim3(DB_NT), 0,
-                       s, bp, beam);
-    I2L_CHECK_LAUNCH();
-    const int tb_lstm = batched_tile_rows(H / 16, R), tb_logits = batched_tile_rows(lo.Vp / DB_COLS, R);
-    for (int t = 0; t < steps; ++t) {
-        float* c_cur = bp.c + (size_t)(t & 1) * LRH;
-        float* c_next = bp.c + (size_t)((t + 1) & 1) * LRH;
-        p.c = c_cur;
-        for (int l = 0; l < L; ++l) {
-            if (tb_lstm == 16) launch_batched_lstm<16>(p, l, 0, s);
-            else if (tb_lstm == 32) launch_batched_lstm<32>(p, l, 0, s);
-            else launch_batched_lstm<64>(p, l, 0, s);
-        }
-        if (tb_logits == 16) launch_batched_logits<16>(p, 0, s);
-        else if (tb_logits == 32) launch_batched_logits<32>(p, 0, s);
-        else launch_batched_logits<64>(p, 0, s);
-        switch (beam) {
-            case 1: launch_beam_step_batched<1>(bp, c_cur, c_next, t, s); break;
-            case 2: launch_beam_step_batched<2>(bp, c_cur, c_next, t, s); break;
-            case 3: launch_beam_step_batched<3>(bp, c_cur, c_next, t, s); break;
-            case 4: launch_beam_step_batched<4>(bp, c_cur, c_next, t, s); break;
-            case 5: launch_beam_step_batched<5>(bp, c_cur, c_next, t, s); break;
-            case 6: launch_beam_step_batched<6>(bp, c_cur, c_next, t, s); break;
-            case 7: launch_beam_step_batched<7>(bp, c_cur, c_next, t, s); break;
-            default: launch_beam_step_batched<8>(bp, c_cur, c_next, t, s); break;
-        }
-        I2L_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(beam_final_batched_kernel, dim3(i2l_cdiv(images, DB_NT)), dim3(DB_NT), 0, s, bp, beam);
-    I2L_CHECK_LAUNCH();
-    return I2L_OK;
+extern "C" int i2l_beam_decode_nbest(const i2l_decoder_weights* w, const void* workspace, int images, int beam, int nbest,
+                                     int steps, int start_id, int end_id, const double* length_norm, void* scratch,
+                                     size_t scratch_bytes, int32_t* seq_out, int32_t* len_out, double* score_out,
+                                     double* key_out, int32_t* finished_out, int32_t* count_out, int flags,
+                                     i2l_stream_t stream) {
+    (void)flags;
+    // every refusal is decided here, before the first HIP call
+    int rc = check_weights(w);
+    if (rc != I2L_OK) return rc;
+    if (!workspace || !scratch || !seq_out || !len_out || !score_out || !count_out || images <= 0 || steps <= 0 ||
+        beam <= 0 || nbest <= 0)
+        return I2L_ERR_ARG;
+    const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
+    if (!beam_nbest_dims_ok(images, beam, nbest, V, H, L, steps)) return I2L_ERR_UNSUPPORTED;
+    const Layout lo = make_layout(images, V, E, H, L);
+    const BeamNbestLayout nl = beam_nbest_layout(images, beam, nbest, lo.Vp, H, L, steps);
+    if (scratch_bytes < nl.total) return I2L_ERR_WORKSPACE;
+
+    char* sb = static_cast<char*>(scratch);
+    BeamBatchedParams bp{};
+    bp.N = nbest; bp.norm = length_norm;
+    bp.list = reinterpret_cast<NbestEntry*>(sb + nl.list);
+    BeamNbestOut nb{};
+    nb.seq_out = seq_out; nb.len_out = len_out; nb.score_out = score_out; nb.key_out = key_out;
+    nb.finished_out = finished_out; nb.count_out = count_out;
+    return beam_batched_enqueue(w, workspace, lo, nl.b, images, beam, steps, start_id, end_id, sb, bp, &nb, i2l_s(stream));
 }
 
 extern "C" size_t i2l_decoder_group_status_offset(int rows, int vocab, int embed, int hidden, int layers) {

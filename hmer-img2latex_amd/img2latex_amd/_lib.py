@@ -20,7 +20,7 @@ ERR_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_LAUNCH = -1, -2, -3, -4      # incl
 STOP_NONE, STOP_STICKY = 0, 1
 SELECT_LOGITS, SELECT_SOFTMAX, SELECT_SAMPLE = 0, 1, 2
 PREP_WEIGHTS, PREP_ROWS, PREP_ALL = 1, 2, 3
-MAX_LSTM_LAYERS, MAX_BEAM = 4, 8
+MAX_LSTM_LAYERS, MAX_BEAM, MAX_NBEST = 4, 8, 16
 # kernel-selection flags (include/img2latex_hip.h I2L_FLAG_*): explicit arguments, the library reads no environment
 FLAG_EXACT_FP32, FLAG_NO_GROUP, FLAG_RESNET_NO_RING, FLAG_RESNET_IM2COL_STEM = 0x1, 0x2, 0x4, 0x8
 FLAG_WEIGHTS_PACKED = 0x10          # conv forward: the workspace still holds the packed filters of these weights
@@ -124,6 +124,10 @@ _SIGNATURES = {
     "i2l_beam_batched_scratch_bytes": (c_size_t, [c_int] * 6),
     "i2l_beam_decode_batched": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                         c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "i2l_beam_nbest_scratch_bytes": (c_size_t, [c_int] * 7),
+    "i2l_beam_decode_nbest": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                      c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_void_p]),
     "i2l_attention_context_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                           c_int, c_int, c_void_p]),
     "i2l_decoder_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -2,6 +2,7 @@
 (img2latex/cli.py:104-120 ``train``, :253-269 ``predict``, :315-332 ``evaluate``), and ``vocab``, which this package adds:
 
     python -m img2latex_amd predict CHECKPOINT IMAGE [--beam-size N] [--max-length N] [--temperature T]
+                                                     [--nbest N --length-penalty A]  (this package: N-best beam search)
                                                      [--top-k K] [--top-p P] [--device cuda]
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
                                   [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
@@ -95,6 +96,15 @@ def predict(checkpoint_path: str, image_path: str, beam_size: int = 0, max_lengt
                                           decode_flags=_decode_flags(decode_kernel))
     return predictor.predict(image=image_path, beam_size=beam_size, max_length=max_length, temperature=temperature,
                              top_k=top_k, top_p=top_p)
+
+
+def predict_nbest(checkpoint_path: str, image_path: str, beam_size: int, nbest: int, max_length: int = 141,
+                  length_penalty: float = 0.0, device: Optional[str] = None):
+    """(this package) the ``nbest`` best beam-search hypotheses of the image as (latex, score, key), in rank order."""
+    from .training import Predictor
+    predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device))
+    return predictor.predict_nbest(image=image_path, beam_size=beam_size, nbest=nbest, max_length=max_length,
+                                   length_penalty=length_penalty)
 
 
 def vocab(formulas_file: str, out_path: str, max_sequence_length: int = 150, device: Optional[str] = None):
@@ -392,6 +402,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     p.add_argument("--device", default=None, help="Device to use for inference (cuda)")
     p.add_argument("--decode-kernel", choices=("auto", "batched"), default="auto",
                    help="(this package) decode kernel, greedy and --top-k / --top-p sampling: auto, or the step-batched matrix-core decode")
+    p.add_argument("--nbest", type=int, default=0,
+                   help="(this package) with --beam-size K > 0: print the N best hypotheses, one key<TAB>latex line each, "
+                        "in rank order (0: the single result as before)")
+    p.add_argument("--length-penalty", type=float, default=0.0,
+                   help="(this package) with --nbest: rank by score / length ** A (0: by the raw score)")
     t = sub.add_parser("train", help="Train the image-to-LaTeX model.")
     t.add_argument("--config-path", default="img2latex/configs/config.yaml", help="Path to configuration file")
     t.add_argument("--experiment-name", default="img2latex_v1", help="Name of the experiment")
@@ -436,6 +451,15 @@ def main(argv: Optional[List[str]] = None) -> int:
     v.add_argument("--max-sequence-length", type=int, default=150, help="Maximum sequence length stored with the vocabulary")
     v.add_argument("--device", default=None, help="Device to fit on (cuda)")
     args = ap.parse_args(argv)
+    if args.command == "predict" and args.nbest < 0:
+        ap.error("--nbest must be >= 0")
+    if args.command == "predict" and args.nbest > 0:
+        if args.beam_size <= 0:
+            ap.error("--nbest needs --beam-size above 0")
+        for latex, _, key in predict_nbest(args.checkpoint_path, args.image_path, args.beam_size, args.nbest,
+                                           args.max_length, args.length_penalty, args.device):
+            print(f"{key!r}\t{latex}")
+        return 0
     if args.command == "predict":
         latex = predict(args.checkpoint_path, args.image_path, args.beam_size, args.max_length, args.temperature,
                         args.top_k, args.top_p, args.device, args.decode_kernel)

@@ -8,8 +8,10 @@ device->host copy of the ids at the end instead of a sync per step).
 from __future__ import annotations
 
 import ctypes
+import math
 import warnings
-from typing import Dict, List, Optional
+from collections import namedtuple
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -18,6 +20,34 @@ import torch.nn as nn
 from .. import _lib
 from .cnn_encoder import CNNEncoder
 from .lstm_decoder import LSTMDecoder
+
+# one row of beam_search_nbest: tokens (START stripped, cut at END), the raw sum of log-probabilities, the ranking key
+# score / norm[length] and whether the beam ended in END
+BeamHypothesis = namedtuple("BeamHypothesis", ["tokens", "score", "key", "finished"])
+
+
+def length_norm_table(max_length: int, length_penalty: float = 0.0, length_norm: Optional[Sequence[float]] = None):
+    """The float64 table of ``max_length + 1`` divisors beam_search_nbest ranks by (index: tokens after START, END
+    included), or None for all ones.  ``length_penalty = a``: ``norm[n] = float(n) ** a`` for n >= 1, ``norm[0] = 1``.
+    ``length_norm``: the caller's own table, validated here -- ValueError for a wrong length, a non-finite or
+    non-positive value, or a non-zero ``length_penalty`` beside it."""
+    if length_norm is not None:
+        if length_penalty != 0.0:
+            raise ValueError("img2latex_amd: pass length_norm or a non-zero length_penalty, not both")
+        table = [float(v) for v in length_norm]
+        if len(table) != max_length + 1:
+            raise ValueError(f"img2latex_amd: length_norm needs max_length + 1 = {max_length + 1} values, got {len(table)}")
+        if not all(math.isfinite(v) and v > 0.0 for v in table):
+            raise ValueError("img2latex_amd: every length_norm value must be finite and > 0")
+        return table
+    if not math.isfinite(length_penalty):
+        raise ValueError("img2latex_amd: length_penalty must be finite")
+    if length_penalty == 0.0:
+        return None
+    table = [1.0] + [float(n) ** float(length_penalty) for n in range(1, max_length + 1)]
+    if not all(math.isfinite(v) and v > 0.0 for v in table):
+        raise ValueError(f"img2latex_amd: length_penalty {length_penalty} leaves a table value that is not finite and > 0")
+    return table
 
 
 class Seq2SeqModel(nn.Module):
@@ -197,3 +227,40 @@ class Seq2SeqModel(nn.Module):
         if return_scores:
             return out, score.cpu().tolist()
         return out
+
+    def beam_search_nbest(self, encoder_output: torch.Tensor, start_token_id: int, end_token_id: int, max_length: int,
+                          beam_size: int, nbest: Optional[int] = None, length_penalty: float = 0.0,
+                          length_norm: Optional[Sequence[float]] = None) -> List[List[BeamHypothesis]]:
+        """Per image the ``nbest`` (default ``beam_size``) best hypotheses of the beam search above, ranked by
+        ``score / norm[n]``, n = tokens after START with END (``length_norm_table``): the completed beams in rank order,
+        then, when the search ran out of steps, its final beams.  With ``nbest = 1`` and no normalisation, row 0 is
+        ``beam_search_batch``'s result under _lib.FLAG_BEAM_BATCHED.  Always the step-batched search
+        (i2l_beam_decode_nbest); dimensions it refuses raise RuntimeError."""
+        nbest = int(beam_size if nbest is None else nbest)
+        table = length_norm_table(int(max_length), float(length_penalty), length_norm)
+        dec = self.decoder
+        w, keep, enc = dec.prepare(encoder_output)
+        n, dev = enc.shape[0], enc.device
+        L = _lib.lib()
+        nbytes = L.i2l_beam_nbest_scratch_bytes(n, int(beam_size), nbest, dec.vocab_size, dec.hidden_dim, dec.lstm_layers,
+                                                int(max_length))
+        if nbytes == 0:
+            raise RuntimeError(f"img2latex_amd: dimensions not supported by the n-best beam search (beam_size <= "
+                               f"{_lib.MAX_BEAM}, nbest <= {_lib.MAX_NBEST}, vocabulary <= 2048)")
+        norm = None if table is None else torch.tensor(table, dtype=torch.float64, device=dev)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # lives for this call only, on this stream
+        seq = torch.empty((n, nbest, max_length + 1), dtype=torch.int32, device=dev)
+        ln = torch.empty((n, nbest), dtype=torch.int32, device=dev)
+        score = torch.empty((n, nbest), dtype=torch.float64, device=dev)
+        key = torch.empty((n, nbest), dtype=torch.float64, device=dev)
+        fin = torch.empty((n, nbest), dtype=torch.int32, device=dev)
+        count = torch.empty((n,), dtype=torch.int32, device=dev)
+        _lib.check(L.i2l_beam_decode_nbest(ctypes.byref(w), dec._ws.data_ptr(), n, int(beam_size), nbest, int(max_length),
+                                           int(start_token_id), int(end_token_id), _lib.ptr(norm), scratch.data_ptr(),
+                                           nbytes, seq.data_ptr(), ln.data_ptr(), score.data_ptr(), key.data_ptr(),
+                                           fin.data_ptr(), count.data_ptr(), 0, _lib.stream_ptr()), "beam_decode_nbest")
+        seq_h, ln_h, sc_h = seq.cpu().tolist(), ln.cpu().tolist(), score.cpu().tolist()
+        key_h, fin_h, cnt_h = key.cpu().tolist(), fin.cpu().tolist(), count.cpu().tolist()
+        del keep, scratch, norm
+        return [[BeamHypothesis(seq_h[j][r][:ln_h[j][r]], sc_h[j][r], key_h[j][r], bool(fin_h[j][r]))
+                 for r in range(cnt_h[j])] for j in range(n)]

@@ -17,7 +17,7 @@ from __future__ import annotations
 import os
 import warnings
 import weakref
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -714,3 +714,27 @@ class Predictor:
         if seq and seq[-1] == end:
             seq = seq[:-1]
         return self.tokenizer.decode(seq)
+
+    def predict_batch_nbest(self, images, beam_size: int = 5, nbest: Optional[int] = None, max_length: int = 141,
+                            length_penalty: float = 0.0, batch_size: int = 16) -> List[List[Tuple[str, float, float]]]:
+        """Per image the (latex, score, key) of its ``nbest`` (default ``beam_size``) best beam-search hypotheses in rank
+        order (Seq2SeqModel.beam_search_nbest: key = score / length ** length_penalty), every image through
+        ``_prepare_image`` as in ``predict_batch``, the ids through the tokenizer's own ``decode``."""
+        if isinstance(images, torch.Tensor):
+            images = [images] if images.dim() <= 3 else list(images)
+        start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
+        results: List[List[Tuple[str, float, float]]] = []
+        for i in range(0, len(images), batch_size):
+            x = torch.stack([self._prepare_image(im) for im in images[i:i + batch_size]])
+            if x.dim() == 5 and x.shape[1] == 1:
+                x = x.squeeze(1)
+            with torch.no_grad():
+                rows = self.model.beam_search_nbest(self.model.encoder(x.to(self.device)), start, end, max_length,
+                                                    beam_size, nbest=nbest, length_penalty=length_penalty)
+            results.extend([(self.tokenizer.decode(h.tokens), h.score, h.key) for h in hyps] for hyps in rows)
+        return results
+
+    def predict_nbest(self, image, beam_size: int = 5, nbest: Optional[int] = None, max_length: int = 141,
+                      length_penalty: float = 0.0) -> List[Tuple[str, float, float]]:
+        """``predict_batch_nbest`` for one image (path / PIL / ndarray / tensor)."""
+        return self.predict_batch_nbest([image], beam_size, nbest, max_length, length_penalty)[0]

@@ -42,6 +42,7 @@ extern "C" {
 
 #define I2L_MAX_LSTM_LAYERS 4
 #define I2L_MAX_BEAM 8
+#define I2L_MAX_NBEST 16   /* rows per image of i2l_beam_decode_nbest */
 
 typedef void* i2l_stream_t;
 
@@ -488,6 +489,33 @@ size_t i2l_beam_batched_scratch_bytes(int images, int beam, int vocab, int hidde
 int i2l_beam_decode_batched(const i2l_decoder_weights* w, const void* workspace, int images, int beam, int steps,
                             int start_id, int end_id, void* scratch, size_t scratch_bytes, int32_t* seq_out,
                             int32_t* len_out, double* score_out, int flags, i2l_stream_t stream);
+
+/* N-best beam search with length-normalised ranking: the search of i2l_beam_decode_batched (the same launches per step,
+ * the same candidates, fp64 scores, stable selection, retirement one iteration later and both `break`s), with another
+ * ending.  Every completed beam b is kept with key(b) = score(b) / length_norm[n(b)], n = its tokens after START, END
+ * included; the result rows of an image are `completed` sorted by key, descending and stable (earlier-retired first, slot
+ * order within a step), cut to nbest.  If the search ran out of steps (neither `break` fired) and rows are left, the
+ * final beams follow, by key, stable in slot order; such a row has finished = 1 iff its last token is END (the
+ * reference never retires a beam that ends at the very last step).  Rows from `completed` have finished = 1.  With
+ * nbest = 1 and length_norm NULL, seq / len / score are those of i2l_beam_decode_batched, bit for bit.
+ *   length_norm  DEVICE array of steps + 1 fp64 values, finite and > 0 (the caller validates them), or NULL = all ones;
+ *                the kernel only divides (correctly rounded: a host restatement gets the same keys).  [0] is used only
+ *                when start_id == end_id.
+ *   seq_out      (images, nbest, steps + 1) int32: START stripped, cut at END, -1 padded
+ *   len_out      (images, nbest) int32;  score_out (images, nbest) fp64 raw sums;  key_out (images, nbest) fp64 or NULL
+ *   finished_out (images, nbest) int32 or NULL;  count_out (images) int32 rows filled.
+ *   Rows >= count: len = -1, ids = -1, score = key = -inf, finished = 0.  Every element of every output is written.
+ *   scratch      i2l_beam_nbest_scratch_bytes(...) bytes: that of i2l_beam_decode_batched plus per image nbest entries
+ *                (key, score, history row, slot).
+ * Accepted: as i2l_beam_decode_batched, and 1 <= nbest <= I2L_MAX_NBEST whatever the beam width (nbest > beam is legal:
+ * `completed` grows by up to `beam` entries per step).  Refusals as there (a NULL score_out or count_out is I2L_ERR_ARG
+ * too; nbest <= 0: I2L_ERR_ARG, nbest > I2L_MAX_NBEST: I2L_ERR_UNSUPPORTED), decided on the host before the first HIP
+ * call; the size query returns 0 for refused dimensions.  flags: none used.  The library keeps no state. */
+size_t i2l_beam_nbest_scratch_bytes(int images, int beam, int nbest, int vocab, int hidden, int layers, int steps);
+int i2l_beam_decode_nbest(const i2l_decoder_weights* w, const void* workspace, int images, int beam, int nbest, int steps,
+                          int start_id, int end_id, const double* length_norm, void* scratch, size_t scratch_bytes,
+                          int32_t* seq_out, int32_t* len_out, double* score_out, double* key_out, int32_t* finished_out,
+                          int32_t* count_out, int flags, i2l_stream_t stream);
 
 /* Additive attention, general source length S (Attention.forward, decoder.py:312-343):
  * context[b] = softmax_s(v . tanh(W [hidden[b] ; enc[b,s]] + b_a)) @ enc[b].
