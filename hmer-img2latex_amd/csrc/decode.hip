@@ -238,11 +238,35 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned row
     return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
+// Phase (c) of a beam step for one live slot, by one wave: log_softmax of the row x[0, V) in fp32 (seq2seq.py:266) and
+// its top K (:267: descending, the lower index first on ties) by K rounds of first-index wave arg max.  Lane 0 writes
+// topv[0, K) / topi[0, K).  V <= 2048: the taken-mask has 32 bits per lane.
+__device__ __forceinline__ void beam_topk_row(const float* x, int V, int K, int lane, float* topv, int* topi) {
+    float m = -INFINITY;
+    for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int v = lane; v < V; v += 64) s += expf(x[v] - m);
+    s = wave_sum(s);
+    const float lse = logf(s);
+    unsigned taken = 0;                                  // bit i: element lane + 64*i already selected
+    for (int j = 0; j < K; ++j) {
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int v = lane, i = 0; v < V; v += 64, ++i)
+            if (!((taken >> i) & 1u) && x[v] > bv) { bv = x[v]; bi = v; }
+        wave_argmax(bv, bi);
+        if (bi < V && (bi & 63) == lane) taken |= 1u << (bi >> 6);
+        if (lane == 0) { topv[j] = (bv - m) - lse; topi[j] = bi < V ? bi : 0; }
+    }
+}
+
 #include "decode_group.inc.h"
 #include "decode_group16.inc.h"
 #include "beam_group.inc.h"
 #include "decode_batched.inc.h"
 #include "sample_batched.inc.h"
+#include "beam_rules.inc.h"
 #include "beam_batched.inc.h"
 #include "beam_nbest.inc.h"
 
@@ -541,6 +565,9 @@ __global__ __launch_bounds__(NT) void decode_kernel(DecodeParams p) {
 
 // ---------------------------------------------------------------------------------------------
 // Beam search: one workgroup per image, K beams = K rows of the step (seq2seq.py:234-298 at B=1).
+// The kernel is the decoder step (b), the gather (e) and the barriers; the search's decisions are shared with the
+// step-batched kernels: phase (c) is beam_topk_row above, the serial rules (a), (d), (f) and the result are
+// beam_rules.inc.h's, run by thread 0 on the LDS arrays below.
 // ---------------------------------------------------------------------------------------------
 struct BeamParams {
     StepWeights w;
@@ -570,7 +597,7 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamParams p) {
     int* live = last + K;                               // [K]
     int* npar = live + K;                               // [K] parent slot of the new beams
     int* ntok = npar + K;                               // [K]
-    int* ctl = ntok + K;                                // [0]=nb [1]=nlive [2]=done
+    int* ctl = ntok + K;                                // [0] = the search has ended (thread 0's im.done, for all threads)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int img = blockIdx.x;
@@ -578,37 +605,18 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamParams p) {
     int32_t* parhist = p.parhist + (size_t)img * T * K;
 
     for (int idx = tid; idx < 2 * LKH; idx += NT) { hs[idx] = 0.f; cs[idx] = 0.f; }
+    // the image's record and the serial rules (beam_rules.inc.h) are thread 0's; (a) of step 0 here, of step t + 1 in
+    // the ending of step t
+    BeamImage im{};
+    int nnew = 0;
     if (tid == 0) {
-        for (int q = 0; q < K; ++q) { score[q] = 0.0; last[q] = p.start_id; live[q] = 0; }
-        ctl[0] = 1; ctl[1] = 0; ctl[2] = 0;
+        beam_start(im, BeamBest{}, score, last, live, K, p.start_id, p.end_id);
+        ctl[0] = im.done;
     }
-    // best completed beam so far (only thread 0 uses these)
-    bool has_c = false;
-    double best_c = 0.0;
-    int best_t = -1, best_q = 0;
-    int t_last = -1;                                    // last history row written
     __syncthreads();
 
-    int par = 0, cpar = 0;
-    for (int t = 0; t < T; ++t) {
-        // (a) beams whose last token is END retire into `completed` (seq2seq.py:258-260), in beam order
-        if (tid == 0) {
-            const int nb = ctl[0];
-            int nl = 0;
-            for (int q = 0; q < K; ++q) {
-                int lv = 0;
-                if (q < nb) {
-                    if (last[q] == p.end_id) {
-                        if (!has_c || score[q] > best_c) { has_c = true; best_c = score[q]; best_t = t - 1; best_q = q; }
-                    } else { lv = 1; ++nl; }
-                }
-                live[q] = lv;
-            }
-            ctl[1] = nl;
-        }
-        __syncthreads();
-        if (ctl[1] == 0) break;                          // `if not candidates: break` (:276-277)
-
+    const int par = 0, cpar = 0;
+    for (int t = 0; t < T && !ctl[0]; ++t) {
         // (b) one decoder step for the K slots (retired / unused slots compute on a clamped token, ignored)
         int tok[K], grow[K];
 #pragma unroll
@@ -623,59 +631,14 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamParams p) {
         project<K>(w, h_top, lp, lg, false, 1.f, best, besti, psum, tid);
         __syncthreads();
 
-        // (c) log_softmax (fp32, :266) and top-K (:267: descending, lower index first on ties); wave per row
-        for (int r = wave; r < K; r += NT / 64) {
-            if (!live[r]) continue;                      // wave-uniform
-            const float* x = lg + (size_t)r * Vp;
-            float m = -INFINITY;
-            for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
-            m = wave_max(m);
-            float s = 0.f;
-            for (int v = lane; v < V; v += 64) s += expf(x[v] - m);
-            s = wave_sum(s);
-            const float lse = logf(s);
-            unsigned taken = 0;                          // bit i: element lane + 64*i already selected
-            for (int j = 0; j < K; ++j) {
-                float bv = -INFINITY;
-                int bi = 0x7fffffff;
-                for (int v = lane, i = 0; v < V; v += 64, ++i)
-                    if (!((taken >> i) & 1u) && x[v] > bv) { bv = x[v]; bi = v; }
-                wave_argmax(bv, bi);
-                if (bi < V && (bi & 63) == lane) taken |= 1u << (bi >> 6);
-                if (lane == 0) { topv[r * K + j] = (bv - m) - lse; topi[r * K + j] = bi < V ? bi : 0; }
-            }
-        }
+        // (c) log_softmax and top-K, a wave per live slot
+        for (int r = wave; r < K; r += NT / 64)
+            if (live[r]) beam_topk_row(lg + (size_t)r * Vp, V, K, lane, topv + r * K, topi + r * K);   // wave-uniform
         __syncthreads();
 
-        // (d) candidates in (beam, rank) order, fp64 scores, stable descending selection of K (:273-280)
-        if (tid == 0) {
-            const int nlive = ctl[1];
-            const int ncand = nlive * K;
-            const int nnew = ncand < K ? ncand : K;
-            unsigned long long used = 0ull;              // K*K <= 64 candidate flags
-            for (int q = 0; q < nnew; ++q) {
-                double bs = 0.0;
-                int bc = -1;
-                for (int s0 = 0; s0 < K; ++s0) {
-                    if (!live[s0]) continue;
-                    for (int j = 0; j < K; ++j) {
-                        const int c = s0 * K + j;
-                        if ((used >> c) & 1ull) continue;
-                        const double sc = score[s0] + (double)topv[c];
-                        if (bc < 0 || sc > bs) { bs = sc; bc = c; }
-                    }
-                }
-                used |= 1ull << bc;
-                npar[q] = bc / K;
-                ntok[q] = topi[bc];
-                nscore[q] = bs;
-                tokhist[(size_t)t * K + q] = topi[bc];
-                parhist[(size_t)t * K + q] = bc / K;
-            }
-            for (int q = nnew; q < K; ++q) { npar[q] = 0; ntok[q] = 0; nscore[q] = 0.0; }
-            ctl[0] = nnew;
-            t_last = t;
-        }
+        // (d) the ranking of the K x K candidates and the history rows
+        if (tid == 0)
+            nnew = beam_rank(live, score, topv, topi, K, npar, ntok, nscore, tokhist + (size_t)t * K, parhist + (size_t)t * K);
         __syncthreads();
 
         // (e) new beam q inherits the fresh state of its parent (hidden.clone(), :272): gather into the other buffers
@@ -695,39 +658,17 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamParams p) {
         }
         __syncthreads();
         // par / cpar unchanged: the gathered state sits in hs[par], cs[cpar] again
+        // (f) the step's ending and (a) of the next step
         if (tid == 0) {
-            const int nb = ctl[0];
-            bool all_end = true;
-            for (int q = 0; q < K; ++q) {
-                score[q] = nscore[q];
-                last[q] = ntok[q];
-                if (q < nb && ntok[q] != p.end_id) all_end = false;
-            }
-            if (all_end) {                               // completed.extend(beams); break   (:282-284)
-                for (int q = 0; q < nb; ++q)
-                    if (!has_c || score[q] > best_c) { has_c = true; best_c = score[q]; best_t = t; best_q = q; }
-                ctl[2] = 1;
-            }
+            beam_step_end(im, BeamBest{}, nnew, ntok, nscore, score, last, live, K, p.end_id, t, T);
+            ctl[0] = im.done;
         }
         __syncthreads();
-        if (ctl[2]) break;
     }
 
-    // result: max(completed) (first on ties) else beams[0]; strip START, cut at END (:286-297)
     if (tid == 0) {
-        int tt = has_c ? best_t : t_last, q = has_c ? best_q : 0;
-        const double sc = has_c ? best_c : score[0];
-        int32_t* out = p.seq_out + (size_t)img * (T + 1);
-        int n = tt + 1;                                  // tokens after START
-        for (int pos = tt; pos >= 0; --pos) {
-            out[pos] = tokhist[(size_t)pos * K + q];
-            q = parhist[(size_t)pos * K + q];
-        }
-        int len = n;
-        for (int i = 0; i < n; ++i)
-            if (out[i] == p.end_id) { len = i; break; }
-        for (int i = len; i < T + 1; ++i) out[i] = -1;
-        p.len_out[img] = len;
+        double sc;
+        p.len_out[img] = beam_best_result(im, score, tokhist, parhist, K, p.end_id, T, p.seq_out + (size_t)img * (T + 1), &sc);
         if (p.score_out) p.score_out[img] = sc;
     }
 }
@@ -944,8 +885,8 @@ extern "C" int i2l_sample_decode(const i2l_decoder_weights* w, const void* works
                                  const int32_t* tok0, const float* h0, const float* c0, float temperature, int top_k,
                                  float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out, float* probs_out,
                                  float* h_out, float* c_out, i2l_stream_t stream) {
-    if (!(temperature > 0.f) || top_k < 0 || top_p < 0.f || (top_k == 0 && top_p == 0.f)) return I2L_ERR_ARG;
-    if (w && w->vocab > 8 * 256) return I2L_ERR_UNSUPPORTED;
+    if (!sample_args_ok(temperature, top_k, top_p)) return I2L_ERR_ARG;
+    if (w && w->vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
     return launch_decode(w, workspace, rows, steps, tok0, nullptr, h0, c0, temperature, I2L_SELECT_SAMPLE, stop, end_id,
                          top_k, top_p, (unsigned long long)seed, ids_out, nullptr, probs_out, h_out, c_out, stream);
 }
@@ -1136,12 +1077,22 @@ extern "C" size_t i2l_decode_batched_scratch_bytes(int rows, int vocab, int hidd
 
 namespace {
 template <int TB>
-void launch_batched_lstm(const BatchedParams& p, int layer, int t, hipStream_t s) {
-    hipLaunchKernelGGL(lstm_step_mfma_kernel<TB>, dim3(p.w.H / 16, i2l_cdiv(p.B, TB)), dim3(DB_NT), 0, s, p, layer, t);
+void launch_batched_lstm(const BatchedParams& p, int t, hipStream_t s) {
+    for (int l = 0; l < p.w.L; ++l)
+        hipLaunchKernelGGL(lstm_step_mfma_kernel<TB>, dim3(p.w.H / 16, i2l_cdiv(p.B, TB)), dim3(DB_NT), 0, s, p, l, t);
 }
 template <int TB>
 void launch_batched_logits(const BatchedParams& p, int t, hipStream_t s) {
     hipLaunchKernelGGL(logits_mfma_kernel<TB>, dim3(p.w.Vp / DB_COLS, i2l_cdiv(p.B, TB)), dim3(DB_NT), 0, s, p, t);
+}
+// the L LSTM launches and the logits launch of step t on p's rows; tb_*: batched_tile_rows of either grid
+void launch_batched_step(const BatchedParams& p, int tb_lstm, int tb_logits, int t, hipStream_t s) {
+    if (tb_lstm == 16) launch_batched_lstm<16>(p, t, s);
+    else if (tb_lstm == 32) launch_batched_lstm<32>(p, t, s);
+    else launch_batched_lstm<64>(p, t, s);
+    if (tb_logits == 16) launch_batched_logits<16>(p, t, s);
+    else if (tb_logits == 32) launch_batched_logits<32>(p, t, s);
+    else launch_batched_logits<64>(p, t, s);
 }
 
 // the loop of both step-batched entries; `sample` != null: sample_batched_kernel selects (select is I2L_SELECT_SAMPLE).
@@ -1184,14 +1135,7 @@ int launch_batched(const i2l_decoder_weights* w, const void* workspace, int rows
     const int tb_lstm = batched_tile_rows(H / 16, rows), tb_logits = batched_tile_rows(lo.Vp / DB_COLS, rows);
     const int sel_grid = i2l_cdiv(rows, DB_NT / 64);
     for (int t = 0; t < steps; ++t) {
-        for (int l = 0; l < L; ++l) {
-            if (tb_lstm == 16) launch_batched_lstm<16>(p, l, t, s);
-            else if (tb_lstm == 32) launch_batched_lstm<32>(p, l, t, s);
-            else launch_batched_lstm<64>(p, l, t, s);
-        }
-        if (tb_logits == 16) launch_batched_logits<16>(p, t, s);
-        else if (tb_logits == 32) launch_batched_logits<32>(p, t, s);
-        else launch_batched_logits<64>(p, t, s);
+        launch_batched_step(p, tb_lstm, tb_logits, t, s);
         if (sample) hipLaunchKernelGGL(sample_batched_kernel, dim3(rows), dim3(NT), 0, s, p, *sample, t);
         else hipLaunchKernelGGL(select_batched_kernel, dim3(sel_grid), dim3(DB_NT), 0, s, p, t);
         I2L_CHECK_LAUNCH();
@@ -1230,7 +1174,7 @@ extern "C" int i2l_sample_decode_batched(const i2l_decoder_weights* w, const voi
     // every refusal is decided on the host, here and in launch_batched, before the first HIP call
     int rc = check_weights(w);
     if (rc != I2L_OK) return rc;
-    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || (top_k == 0 && top_p == 0.f)) return I2L_ERR_ARG;
+    if (!sample_args_ok(temperature, top_k, top_p)) return I2L_ERR_ARG;
     if (rows <= 0 || steps <= 0) return I2L_ERR_ARG;
     if (w->vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
     const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
@@ -1241,7 +1185,7 @@ extern "C" int i2l_sample_decode_batched(const i2l_decoder_weights* w, const voi
 extern "C" int i2l_sample_logits(const float* logits, int ld, int rows, int vocab, float temperature, int top_k,
                                  float top_p, uint64_t seed, int step, int32_t* ids_out, float* probs_out,
                                  i2l_stream_t stream) {
-    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || (top_k == 0 && top_p == 0.f)) return I2L_ERR_ARG;
+    if (!sample_args_ok(temperature, top_k, top_p)) return I2L_ERR_ARG;
     if (rows <= 0 || vocab <= 0 || ld < vocab || step < 0) return I2L_ERR_ARG;
     if (vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
     if (!logits || !ids_out) return I2L_ERR_ARG;
@@ -1422,14 +1366,7 @@ int beam_batched_enqueue(const i2l_decoder_weights* w, const void* workspace, co
         float* c_cur = bp.c + (size_t)(t & 1) * LRH;
         float* c_next = bp.c + (size_t)((t + 1) & 1) * LRH;
         p.c = c_cur;
-        for (int l = 0; l < L; ++l) {
-            if (tb_lstm == 16) launch_batched_lstm<16>(p, l, 0, s);
-            else if (tb_lstm == 32) launch_batched_lstm<32>(p, l, 0, s);
-            else launch_batched_lstm<64>(p, l, 0, s);
-        }
-        if (tb_logits == 16) launch_batched_logits<16>(p, 0, s);
-        else if (tb_logits == 32) launch_batched_logits<32>(p, 0, s);
-        else launch_batched_logits<64>(p, 0, s);
+        launch_batched_step(p, tb_lstm, tb_logits, 0, s);
         switch (beam) {
             case 1: launch_beam_step_batched<1>(bp, nb != nullptr, c_cur, c_next, t, s); break;
             case 2: launch_beam_step_batched<2>(bp, nb != nullptr, c_cur, c_next, t, s); break;

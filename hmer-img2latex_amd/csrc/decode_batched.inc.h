@@ -77,7 +77,7 @@ __global__ __launch_bounds__(DB_NT) void lstm_step_mfma_kernel(BatchedParams p, 
         } else {
             add = *reinterpret_cast<const float4*>(w.biasP[layer] + 4 * unit);
         }
-        const f32x4_t z = (acc[nt][2] + acc[nt][1]) + acc[nt][0];   // small terms first
+        const f32x4_t z = db_fold(acc[nt]);
         const float ig = sigmoidf_(z[0] + add.x), fg = sigmoidf_(z[1] + add.y);
         const float gg = tanhf_(z[2] + add.z), og = sigmoidf_(z[3] + add.w);
         const size_t ci = (size_t)row * H + unit;
@@ -110,8 +110,20 @@ __global__ __launch_bounds__(DB_NT) void logits_mfma_kernel(BatchedParams p, int
     for (int nt = 0; nt < TB / 16; ++nt) {
         const int row = row0 + 16 * nt + (lane & 15);
         if (row >= B) continue;
-        const f32x4_t z = (acc[nt][2] + acc[nt][1]) + acc[nt][0];
+        const f32x4_t z = db_fold(acc[nt]);
         *reinterpret_cast<float4*>(p.lg + (size_t)row * w.Vp + col) = make_float4(z[0] + bb.x, z[1] + bb.y, z[2] + bb.z, z[3] + bb.w);
+    }
+}
+
+// The token selected for `row` at step t, by one thread: ids (-1 once the row has finished under the sticky stop), the
+// next step's token, the finished mark and the count of unfinished rows.
+__device__ __forceinline__ void commit_token_batched(const BatchedParams& p, int row, int t, int sel) {
+    const int was_fin = p.fin[row];
+    if (p.ids) p.ids[(size_t)row * p.T + t] = (p.stop == I2L_STOP_STICKY && was_fin) ? -1 : sel;
+    p.tok[row] = sel;
+    if (sel == p.end_id && !was_fin) {
+        p.fin[row] = 1;
+        if (p.stop == I2L_STOP_STICKY) atomicSub(p.live, 1u);
     }
 }
 
@@ -152,16 +164,7 @@ __global__ __launch_bounds__(DB_NT) void select_batched_kernel(BatchedParams p, 
         wave_argmax(pbest, pbesti);
         besti = pbesti;
     }
-    if (lane == 0) {
-        const int sel = besti < V ? besti : 0;
-        const int was_fin = p.fin[row];
-        if (p.ids) p.ids[(size_t)row * p.T + t] = (p.stop == I2L_STOP_STICKY && was_fin) ? -1 : sel;
-        p.tok[row] = sel;
-        if (sel == p.end_id && !was_fin) {
-            p.fin[row] = 1;
-            if (p.stop == I2L_STOP_STICKY) atomicSub(p.live, 1u);
-        }
-    }
+    if (lane == 0) commit_token_batched(p, row, t, besti < V ? besti : 0);
 }
 
 // state in, tokens, finished marks, the live-row count and ids = -1 (steps an early end never runs)

@@ -40,6 +40,9 @@ __device__ __forceinline__ void db_split8(const float (&v)[8], u32x4_t& q0, u32x
     q2 = u32x4_t{s2[0], s2[1], s2[2], s2[3]};
 }
 
+// the sum of one row tile's three piece classes, small terms first
+__device__ __forceinline__ f32x4_t db_fold(const f32x4_t (&a)[3]) { return (a[2] + a[1]) + a[0]; }
+
 // acc[nt][piece class] += W[0..K)[col0 .. col0 + 63]^T . X[rows row0 .. row0 + TB)[0..K)^T for this workgroup's tile:
 // wave w takes columns col0 + 16 w .. + 15 and all TB / 16 row tiles.  W is [K][ldw] fp32, X is [B][ldx] fp32; rows past
 // B - 1 read row B - 1 (the caller drops them).  K % DB_KC == 0.  The next round's global loads are issued before this

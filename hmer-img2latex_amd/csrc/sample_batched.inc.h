@@ -18,6 +18,12 @@
 
 constexpr int SB_MAXV = 8 * NT;          // 2048: i2l_sample_decode's limit
 
+// the sampling arguments of every entry (i2l_sample_decode, i2l_sample_decode_batched, i2l_sample_logits); the
+// comparisons are written so that a NaN is refused
+inline bool sample_args_ok(float temperature, int top_k, float top_p) {
+    return !(!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || (top_k == 0 && top_p == 0.f));
+}
+
 struct SampleRule {
     int top_k;
     float top_p;
@@ -209,15 +215,7 @@ __global__ __launch_bounds__(NT) void sample_batched_kernel(BatchedParams p, Sam
     float* po = r.probs ? r.probs + ((size_t)row * p.T + t) * V : nullptr;
     const int pick = sample_row(p.lg + (size_t)row * p.w.Vp, V, p.temperature, p.use_temp, r.top_k, r.top_p,
                                 uniform01(r.seed, (unsigned)row, (unsigned)t), po, s, tid);
-    if (tid == 0) {
-        const int was_fin = p.fin[row];
-        if (p.ids) p.ids[(size_t)row * p.T + t] = (p.stop == I2L_STOP_STICKY && was_fin) ? -1 : pick;
-        p.tok[row] = pick;
-        if (pick == p.end_id && !was_fin) {
-            p.fin[row] = 1;
-            if (p.stop == I2L_STOP_STICKY) atomicSub(p.live, 1u);
-        }
-    }
+    if (tid == 0) commit_token_batched(p, row, t, pick);
 }
 
 // i2l_sample_logits: the rule applied once to (rows, ld) logits of the caller, one workgroup per row.

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(DB_NT) void lstm_train_step_fwd_kernel(TrainBuf p, 
         const size_t bt = (size_t)row * T + t;
         const float4 add = layer == 0 ? *reinterpret_cast<const float4*>(p.GX + bt * G + 4 * unit)
                                       : *reinterpret_cast<const float4*>(p.biasP[layer] + 4 * unit);
-        const f32x4_t z = (acc[nt][2] + acc[nt][1]) + acc[nt][0];   // small terms first
+        const f32x4_t z = db_fold(acc[nt]);
         const float ig = sigmoidf_(z[0] + add.x), fg = sigmoidf_(z[1] + add.y);
         const float gg = tanhf_(z[2] + add.z), og = sigmoidf_(z[3] + add.w);
         const size_t ci = bt * H + unit;
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(DB_NT) void lstm_train_step_bwd_prod_kernel(BwdBuf 
     for (int nt = 0; nt < TB / 16; ++nt) {
         const int row = row0 + 16 * nt + (lane & 15);
         if (row >= B) continue;
-        const f32x4_t z = (acc[nt][2] + acc[nt][1]) + acc[nt][0];
+        const f32x4_t z = db_fold(acc[nt]);
         *reinterpret_cast<float4*>(part + ((size_t)slice * B + row) * H + col) = make_float4(z[0], z[1], z[2], z[3]);
     }
 }

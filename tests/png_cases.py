@@ -460,8 +460,8 @@ def adam7(px: np.ndarray) -> bytes:
     return bytes(out)
 
 
-def build_host_program(out_dir: str) -> str:
-    """Compiles csrc/png_host_main.cpp (the shared decode core with a ``main``) with the host compiler that comes with
+def build_host_program(out_dir: str, name: str = "png_host_main") -> str:
+    """Compiles csrc/<name>.cpp (png_host_main: the shared decode core with a ``main``) with the host compiler that comes with
     hipcc and ``-fsanitize=address,undefined`` -> ``(the program's path, sanitized)``.  Where the sanitizer runtime cannot
     be linked the program is built plain and ``sanitized`` is False: the caller decides whether that is acceptable."""
     import os
@@ -471,12 +471,12 @@ def build_host_program(out_dir: str) -> str:
     hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     clang = os.path.join(os.path.dirname(os.path.realpath(hipcc)), "..", "lib", "llvm", "bin", "clang++")
     cxx = clang if os.path.exists(clang) else (shutil.which("clang++") or shutil.which("g++") or "c++")
-    exe = os.path.join(out_dir, "png_host_main")
-    base = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-I", csrc, os.path.join(csrc, "png_host_main.cpp"), "-o", exe]
+    exe = os.path.join(out_dir, name)
+    base = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-I", csrc, os.path.join(csrc, name + ".cpp"), "-o", exe]
     r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True)
     sanitized = r.returncode == 0
     if not sanitized:
-        print("png_host_main: the sanitizer build failed, building plain:\n" + r.stderr[-800:])
+        print(name + ": the sanitizer build failed, building plain:\n" + r.stderr[-800:])
         subprocess.run(base, check=True)
     return exe, sanitized
 

@@ -48,6 +48,7 @@ DECODE_REFUSALS = [
     ("top_k -1", dict(top_k=-1), _lib.ERR_ARG),
     ("top_p -0.1", dict(top_p=-0.1), _lib.ERR_ARG),
     ("top_k and top_p zero", dict(top_k=0, top_p=0.0), _lib.ERR_ARG),
+    ("top_p nan", dict(top_p=float("nan")), _lib.ERR_ARG),
     ("rows 0", dict(rows=0), _lib.ERR_ARG),
     ("steps 0", dict(steps=0), _lib.ERR_ARG),
     ("vocab 2049", dict(V=2049), _lib.ERR_UNSUPPORTED),
@@ -68,6 +69,10 @@ def test_decode_refusals_need_no_device(what, kw, code):
         assert need > 0
         kw["scratch_bytes"] = need - 1
     rc = _decode(w, **kw)
+    if what == "top_p nan":     # one check for all three entries (sample_args_ok): the row kernel's entry refuses it as well
+        assert _lib.lib().i2l_sample_decode(ctypes.byref(w), FAKE, 4, 3, FAKE, None, None, 1.0, 5, kw["top_p"], 7,
+                                            _lib.STOP_NONE, 2, FAKE, None, None, None, None) == _lib.ERR_ARG
+        assert _logits(**kw) == _lib.ERR_ARG
     del keep
     assert rc == code, (what, rc)
 
