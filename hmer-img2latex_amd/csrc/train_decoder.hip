@@ -14,7 +14,8 @@
 // Only the two recurrences are sequential; every weight gradient is one large GEMM.  I2L_FLAG_TRAIN_BATCHED swaps both
 // for one launch per (step, layer) on the matrix cores (train_batched.inc.h); everything around them stays.
 // Dropout masks come from a counter-based hash of (seed, stream, element index), so backward
-// regenerates them instead of storing them.  With the reference's Attention over a length-1
+// regenerates them instead of storing them (the rule: DESIGN.md section 4, "The dropout mask rule";
+// tests/dropout_ref.py restates it).  With the reference's Attention over a length-1
 // source the context equals enc (see decode.hip), and the attention parameters receive an
 // exactly-zero gradient: the host zero-fills them.
 #include <math.h>
@@ -683,7 +684,8 @@ extern "C" int i2l_decoder_train_fwd(const i2l_decoder_weights* w, const float* 
     if (rc != I2L_OK) return rc;
     const int split = (flags & I2L_FLAG_EXACT_FP32) ? 0 : 1;
     const bool group_on = !(flags & I2L_FLAG_NO_GROUP);
-    if (!enc || !tokens || !logits_out || B <= 0 || T <= 0 || dropout_p < 0.f || dropout_p >= 1.f) return I2L_ERR_ARG;
+    if (!enc || !tokens || !logits_out || B <= 0 || T <= 0) return I2L_ERR_ARG;
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return I2L_ERR_ARG;      // written so that NaN is refused too
     const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
     const bool batched = train_batched_on(V, E, H, L, flags);
     const TLayout lo = make_tlayout(B, T, V, E, H, L);
@@ -816,6 +818,7 @@ extern "C" int i2l_decoder_train_bwd(const i2l_decoder_weights* w, const int32_t
     const int split = (flags & I2L_FLAG_EXACT_FP32) ? 0 : 1;
     const bool group_on = !(flags & I2L_FLAG_NO_GROUP);
     if (!tokens || !dlogits || !gr || !denc_out || B <= 0 || T <= 0) return I2L_ERR_ARG;
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return I2L_ERR_ARG;      // as the forward: p = 1 would scale by inf
     if (!gr->embedding || !gr->w_ih || !gr->w_hh || !gr->b_ih || !gr->b_hh || !gr->w_out || !gr->b_out) return I2L_ERR_ARG;
     const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
     const bool batched = train_batched_on(V, E, H, L, flags);

@@ -22,6 +22,13 @@ from ..model._train_fn import (decoder_train_backward, decoder_train_forward, en
 from .dp import OverlappedAllReduce, broadcast_parameters, rank_of
 
 
+def step_seed(seed: int, step: int, rank: int, micro: int) -> int:
+    """The dropout seed of one forward_backward: one mask stream per (seed, optimizer step, data-parallel rank,
+    accumulation micro-step).  The kernels hash the LOCAL element index, so without the rank every replica would reuse
+    rank 0's masks for its own rows.  62 bits: what LSTMDecoder.forward draws too."""
+    return ((seed * 1000003 + step) * 4099 + rank + 7919 * micro) & 0x3FFFFFFFFFFFFFFF
+
+
 class TrainStep:
     def __init__(self, model, lr: float = 1e-3, weight_decay: float = 1e-4, clip_grad_norm: float = 5.0,
                  pad_token_id: int = 0, label_smoothing: float = 0.1, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -98,9 +105,7 @@ class TrainStep:
         tokens_in = formulas[:, :-1].contiguous()                    # seq2seq.py:115-120
         targets = formulas[:, 1:].contiguous()                       # trainer.py:306
         B, T = tokens_in.shape
-        # one dropout stream per (seed, optimizer step, data-parallel rank): the kernels hash the LOCAL element index,
-        # so without the rank every replica would reuse rank 0's masks for its own rows
-        self.step_seed = ((self.seed * 1000003 + self.step_count) * 4099 + self.rank + 7919 * self._micro) & 0x3FFFFFFFFFFFFFFF
+        self.step_seed = step_seed(self.seed, self.step_count, self.rank, self._micro)
         enc, enc_state = encoder_train_forward(model.encoder, images)
         logits, dec_state = decoder_train_forward(model.decoder, enc, tokens_in, self.step_seed)
         V = logits.shape[-1]

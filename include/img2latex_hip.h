@@ -541,7 +541,9 @@ typedef struct i2l_decoder_grads {
 
 /* Teacher-forced LSTMDecoder.forward in training mode (decoder.py:100-195) for input tokens
  * (B,T) int32 [= formulas[:, :-1], seq2seq.py:115-120]; keeps what BPTT needs in `workspace`.
- * dropout_p: nn.Dropout p (masks from a counter-based hash of `seed`; 0 disables);
+ * dropout_p: nn.Dropout p in [0, 1) (anything else, NaN included, is I2L_ERR_ARG in both calls; 0 disables).  The masks
+ * are a counter-based hash of (seed, stream, element index), never stored: the hash, the streams, the element indices and
+ * which half of X is masked on which path are stated once in DESIGN.md, section 4, "The dropout mask rule";
  * attention_path: 0 = decoder.py:121-143 (dropout on cat[emb,enc]), 1 = :144-193 (dropout on emb).
  * logits_out (B,T,V).  flags: I2L_FLAG_NO_GROUP (row-per-workgroup recurrences), I2L_FLAG_EXACT_FP32 (GEMMs),
  * I2L_FLAG_TRAIN_BATCHED (step-batched recurrences); the caller MUST pass the same flags to the backward call: forward
