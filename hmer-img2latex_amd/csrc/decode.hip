@@ -266,6 +266,8 @@ __device__ __forceinline__ void beam_topk_row(const float* x, int V, int K, int 
 #include "beam_group.inc.h"
 #include "decode_batched.inc.h"
 #include "sample_batched.inc.h"
+#include "bracket_rules.inc.h"
+#include "decode_constrained.inc.h"
 #include "beam_rules.inc.h"
 #include "beam_batched.inc.h"
 #include "beam_nbest.inc.h"
@@ -1095,13 +1097,14 @@ void launch_batched_step(const BatchedParams& p, int tb_lstm, int tb_logits, int
     else launch_batched_logits<64>(p, t, s);
 }
 
-// the loop of both step-batched entries; `sample` != null: sample_batched_kernel selects (select is I2L_SELECT_SAMPLE).
+// the loop of the step-batched entries; `sample` != null: sample_batched_kernel selects (select is I2L_SELECT_SAMPLE);
+// `con` != null: the constrained twin of either selection kernel, on the rows' zeroed bracket state.
 // The caller has checked the weights and its own arguments; every other refusal is decided here, before the first HIP call.
 int launch_batched(const i2l_decoder_weights* w, const void* workspace, int rows, int steps, const int32_t* tok0,
                    const int32_t* forced, const float* h0, const float* c0, float temperature, int select, int stop,
-                   int end_id, const SampleRule* sample, int32_t* ids_out, float* logits_out, float* h_out, float* c_out,
-                   void* scratch, size_t scratch_bytes, uint32_t* resident_flag, uint32_t resident_value,
-                   i2l_stream_t stream) {
+                   int end_id, const SampleRule* sample, const ConstrainRule* con, int32_t* ids_out, float* logits_out,
+                   float* h_out, float* c_out, void* scratch, size_t scratch_bytes, uint32_t* resident_flag,
+                   uint32_t resident_value, i2l_stream_t stream) {
     if (!workspace || !tok0 || rows <= 0 || steps <= 0) return I2L_ERR_ARG;
     if ((h0 == nullptr) != (c0 == nullptr)) return I2L_ERR_ARG;
     if (stop != I2L_STOP_NONE && stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
@@ -1127,6 +1130,7 @@ int launch_batched(const i2l_decoder_weights* w, const void* workspace, int rows
         hipLaunchKernelGGL(publish_value32_kernel, dim3(1), dim3(1), 0, s, resident_flag, resident_value);
         I2L_CHECK_LAUNCH();
     }
+    if (con && hipMemsetAsync(con->state, 0, (size_t)rows * sizeof(BracketState), s) != hipSuccess) return I2L_ERR_LAUNCH;
     const size_t most = (size_t)L * rows * H > (size_t)rows * steps ? (size_t)L * rows * H : (size_t)rows * steps;
     const size_t copy_blocks = (most + DB_NT - 1) / DB_NT;
     const int copy_grid = (int)(copy_blocks < 1024 ? copy_blocks : 1024);
@@ -1136,7 +1140,9 @@ int launch_batched(const i2l_decoder_weights* w, const void* workspace, int rows
     const int sel_grid = i2l_cdiv(rows, DB_NT / 64);
     for (int t = 0; t < steps; ++t) {
         launch_batched_step(p, tb_lstm, tb_logits, t, s);
-        if (sample) hipLaunchKernelGGL(sample_batched_kernel, dim3(rows), dim3(NT), 0, s, p, *sample, t);
+        if (con && sample) hipLaunchKernelGGL(sample_constrained_kernel, dim3(rows), dim3(NT), 0, s, p, *sample, *con, t);
+        else if (con) hipLaunchKernelGGL(select_constrained_kernel, dim3(sel_grid), dim3(DB_NT), 0, s, p, *con, t);
+        else if (sample) hipLaunchKernelGGL(sample_batched_kernel, dim3(rows), dim3(NT), 0, s, p, *sample, t);
         else hipLaunchKernelGGL(select_batched_kernel, dim3(sel_grid), dim3(DB_NT), 0, s, p, t);
         I2L_CHECK_LAUNCH();
     }
@@ -1159,7 +1165,8 @@ extern "C" int i2l_greedy_decode_batched(const i2l_decoder_weights* w, const voi
     if (rc != I2L_OK) return rc;
     if (select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
     return launch_batched(w, workspace, rows, steps, tok0, forced, h0, c0, temperature, select, stop, end_id, nullptr,
-                          ids_out, logits_out, h_out, c_out, scratch, scratch_bytes, resident_flag, resident_value, stream);
+                          nullptr, ids_out, logits_out, h_out, c_out, scratch, scratch_bytes, resident_flag, resident_value,
+                          stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1179,7 +1186,7 @@ extern "C" int i2l_sample_decode_batched(const i2l_decoder_weights* w, const voi
     if (w->vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
     const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
     return launch_batched(w, workspace, rows, steps, tok0, nullptr, h0, c0, temperature, I2L_SELECT_SAMPLE, stop, end_id,
-                          &rule, ids_out, nullptr, h_out, c_out, scratch, scratch_bytes, nullptr, 0, stream);
+                          &rule, nullptr, ids_out, nullptr, h_out, c_out, scratch, scratch_bytes, nullptr, 0, stream);
 }
 
 extern "C" int i2l_sample_logits(const float* logits, int ld, int rows, int vocab, float temperature, int top_k,
@@ -1192,6 +1199,84 @@ extern "C" int i2l_sample_logits(const float* logits, int ld, int rows, int voca
     const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
     hipLaunchKernelGGL(sample_logits_kernel, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab, temperature,
                        (temperature != 1.0f) ? 1 : 0, rule, (unsigned)step, ids_out);
+    I2L_CHECK_LAUNCH();
+    return I2L_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Bracket-constrained step-batched decode (bracket_rules.inc.h, decode_constrained.inc.h): the same loop, the constrained
+// twin of either selection kernel as the last launch of a step.  Every refusal is decided on the host, here and in
+// launch_batched, before the first HIP call; the library keeps no state -- the rows' state is the caller's buffer.
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t i2l_bracket_state_bytes(int rows) { return rows > 0 ? (size_t)rows * sizeof(BracketState) : 0; }
+
+namespace {
+// the constraint's own arguments; rows > 0 and vocab > 0 are the caller's checks
+int check_constraint(int rows, int vocab, int end_id, const uint8_t* cls, const void* state, size_t state_bytes) {
+    if (end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
+    if (state_bytes < (size_t)rows * sizeof(BracketState)) return I2L_ERR_WORKSPACE;
+    return I2L_OK;
+}
+}  // namespace
+
+extern "C" int i2l_greedy_decode_constrained(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                             const int32_t* tok0, const float* h0, const float* c0, float temperature,
+                                             int select, int stop, int end_id, int32_t* ids_out, float* logits_out,
+                                             float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
+                                             uint32_t* resident_flag, uint32_t resident_value, const uint8_t* cls,
+                                             void* state, size_t state_bytes, i2l_stream_t stream) {
+    (void)flags;
+    int rc = check_weights(w);
+    if (rc != I2L_OK) return rc;
+    if (select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
+    if (rows <= 0 || steps <= 0) return I2L_ERR_ARG;
+    rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes);
+    if (rc != I2L_OK) return rc;
+    const ConstrainRule con{cls, static_cast<BracketState*>(state)};
+    return launch_batched(w, workspace, rows, steps, tok0, nullptr, h0, c0, temperature, select, stop, end_id, nullptr, &con,
+                          ids_out, logits_out, h_out, c_out, scratch, scratch_bytes, resident_flag, resident_value, stream);
+}
+
+extern "C" int i2l_sample_decode_constrained(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                             const int32_t* tok0, const float* h0, const float* c0, float temperature,
+                                             int top_k, float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out,
+                                             float* probs_out, float* h_out, float* c_out, void* scratch,
+                                             size_t scratch_bytes, int flags, const uint8_t* cls, void* state,
+                                             size_t state_bytes, i2l_stream_t stream) {
+    (void)flags;
+    int rc = check_weights(w);
+    if (rc != I2L_OK) return rc;
+    if (!sample_args_ok(temperature, top_k, top_p)) return I2L_ERR_ARG;
+    if (rows <= 0 || steps <= 0) return I2L_ERR_ARG;
+    if (w->vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
+    rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes);
+    if (rc != I2L_OK) return rc;
+    const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
+    const ConstrainRule con{cls, static_cast<BracketState*>(state)};
+    return launch_batched(w, workspace, rows, steps, tok0, nullptr, h0, c0, temperature, I2L_SELECT_SAMPLE, stop, end_id,
+                          &rule, &con, ids_out, nullptr, h_out, c_out, scratch, scratch_bytes, nullptr, 0, stream);
+}
+
+extern "C" int i2l_constrained_pick_logits(const float* logits, int ld, int rows, int vocab, float temperature, int select,
+                                           int top_k, float top_p, uint64_t seed, int step, int steps, const uint8_t* cls,
+                                           int end_id, void* state, int32_t* ids_out, float* probs_out,
+                                           uint8_t* allowed_out, i2l_stream_t stream) {
+    const bool greedy = top_k == 0 && top_p == 0.f;
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return I2L_ERR_ARG;
+    if (greedy && select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
+    if (rows <= 0 || vocab <= 0 || ld < vocab || step < 0 || steps <= 0 || step >= steps) return I2L_ERR_ARG;
+    if (!greedy && vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
+    if (!logits || !ids_out || end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
+    const ConstrainRule con{cls, static_cast<BracketState*>(state)};
+    const int use_temp = (temperature != 1.0f) ? 1 : 0, rem = steps - step - 1;
+    if (greedy) {
+        hipLaunchKernelGGL(pick_constrained_select_kernel, dim3(i2l_cdiv(rows, DB_NT / 64)), dim3(DB_NT), 0, i2l_s(stream),
+                           logits, ld, rows, vocab, temperature, use_temp, select, con, end_id, rem, ids_out, allowed_out);
+    } else {
+        const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
+        hipLaunchKernelGGL(pick_constrained_sample_kernel, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab,
+                           temperature, use_temp, rule, (unsigned)step, con, end_id, rem, ids_out, allowed_out);
+    }
     I2L_CHECK_LAUNCH();
     return I2L_OK;
 }

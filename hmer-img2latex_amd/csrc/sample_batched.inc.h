@@ -135,15 +135,25 @@ __device__ __forceinline__ void bitonic_desc(unsigned long long* key, int N, int
     }
 }
 
+// every column may be drawn: the plain kernels' `allow`
+struct AllowAll {
+    __device__ __forceinline__ bool operator()(int) const { return true; }
+};
+
 // One row: x[0, V) raw logits, u the row's uniform of this step.  Every thread returns the pick; po (V floats or null)
-// receives the final distribution.  V <= SB_MAXV, blockDim.x == NT.
+// receives the final distribution.  V <= SB_MAXV, blockDim.x == NT.  A column v with !allow(v) enters as -INFINITY: its
+// probability is exactly 0 and the others renormalise (decode_constrained.inc.h); the result is 0x7fffffff or a
+// disallowed column only when no allowed column holds a finite logit.
+template <class Allow>
 __device__ __forceinline__ int sample_row(const float* __restrict__ x, int V, float temperature, int use_temp, int top_k,
-                                          float top_p, float u, float* __restrict__ po, SampleLds& s, int tid) {
+                                          float top_p, float u, float* __restrict__ po, SampleLds& s, int tid,
+                                          const Allow& allow) {
     float best[1] = {-INFINITY};
     int besti[1] = {0x7fffffff};
     for (int v = tid; v < V; v += NT) {
         float a = x[v];
         if (use_temp) a = a / temperature;
+        if (!allow(v)) a = -INFINITY;
         s.q[v] = a;
         if (a > best[0]) { best[0] = a; besti[0] = v; }
     }
@@ -214,7 +224,7 @@ __global__ __launch_bounds__(NT) void sample_batched_kernel(BatchedParams p, Sam
     const int V = p.w.V, row = blockIdx.x, tid = threadIdx.x;
     float* po = r.probs ? r.probs + ((size_t)row * p.T + t) * V : nullptr;
     const int pick = sample_row(p.lg + (size_t)row * p.w.Vp, V, p.temperature, p.use_temp, r.top_k, r.top_p,
-                                uniform01(r.seed, (unsigned)row, (unsigned)t), po, s, tid);
+                                uniform01(r.seed, (unsigned)row, (unsigned)t), po, s, tid, AllowAll{});
     if (tid == 0) commit_token_batched(p, row, t, pick);
 }
 
@@ -226,6 +236,6 @@ __global__ __launch_bounds__(NT) void sample_logits_kernel(const float* __restri
     const int row = blockIdx.x, tid = threadIdx.x;
     float* po = r.probs ? r.probs + (size_t)row * V : nullptr;
     const int pick = sample_row(logits + (size_t)row * ld, V, temperature, use_temp, r.top_k, r.top_p,
-                                uniform01(r.seed, (unsigned)row, step), po, s, tid);
+                                uniform01(r.seed, (unsigned)row, step), po, s, tid, AllowAll{});
     if (tid == 0) ids[row] = pick;
 }

@@ -89,11 +89,14 @@ def _train_flags(train_kernel: str) -> int:
 
 
 def predict(checkpoint_path: str, image_path: str, beam_size: int = 0, max_length: int = 141, temperature: float = 1.0,
-            top_k: int = 0, top_p: float = 0.0, device: Optional[str] = None, decode_kernel: str = "auto") -> str:
-    """cli.py:253-308: returns the LaTeX string the command prints.  ``decode_kernel``: see ``_decode_flags``."""
+            top_k: int = 0, top_p: float = 0.0, device: Optional[str] = None, decode_kernel: str = "auto",
+            well_formed: bool = False) -> str:
+    """cli.py:253-308: returns the LaTeX string the command prints.  ``decode_kernel``: see ``_decode_flags``.
+    ``well_formed``: the bracket-constrained decode (training/constraint.py): braces, \\left / \\right and \\begin / \\end
+    nest and the formula ends within ``max_length`` tokens."""
     from .training import Predictor
     predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device),
-                                          decode_flags=_decode_flags(decode_kernel))
+                                          decode_flags=_decode_flags(decode_kernel), well_formed=bool(well_formed))
     return predictor.predict(image=image_path, beam_size=beam_size, max_length=max_length, temperature=temperature,
                              top_k=top_k, top_p=top_p)
 
@@ -301,7 +304,8 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
 
 def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_size: int = 32,
              num_samples: Optional[int] = None, beam_size: int = 0, device: Optional[str] = None,
-             output_dir: str = "outputs", decode: Optional[str] = None, decode_kernel: str = "auto") -> Dict:
+             output_dir: str = "outputs", decode: Optional[str] = None, decode_kernel: str = "auto",
+             well_formed: bool = False) -> Dict:
     """cli.py:315-518 on the device: returns {"bleu", "levenshtein", "batch_size"} over the whole split -- the means over
     all pairs, as ``calculate_metrics`` on the reference's two lists computes them -- after printing the three result
     lines and writing ``predictions.json``.
@@ -312,7 +316,7 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
     unreadable file.  ``_prepare_image``'s other step, the bilinear resize of a tensor that is not 64 x 800, is not
     repeated: the loaders are built at the model's own input size, and the reference's encoder cannot run any other.
     ``decode``: "host" or "device", where the page files are decoded (``data.PageStore``); None: the checkpoint's
-    config key ``data.decode``, "host" when absent."""
+    config key ``data.decode``, "host" when absent.  ``well_formed``: as in ``predict``."""
     import json
     import warnings
     from pathlib import Path
@@ -323,7 +327,7 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
     experiment_name = Path(checkpoint_path).parent.parent.name              # cli.py:340-349: outputs/<experiment>/checkpoints/<file>
     config = torch.load(checkpoint_path, map_location="cpu", weights_only=False).get("config", {}) or {}
     predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=dev,
-                                          decode_flags=_decode_flags(decode_kernel))
+                                          decode_flags=_decode_flags(decode_kernel), well_formed=bool(well_formed))
     max_samples = {"train": None, "val": None, "test": None}
     if num_samples:
         max_samples[split] = num_samples
@@ -402,6 +406,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     p.add_argument("--device", default=None, help="Device to use for inference (cuda)")
     p.add_argument("--decode-kernel", choices=("auto", "batched"), default="auto",
                    help="(this package) decode kernel, greedy and --top-k / --top-p sampling: auto, or the step-batched matrix-core decode")
+    p.add_argument("--well-formed", action="store_true",
+                   help="(this package) bracket-constrained decode: { }, \\left \\right and \\begin \\end nest and the formula "
+                        "ends within the maximum length (nesting only: no arity, no semantics)")
     p.add_argument("--nbest", type=int, default=0,
                    help="(this package) with --beam-size K > 0: print the N best hypotheses, one key<TAB>latex line each, "
                         "in rank order (0: the single result as before)")
@@ -445,6 +452,9 @@ def main(argv: Optional[List[str]] = None) -> int:
                    help="(this package) decode kernel, greedy and --top-k / --top-p sampling: auto, or the step-batched matrix-core decode")
     e.add_argument("--decode", choices=("host", "device"), default=None,
                    help="(this package) decode the page files with PIL on the host or with the PNG kernel on the device")
+    e.add_argument("--well-formed", action="store_true",
+                   help="(this package) bracket-constrained decode: { }, \\left \\right and \\begin \\end nest and the formula "
+                        "ends within the maximum length (nesting only: no arity, no semantics)")
     v = sub.add_parser("vocab", help="(this package) Fit the vocabulary of a formulas file on the device and save it.")
     v.add_argument("formulas_file", help="Path to the formulas file, one formula per line")
     v.add_argument("out_path", help="Path to save the vocabulary to (LaTeXTokenizer.save's layout)")
@@ -453,6 +463,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     args = ap.parse_args(argv)
     if args.command == "predict" and args.nbest < 0:
         ap.error("--nbest must be >= 0")
+    if args.command == "predict" and args.well_formed and (args.nbest > 0 or args.beam_size > 0):
+        ap.error("--well-formed covers the greedy and sampling decode, not beam search")
     if args.command == "predict" and args.nbest > 0:
         if args.beam_size <= 0:
             ap.error("--nbest needs --beam-size above 0")
@@ -462,7 +474,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     if args.command == "predict":
         latex = predict(args.checkpoint_path, args.image_path, args.beam_size, args.max_length, args.temperature,
-                        args.top_k, args.top_p, args.device, args.decode_kernel)
+                        args.top_k, args.top_p, args.device, args.decode_kernel, args.well_formed)
         print("Generated LaTeX:")
         print(latex)
         return 0
@@ -471,7 +483,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     if args.command == "evaluate":
         evaluate(args.checkpoint_path, args.data_dir, args.split, args.batch_size, args.num_samples, args.beam_size,
-                 args.device, args.output_dir, args.decode, args.decode_kernel)
+                 args.device, args.output_dir, args.decode, args.decode_kernel, args.well_formed)
         return 0
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,

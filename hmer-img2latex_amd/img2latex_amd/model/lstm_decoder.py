@@ -188,8 +188,11 @@ class LSTMDecoder(nn.Module):
                   temperature: float = 1.0, select: int = _lib.SELECT_LOGITS, stop: int = _lib.STOP_NONE,
                   end_id: int = -1, want_ids: bool = True, want_logits: bool = False,
                   want_state: bool = False, reuse_weight_images: bool = True, rows_per_workgroup: int = 0,
-                  flags: int = 0, prepared=None, resident=None):
+                  flags: int = 0, prepared=None, resident=None, constraint=None):
         """prepare + one persistent i2l_greedy_decode launch.  Returns (ids, logits, (h, c)).
+        ``constraint`` = a ``training.constraint.BracketTable``: the bracket-constrained step-batched decode
+        (i2l_greedy_decode_constrained) whatever the flags say -- a grouped-shape decoder is routed to the step-batched
+        kernels too; every row nests its groups and ends on END within ``steps``.  Not with ``forced``.
         ``prepared`` = (w, keep, enc, workspace) of an earlier ``prepare(encoder_output, slot=...)`` whose completion the
         current stream already waits for: the launch uses that workspace and prepares nothing.
         ``resident`` = (int32 device tensor, value): the launch stores ``value`` there once its workgroups own their compute
@@ -221,6 +224,18 @@ class LSTMDecoder(nn.Module):
         all_flags = int(flags) | int(self.kernel_flags)
         res_ptr = None if resident is None else resident[0].data_ptr()
         res_val = 0 if resident is None else int(resident[1]) & 0xFFFFFFFF
+        if constraint is not None:
+            if forced is not None:
+                raise RuntimeError("img2latex_amd: a constrained decode takes no forced tokens")
+            cls, state, scratch, nbytes = self._constraint_buffers(constraint, rows, end_id, dev)
+            _lib.check(_lib.lib().i2l_greedy_decode_constrained(
+                ctypes.byref(w), ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
+                float(temperature), select, stop, int(end_id), _lib.ptr(ids), _lib.ptr(logits), _lib.ptr(h), _lib.ptr(c),
+                scratch.data_ptr(), nbytes, all_flags, res_ptr, res_val, cls.data_ptr(), state.data_ptr(), state.numel(),
+                _lib.stream_ptr()), "greedy_decode_constrained")
+            _lib.mark("decode")
+            del keep, scratch, state   # the caching allocator hands the blocks out again only in stream order
+            return ids, logits, ((h, c) if want_state else None)
         if all_flags & _lib.FLAG_DECODE_BATCHED:
             # step-batched matrix-core path (decode_batched.inc.h): its scratch lives for this call only, on this stream
             nbytes = _lib.lib().i2l_decode_batched_scratch_bytes(rows, self.vocab_size, self.hidden_dim, self.lstm_layers)
@@ -244,6 +259,18 @@ class LSTMDecoder(nn.Module):
         _lib.mark("decode")
         del keep
         return ids, logits, ((h, c) if want_state else None)
+
+    def _constraint_buffers(self, constraint, rows: int, end_id: int, dev):
+        """(class bytes on ``dev``, the rows' 16 state bytes, the step-batched scratch, its size) of one constrained call."""
+        if constraint.vocab != self.vocab_size:
+            raise RuntimeError(f"img2latex_amd: the constraint's table has {constraint.vocab} columns, the decoder's "
+                               f"vocabulary {self.vocab_size}")
+        constraint._end(end_id)                            # inside the table, and neutral there
+        nbytes = _lib.lib().i2l_decode_batched_scratch_bytes(rows, self.vocab_size, self.hidden_dim, self.lstm_layers)
+        if nbytes == 0:
+            raise RuntimeError("img2latex_amd: decoder dimensions not supported by the step-batched decode")
+        state = torch.empty(_lib.lib().i2l_bracket_state_bytes(rows), dtype=torch.uint8, device=dev)   # zeroed by the call
+        return constraint.device(dev), state, torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
 
     def halves_supported(self, stop: int = _lib.STOP_NONE) -> bool:
         """True where ``decode_halves`` has a kernel: the 16-member grouped decode's dimensions, no sticky stop."""
@@ -284,10 +311,12 @@ class LSTMDecoder(nn.Module):
 
     def sample_steps(self, encoder_output: torch.Tensor, steps: int, tok0: torch.Tensor, temperature: float,
                      top_k: int, top_p: float, seed: int, stop: int = _lib.STOP_STICKY, end_id: int = -1,
-                     hidden: Optional[Hidden] = None, want_probs: bool = False, flags: int = 0, want_state: bool = False):
+                     hidden: Optional[Hidden] = None, want_probs: bool = False, flags: int = 0, want_state: bool = False,
+                     constraint=None):
         """prepare + one i2l_sample_decode launch (predictor.py:295-331), or with ``(flags | self.kernel_flags) &
         FLAG_DECODE_BATCHED`` the step-batched i2l_sample_decode_batched.  Returns (ids, probs or None), with
-        ``want_state`` (ids, probs or None, (h, c))."""
+        ``want_state`` (ids, probs or None, (h, c)).  ``constraint`` = a BracketTable: the bracket-constrained
+        i2l_sample_decode_constrained, whatever the flags say (see ``run_steps``)."""
         w, keep, enc = self.prepare(encoder_output)
         rows, dev = enc.shape[0], enc.device
         tok0 = _lib.require_gpu(tok0, "tok0", torch.int32)
@@ -301,7 +330,15 @@ class LSTMDecoder(nn.Module):
             h = torch.empty((self.lstm_layers, rows, self.hidden_dim), dtype=torch.float32, device=dev)
             c = torch.empty_like(h)
         all_flags = int(flags) | int(self.kernel_flags)
-        if all_flags & _lib.FLAG_DECODE_BATCHED:
+        if constraint is not None:
+            cls, state, scratch, nbytes = self._constraint_buffers(constraint, rows, end_id, dev)
+            _lib.check(_lib.lib().i2l_sample_decode_constrained(
+                ctypes.byref(w), self._ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
+                float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, stop, int(end_id),
+                ids.data_ptr(), _lib.ptr(probs), _lib.ptr(h), _lib.ptr(c), scratch.data_ptr(), nbytes, all_flags,
+                cls.data_ptr(), state.data_ptr(), state.numel(), _lib.stream_ptr()), "sample_decode_constrained")
+            del scratch, state
+        elif all_flags & _lib.FLAG_DECODE_BATCHED:
             # step-batched matrix-core path (sample_batched.inc.h): its scratch lives for this call only, on this stream
             nbytes = _lib.lib().i2l_decode_batched_scratch_bytes(rows, self.vocab_size, self.hidden_dim, self.lstm_layers)
             if nbytes == 0:
@@ -343,6 +380,38 @@ class LSTMDecoder(nn.Module):
             logits.data_ptr(), int(ld), rows, V, float(temperature), int(top_k), float(top_p),
             int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), ids.data_ptr(), _lib.ptr(probs), _lib.stream_ptr()), "sample_logits")
         return ids, probs
+
+    @staticmethod
+    def constrained_pick_logits(logits: torch.Tensor, constraint, end_id: int, state: torch.Tensor, step: int, steps: int,
+                                temperature: float = 1.0, select: int = _lib.SELECT_LOGITS, top_k: int = 0,
+                                top_p: float = 0.0, seed: int = 0, want_probs: bool = False, want_allowed: bool = False):
+        """Step ``step`` of ``steps`` of the bracket-constrained selection applied once to (rows, V) fp32 logits on the
+        device (i2l_constrained_pick_logits; a row may be a strided view with unit column stride): the arg max under
+        ``select`` when ``top_k == 0 and top_p == 0``, else a draw as ``sample_logits``.  ``state`` is the rows' (rows * 16)
+        uint8 device tensor, zeroed by the caller before step 0; the call advances it.  Returns (ids (rows) int32, probs
+        (rows, V) or None, allowed (rows, V) uint8 or None)."""
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or not logits.is_cuda or logits.dtype != torch.float32:
+            raise RuntimeError("img2latex_amd: constrained_pick_logits needs a (rows, V) fp32 tensor on the ROCm device")
+        rows, V = logits.shape
+        if constraint.vocab != V:
+            raise RuntimeError(f"img2latex_amd: the constraint's table has {constraint.vocab} columns, the logits {V}")
+        constraint._end(end_id)
+        if state.dtype != torch.uint8 or state.device != logits.device or not state.is_contiguous() \
+                or state.numel() < _lib.lib().i2l_bracket_state_bytes(rows):
+            raise RuntimeError(f"img2latex_amd: state must be a contiguous uint8 device tensor of {16 * rows} bytes")
+        if logits.stride(1) != 1 or (rows > 1 and logits.stride(0) < V):
+            logits = logits.contiguous()
+        ld = max(V, logits.stride(0))
+        sampling = int(top_k) != 0 or float(top_p) != 0.0
+        ids = torch.empty((rows,), dtype=torch.int32, device=logits.device)
+        probs = torch.empty((rows, V), dtype=torch.float32, device=logits.device) if want_probs and sampling else None
+        allowed = torch.empty((rows, V), dtype=torch.uint8, device=logits.device) if want_allowed else None
+        _lib.check(_lib.lib().i2l_constrained_pick_logits(
+            logits.data_ptr(), int(ld), rows, V, float(temperature), int(select), int(top_k), float(top_p),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(steps), constraint.device(logits.device).data_ptr(), int(end_id),
+            state.data_ptr(), ids.data_ptr(), _lib.ptr(probs), _lib.ptr(allowed), _lib.stream_ptr()),
+            "constrained_pick_logits")
+        return ids, probs, allowed
 
     # ------------------------------------------------------------------ reference surface
     def forward(self, encoder_output: torch.Tensor, target_sequence: torch.Tensor, hidden=None) -> torch.Tensor:

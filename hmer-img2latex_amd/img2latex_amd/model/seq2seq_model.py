@@ -87,9 +87,11 @@ class Seq2SeqModel(nn.Module):
 
     # ---------------------------------------------------------------- inference
     def inference(self, image: torch.Tensor, start_token_id: int, end_token_id: int, max_length: int = None,
-                  temperature: float = None, top_k: int = None, top_p: float = None, beam_size: int = None):
+                  temperature: float = None, top_k: int = None, top_p: float = None, beam_size: int = None,
+                  constraint=None):
         """seq2seq.py:124-190: List[int] for one image, List[List[int]] for a batch.  (A ResNet encoder runs the eval
-        trunk its ``eval_precision`` selects; nothing here depends on which.)"""
+        trunk its ``eval_precision`` selects; nothing here depends on which.)  ``constraint`` = a BracketTable: the greedy
+        search is the bracket-constrained one (LSTMDecoder.run_steps); beam search has no constrained form."""
         max_length = 150 if max_length is None else max_length
         temperature = 1.0 if temperature is None else temperature
         top_k = 0 if top_k is None else top_k
@@ -99,16 +101,20 @@ class Seq2SeqModel(nn.Module):
         if encoder_output.dim() == 1:
             encoder_output = encoder_output.unsqueeze(0)
         if beam_size > 0:
+            if constraint is not None:
+                raise RuntimeError("img2latex_amd: beam search has no bracket-constrained form; use beam_size=0")
             return self._beam_search(encoder_output, start_token_id, end_token_id, max_length, beam_size)
-        return self._greedy_search(encoder_output, start_token_id, end_token_id, max_length, temperature, top_k, top_p)
+        return self._greedy_search(encoder_output, start_token_id, end_token_id, max_length, temperature, top_k, top_p,
+                                   constraint=constraint)
 
     def greedy_ids(self, encoder_output: torch.Tensor, start_token_id: int, end_token_id: int, max_length: int,
                    temperature: float = 1.0, stop: int = _lib.STOP_NONE, select: int = _lib.SELECT_LOGITS,
-                   want_logits: bool = False, rows_per_workgroup: int = 0, flags: int = 0, prepared=None, resident=None):
+                   want_logits: bool = False, rows_per_workgroup: int = 0, flags: int = 0, prepared=None, resident=None,
+                   constraint=None):
         """Device-side greedy loop; returns (ids (B,T) int32 on device, logits or None).  ``flags``:
         _lib.FLAG_DECODE_GROUP8 / _GROUP16 select the 8-member (vector ALUs) / 16-member (matrix cores) grouped kernels (the
         ones that share a CU with a conv workgroup);
-        ``prepared`` / ``resident``: see LSTMDecoder.run_steps."""
+        ``prepared`` / ``resident`` / ``constraint``: see LSTMDecoder.run_steps."""
         B = encoder_output.shape[0]
         key = (B, int(start_token_id), encoder_output.device)
         if getattr(self, "_tok0_key", None) != key:               # the START column: built once per batch shape
@@ -118,34 +124,36 @@ class Seq2SeqModel(nn.Module):
         ids, logits, _ = self.decoder.run_steps(encoder_output, max_length, tok0, temperature=temperature,
                                                 select=select, stop=stop, end_id=end_token_id,
                                                 want_logits=want_logits, rows_per_workgroup=rows_per_workgroup,
-                                                flags=flags, prepared=prepared, resident=resident)
+                                                flags=flags, prepared=prepared, resident=resident,
+                                                constraint=constraint)
         return ids, logits
 
     def greedy_ids_host(self, encoder_output: torch.Tensor, start_token_id: int, end_token_id: int, max_length: int,
                         temperature: float = 1.0, stop: int = _lib.STOP_NONE, select: int = _lib.SELECT_LOGITS,
-                        flags: int = 0) -> torch.Tensor:
+                        flags: int = 0, constraint=None) -> torch.Tensor:
         """greedy_ids + the ONE device->host copy of the search, with the timeout fallback both callers
         (_greedy_search and Predictor.predict_batch_ids) share: the grouped kernel needs its 4 members resident
         together; on a GPU shared with other work (fewer than 32 free CUs) a bounded wait can expire (ids -3) ->
         run the row-per-workgroup HIP kernel, which needs no partner."""
         ids, _ = self.greedy_ids(encoder_output, start_token_id, end_token_id, max_length, temperature, stop=stop,
-                                 select=select, flags=flags)
+                                 select=select, flags=flags, constraint=constraint)
         ids = ids.cpu()
         if _lib.ids_timed_out(ids):
             warnings.warn("img2latex_amd: grouped decode timed out (GPU oversubscribed?); "
                           "re-running on the row-per-workgroup kernel", RuntimeWarning)
             ids, _ = self.greedy_ids(encoder_output, start_token_id, end_token_id, max_length, temperature, stop=stop,
-                                     select=select, rows_per_workgroup=1, flags=flags)
+                                     select=select, rows_per_workgroup=1, flags=flags, constraint=constraint)
             ids = _lib.check_ids(ids.cpu())
         return ids
 
     def _greedy_search(self, encoder_output: torch.Tensor, start_token_id: int, end_token_id: int,
-                       max_length: int, temperature: float, top_k: int, top_p: float):
+                       max_length: int, temperature: float, top_k: int, top_p: float, constraint=None):
         """seq2seq.py:192-232.  top_k / top_p are accepted and ignored, as in the reference.
         The loop stops when ALL rows emit END in the same step (:220); the kernel runs the
         rows independently, so that step is located in the ids afterwards."""
         B = encoder_output.shape[0]
-        ids = self.greedy_ids_host(encoder_output, start_token_id, end_token_id, max_length, temperature).numpy()
+        ids = self.greedy_ids_host(encoder_output, start_token_id, end_token_id, max_length, temperature,
+                                   constraint=constraint).numpy()
         # host post-processing in numpy: one thread, no dispatch (torch would fan a 38 k-element compare out to every
         # host core: measured 10 ms per batch on the 16-core GPU box against 1.4 ms for the whole device path)
         all_end = (ids == end_token_id).all(axis=0)

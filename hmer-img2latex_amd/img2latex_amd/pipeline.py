@@ -57,8 +57,14 @@ class GreedyPipeline:
                  encoder_priority: int = 0, hold_encoder: Optional[bool] = None, wait_timeout_us: float = 20000.0,
                  clear_early: bool = True,
                  stop: int = _lib.STOP_NONE, select: int = _lib.SELECT_LOGITS, detokenize=None,
-                 split_decode: Optional[bool] = None):
+                 split_decode: Optional[bool] = None, constraint=None):
         self.model = model
+        # constraint (training.constraint.BracketTable or None): the bracket-constrained decode.  It exists on the step-batched
+        # kernels only, so a pipeline that asks for a grouped co-resident decode refuses it instead of dropping it.
+        self.constraint = constraint
+        if constraint is not None and (int(decode_flags) & (_lib.FLAG_DECODE_GROUP8 | _lib.FLAG_DECODE_GROUP16) or split_decode):
+            raise RuntimeError("img2latex_amd: GreedyPipeline's grouped co-resident decode (FLAG_DECODE_GROUP8 / _GROUP16, "
+                               "split_decode) has no bracket-constrained form; pass decode_flags=FLAG_DECODE_BATCHED")
         self.start, self.end, self.max_length, self.temperature = start_token_id, end_token_id, max_length, temperature
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -201,7 +207,8 @@ class GreedyPipeline:
                                                stop=self.stop, select=self.select,
                                                rows_per_workgroup=self.rows_per_workgroup, flags=dflags,
                                                prepared=prepared,
-                                               resident=(self._resident, seq) if self.hold_encoder else None)
+                                               resident=(self._resident, seq) if self.hold_encoder else None,
+                                               constraint=self.constraint)
                 if rec is not None:
                     rec["dec_end"].record(dec_stream)
                 b = _Batch(seq - 1, self._host_buffer(ids.shape), enc, slot)
@@ -380,7 +387,8 @@ class GreedyPipeline:
                           "row-per-workgroup kernel", RuntimeWarning)
             with torch.no_grad():
                 ids, _ = self.model.greedy_ids(enc, self.start, self.end, self.max_length, self.temperature,
-                                               stop=self.stop, select=self.select, rows_per_workgroup=1)
+                                               stop=self.stop, select=self.select, rows_per_workgroup=1,
+                                               constraint=self.constraint)
             host.copy_(ids)
             if text is not None:                     # the strings of the first attempt are those of the -3 rows: again
                 dev_text = self.detok.launch(ids, self.end)

@@ -68,9 +68,9 @@ class TokenTable:
         """Take a fitted vocabulary (training/vocab.py): the maps and the four special ids anew, as ``_init_special_tokens``
         + ``fit`` leave them, this object's cached device tables dropped (they hold the old vocabulary), and the
         reference's warning about rows longer than ``max_sequence_length`` (tokenizer.py:106-113)."""
-        from . import tokenizer as _tokenizer
+        from . import constraint as _constraint, tokenizer as _tokenizer
         self._set_vocabulary(fitted.token_to_id)
-        for cache in (_TABLES, _tokenizer._TABLES):
+        for cache in (_TABLES, _tokenizer._TABLES, _constraint._TABLES):
             cache.pop(self, None)
         if self.max_sequence_length is not None and fitted.longest_row > self.max_sequence_length:
             warnings.warn(f"Found sequences of length {fitted.longest_row}, which is longer than max_sequence_length "
@@ -241,10 +241,14 @@ def _is_pil(obj) -> bool:
 
 class Predictor:
     def __init__(self, model: Seq2SeqModel, tokenizer, device: Optional[torch.device] = None,
-                 model_type: str = "cnn_lstm", decode_flags: int = 0):
+                 model_type: str = "cnn_lstm", decode_flags: int = 0, well_formed=False):
         # decode_flags (_lib.FLAG_DECODE_BATCHED: the step-batched matrix-core decode) are OR-ed into the flags of every
         # greedy and every sampling decode this predictor launches; 0 = the automatic kernel choice
         self.decode_flags = int(decode_flags)
+        # well_formed: every greedy and sampling decode of this predictor is the bracket-constrained one (training/constraint.py:
+        # groups nest, END within max_length) -- True: the table BracketTable.from_tokenizer gives, or a BracketTable of the
+        # caller's; each call's own ``well_formed=`` overrides it.  Off by default: nothing changes without it.
+        self.well_formed = well_formed
         self.device = torch.device("cuda") if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("img2latex_amd: Predictor runs on a ROCm device only (no CPU fallback)")
@@ -255,7 +259,7 @@ class Predictor:
 
     @classmethod
     def from_checkpoint(cls, checkpoint_path: str, device: Optional[torch.device] = None,
-                        decode_flags: int = 0) -> "Predictor":
+                        decode_flags: int = 0, well_formed=False) -> "Predictor":
         checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
         config = checkpoint.get("config", {})
         tcfg = checkpoint.get("tokenizer_config", {})
@@ -263,7 +267,13 @@ class Predictor:
         model = model_from_checkpoint_config(config, tokenizer.vocab_size)
         model.load_state_dict(checkpoint["model_state_dict"])               # predictor.py:129, strict
         return cls(model=model, tokenizer=tokenizer, device=device,
-                   model_type=config.get("model", {}).get("name", "cnn_lstm"), decode_flags=decode_flags)
+                   model_type=config.get("model", {}).get("name", "cnn_lstm"), decode_flags=decode_flags,
+                   well_formed=well_formed)
+
+    def _constraint(self, well_formed=None):
+        """The BracketTable of a call: its own ``well_formed`` (None: the predictor's), True meaning the tokenizer's table."""
+        from .constraint import as_table
+        return as_table(self.well_formed if well_formed is None else well_formed, self.tokenizer)
 
     # ------------------------------------------------------------------ predictor.py:396-521
     def _prepare_image(self, image) -> torch.Tensor:
@@ -335,32 +345,33 @@ class Predictor:
         return t.to(self.device, dtype=torch.float32).contiguous()
 
     def predict_batch_ids(self, images, max_length: int = 141, temperature: float = 1.0, top_k: int = 0,
-                          top_p: float = 0.0, seed: Optional[int] = None) -> List[List[int]]:
+                          top_p: float = 0.0, seed: Optional[int] = None, well_formed=None) -> List[List[int]]:
         """Token ids of the batched loop (predictor.py:254-361): START kept, cut before the first END.
         Sampling (multinomial over the top-k / top-p masked softmax) iff temperature > 0 and
         (top_k > 0 or top_p > 0), exactly the reference's condition (:330); argmax of softmax otherwise."""
         x = self._as_batch(images)
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
+        constraint = self._constraint(well_formed)
         with torch.no_grad():
             enc = self.model.encoder(x)
             if temperature > 0 and (top_k > 0 or top_p > 0.0):
-                ids = _lib.check_ids(self._sample_ids(enc, max_length, temperature, top_k, top_p, seed).cpu())
+                ids = _lib.check_ids(self._sample_ids(enc, max_length, temperature, top_k, top_p, seed, constraint).cpu())
             else:       # same timeout fallback as Seq2SeqModel._greedy_search
                 ids = self.model.greedy_ids_host(enc, start, end, max_length, temperature, stop=_lib.STOP_STICKY,
-                                                 select=_lib.SELECT_SOFTMAX, flags=self.decode_flags)
+                                                 select=_lib.SELECT_SOFTMAX, flags=self.decode_flags, constraint=constraint)
         a = ids.numpy()
         stop = (a == end) | (a < 0)                           # first END, or the kernel's "row finished" filler
         lens = np.where(stop.any(axis=1), stop.argmax(axis=1), a.shape[1]).tolist()
         return [[start] + row[:n] for row, n in zip(a.tolist(), lens)]
 
-    def _sample_ids(self, enc, max_length, temperature, top_k, top_p, seed) -> torch.Tensor:
+    def _sample_ids(self, enc, max_length, temperature, top_k, top_p, seed, constraint=None) -> torch.Tensor:
         """The sampling branch of the batched loop (predictor.py:295-331): (B, max_length) ids on the device."""
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         tok0 = torch.full((enc.shape[0],), int(self.tokenizer.start_token_id), dtype=torch.int32, device=enc.device)
         ids, _ = self.model.decoder.sample_steps(enc, max_length, tok0, temperature, top_k, top_p, seed,
                                                  stop=_lib.STOP_STICKY, end_id=self.tokenizer.end_token_id,
-                                                 flags=self.decode_flags)
+                                                 flags=self.decode_flags, constraint=constraint)
         return ids
 
     def _greedy_strings(self, table: DetokenizeTable, enc, max_length, temperature, **loop) -> List[str]:
@@ -379,19 +390,20 @@ class Predictor:
             _lib.check_ids(first)
         return texts
 
-    def _batch_strings(self, table: DetokenizeTable, x: torch.Tensor, max_length, temperature, top_k, top_p, seed) -> List[str]:
+    def _batch_strings(self, table: DetokenizeTable, x: torch.Tensor, max_length, temperature, top_k, top_p, seed,
+                       constraint=None) -> List[str]:
         """``predict_batch_ids`` + START / END stripping + ``tokenizer.decode`` (predictor.py:384-391) with the ids staying
         on the device: the same loop launches, then i2l_detokenize (cut before END, drop the special ids, join)."""
         x = self._as_batch(x)
         with torch.no_grad():
             enc = self.model.encoder(x)
             if temperature > 0 and (top_k > 0 or top_p > 0.0):
-                ids = self._sample_ids(enc, max_length, temperature, top_k, top_p, seed)
+                ids = self._sample_ids(enc, max_length, temperature, top_k, top_p, seed, constraint)
                 texts, first = table.decode_now(ids, self.tokenizer.end_token_id)
                 _lib.check_ids(first)
                 return texts
             return self._greedy_strings(table, enc, max_length, temperature, stop=_lib.STOP_STICKY,
-                                        select=_lib.SELECT_SOFTMAX)
+                                        select=_lib.SELECT_SOFTMAX, constraint=constraint)
 
     def predict_ids_stream(self, batches, max_length: int = 141, temperature: float = 1.0):
         """``predict_batch_ids`` (the greedy branch: argmax of softmax, sticky stop) for a STREAM of image batches, through
@@ -402,25 +414,29 @@ class Predictor:
         "fp32"`` the features of the two paths are bit-identical."""
         return self._stream(batches, max_length, temperature, None)
 
-    def predict_strings_stream(self, batches, max_length: int = 141, temperature: float = 1.0):
+    def predict_strings_stream(self, batches, max_length: int = 141, temperature: float = 1.0, well_formed=None):
         """``predict_ids_stream`` with the strings built on the device: per batch exactly
         ``[tokenizer.decode(seq[1:]) for seq in <that batch of predict_ids_stream>]``.  The pipeline runs i2l_detokenize
         behind each decode and copies the packed bytes + row offsets beside the ids; the host slices them.  A tokenizer
-        without a device image (``token_image`` gives None) takes the host ``decode`` on the id stream."""
+        without a device image (``token_image`` gives None) takes the host ``decode`` on the id stream.  ``well_formed``:
+        the bracket-constrained decode; the pipeline then runs the step-batched kernels, not the grouped co-resident ones."""
         table = detokenize_table(self.tokenizer, self.device)
+        constraint = self._constraint(well_formed)
         if table is None:
-            for seqs in self._stream(batches, max_length, temperature, None):
+            for seqs in self._stream(batches, max_length, temperature, None, constraint):
                 yield [self.tokenizer.decode(seq[1:]) for seq in seqs]
             return
-        yield from self._stream(batches, max_length, temperature, table)
+        yield from self._stream(batches, max_length, temperature, table, constraint)
 
-    def _stream(self, batches, max_length, temperature, table):
+    def _stream(self, batches, max_length, temperature, table, constraint=None):
         from ..pipeline import GreedyPipeline
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
         n_enc = 2 if hasattr(self.model.encoder, "_trunk_train") else 1      # ResNet trunk: two in flight
+        # a constrained decode is a step-batched one: the grouped co-resident kernels have no constrained form
+        group = _lib.FLAG_DECODE_GROUP16 if constraint is None else _lib.FLAG_DECODE_BATCHED
         pipe = GreedyPipeline(self.model, start, end, max_length, temperature, rows_per_workgroup=0,
-                              decode_flags=_lib.FLAG_DECODE_GROUP16 | self.decode_flags, decode_priority=-1, encoder_streams=n_enc,
-                              stop=_lib.STOP_STICKY, select=_lib.SELECT_SOFTMAX, detokenize=table)
+                              decode_flags=group | self.decode_flags, decode_priority=-1, encoder_streams=n_enc,
+                              stop=_lib.STOP_STICKY, select=_lib.SELECT_SOFTMAX, detokenize=table, constraint=constraint)
 
         def finish(ids_host):
             a = ids_host.numpy()
@@ -440,7 +456,7 @@ class Predictor:
             pipe.close()                                     # gives its decoder workspaces back
 
     def evaluate_batch(self, images, targets: Union[torch.Tensor, Sequence[str]], max_length: Optional[int] = None,
-                       return_strings: bool = False) -> Dict:
+                       return_strings: bool = False, well_formed=None) -> Dict:
         """One batch of the reference's ``evaluate`` command (cli.py:449-495) with every stage on the device and
         the token ids never leaving HBM between them:
 
@@ -459,10 +475,11 @@ class Predictor:
         ``tokenizer.decode`` of every row of "pred_ids", built by i2l_detokenize in the same chain (from the decode's ids
         under the compaction's own cut and drop rule: the compacted rows are zero-padded and the kernel takes no
         lengths) and copied beside the statistics; a tokenizer without a device image decodes "pred_ids" on the host."""
-        return self._evaluate_finish(self._evaluate_launch(images, targets, max_length, return_strings=return_strings))
+        return self._evaluate_finish(self._evaluate_launch(images, targets, max_length, return_strings=return_strings,
+                                                           constraint=self._constraint(well_formed)))
 
     def evaluate_stream(self, batches, max_length: Optional[int] = None, lookahead: int = 2, return_strings: bool = False,
-                        return_statistics: bool = False):
+                        return_statistics: bool = False, well_formed=None):
         """``evaluate_batch`` over an iterable of (images, targets), one result per batch in order, software-pipelined:
         the host work of batch i+1 (shape pass, packing the ragged pages into pinned memory, their upload on a side
         stream) runs while the device is still busy with batch i, and the host only waits for batch i's statistics
@@ -485,13 +502,15 @@ class Predictor:
 
         ``return_strings``: as in ``evaluate_batch`` ("pred_text").  ``return_statistics``: every result also carries
         "statistics", a host copy of its (B, 9) int32 statistics rows; ``metrics.metrics_from_packed`` of the rows of all
-        batches, concatenated, gives the means over all pairs of a split (not means of batch means)."""
+        batches, concatenated, gives the means over all pairs of a split (not means of batch means).  ``well_formed``: the
+        bracket-constrained decode (step-batched kernels) in the place of the grouped one, the schedule otherwise the same."""
         from collections import deque
         pending = deque()
+        constraint = self._constraint(well_formed)
         lookahead = max(1, min(int(lookahead), 2))           # the landing buffers / decoder slots rotate over 4 / 3
         for images, targets in batches:
             pending.append(self._evaluate_launch(images, targets, max_length, side_upload=True, coresident=True,
-                                                 return_strings=return_strings))
+                                                 return_strings=return_strings, constraint=constraint))
             pending[-1]["return_statistics"] = return_statistics
             if len(pending) > lookahead:
                 yield self._evaluate_finish(pending.popleft())
@@ -499,7 +518,8 @@ class Predictor:
             yield self._evaluate_finish(pending.popleft())
 
     def _evaluate_launch(self, images, targets, max_length: Optional[int], side_upload: bool = False,
-                         rows_per_workgroup: int = 0, coresident: bool = False, return_strings: bool = False):
+                         rows_per_workgroup: int = 0, coresident: bool = False, return_strings: bool = False,
+                         constraint=None):
         """Enqueues the whole chain of one batch and the copy of its statistics to pinned memory; no host wait.
         ``coresident``: two streams -- everything up to the decoder's prepare on the first, the decode and what follows on the
         second (see evaluate_stream); otherwise the whole chain on the current stream."""
@@ -594,7 +614,8 @@ class Predictor:
                                                select=_lib.SELECT_SOFTMAX, rows_per_workgroup=rows_per_workgroup,
                                                flags=(_lib.FLAG_DECODE_GROUP16 if coresident else 0) | self.decode_flags,
                                                prepared=prepared,
-                                               resident=(st["resident"], st["n"]) if coresident else None)
+                                               resident=(st["resident"], st["n"]) if coresident else None,
+                                               constraint=constraint)
             if coresident:
                 decoded = torch.cuda.Event()
                 decoded.record(s_dec)
@@ -635,7 +656,7 @@ class Predictor:
             done = torch.cuda.Event()
             done.record()
         return dict(host=host, done=done, keep=(packed, x, tgt), p_ids=p_ids, p_len=p_len, raw=(raw, targets, max_length),
-                    rows_per_workgroup=rows_per_workgroup, return_strings=return_strings, text=text)
+                    rows_per_workgroup=rows_per_workgroup, return_strings=return_strings, text=text, constraint=constraint)
 
     def _evaluate_finish(self, h) -> Dict:
         from . import metrics as M
@@ -644,7 +665,8 @@ class Predictor:
         if _lib.ids_timed_out(host[:, 9:10]) and h["rows_per_workgroup"] == 0:
             # the timeout fallback of Seq2SeqModel.greedy_ids_host: the row-per-workgroup kernel needs no partner
             raw, targets, max_length = h["raw"]
-            again = self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=1, return_strings=h["return_strings"])
+            again = self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=1, return_strings=h["return_strings"],
+                                          constraint=h["constraint"])
             again["return_statistics"] = h.get("return_statistics", False)
             return self._evaluate_finish(again)
         _lib.check_ids(host[:, 9:10])
@@ -652,7 +674,7 @@ class Predictor:
             # string targets at the stream's fixed width and a row was cut: once more with collate's width
             raw, targets, max_length = h["raw"]
             again = self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=h["rows_per_workgroup"],
-                                          return_strings=h["return_strings"])
+                                          return_strings=h["return_strings"], constraint=h["constraint"])
             again["return_statistics"] = h.get("return_statistics", False)
             return self._evaluate_finish(again)
         out = M.metrics_from_packed(host)
@@ -667,7 +689,8 @@ class Predictor:
         return out
 
     def predict_batch(self, images, beam_size: int = 0, max_length: int = 141, temperature: float = 1.0,
-                      top_k: int = 0, top_p: float = 0.0, batch_size: int = 16, seed: Optional[int] = None) -> List[str]:
+                      top_k: int = 0, top_p: float = 0.0, batch_size: int = 16, seed: Optional[int] = None,
+                      well_formed=None) -> List[str]:
         """predictor.py:205-394: every image through ``_prepare_image`` (:242), stacked, the batched greedy loop.  As in
         the reference beam_size is clamped to 0 (:231-235)."""
         if isinstance(images, torch.Tensor):
@@ -675,16 +698,18 @@ class Predictor:
         results: List[str] = []
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
         table = detokenize_table(self.tokenizer, self.device)               # None: the tokenizer keeps its host decode
+        constraint = self._constraint(well_formed)
         for i in range(0, len(images), batch_size):
             x = torch.stack([self._prepare_image(im) for im in images[i:i + batch_size]])
             if x.dim() == 5 and x.shape[1] == 1:                            # :254-257
                 x = x.squeeze(1)
             if table is not None:
                 results.extend(self._batch_strings(table, x, max_length, temperature, top_k, top_p,
-                                                   None if seed is None else seed + i))
+                                                   None if seed is None else seed + i, constraint))
                 continue
             for seq in self.predict_batch_ids(x, max_length, temperature, top_k, top_p,
-                                              None if seed is None else seed + i):
+                                              None if seed is None else seed + i,
+                                              well_formed=False if constraint is None else constraint):
                 if seq and seq[0] == start:                                 # :384-388
                     seq = seq[1:]
                 if seq and seq[-1] == end:
@@ -693,20 +718,22 @@ class Predictor:
         return results
 
     def predict(self, image, beam_size: int = 0, max_length: int = 141, temperature: float = 1.0, top_k: int = 0,
-                top_p: float = 0.0) -> str:
+                top_p: float = 0.0, well_formed=None) -> str:
         """predictor.py:139-203: one image (path / PIL / ndarray / tensor) through ``_prepare_image`` and
         Seq2SeqModel.inference (greedy; beam clamped to 0)."""
         x = self._prepare_image(image).to(self.device)
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
         table = detokenize_table(self.tokenizer, self.device)
+        constraint = self._constraint(well_formed)
         if table is not None and x.dim() == 4 and x.shape[0] == 1:
             # one image: _greedy_search's loop (logits arg max, no sticky stop; top_k / top_p ignored as there), the row
             # cut before its first END and decoded on the device
             with torch.no_grad():
-                return self._greedy_strings(table, self.model.encoder(x), max_length, temperature)[0]
+                return self._greedy_strings(table, self.model.encoder(x), max_length, temperature, constraint=constraint)[0]
         with torch.no_grad():
             seq = self.model.inference(image=x, start_token_id=start, end_token_id=end, max_length=max_length,
-                                       beam_size=0, temperature=temperature, top_k=top_k, top_p=top_p)
+                                       beam_size=0, temperature=temperature, top_k=top_k, top_p=top_p,
+                                       constraint=constraint)
         if seq and isinstance(seq[0], list):
             seq = seq[0]
         if seq and seq[0] == start:

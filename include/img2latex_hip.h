@@ -446,6 +446,51 @@ int i2l_sample_decode_batched(const i2l_decoder_weights* w, const void* workspac
 int i2l_sample_logits(const float* logits, int ld, int rows, int vocab, float temperature, int top_k, float top_p,
                       uint64_t seed, int step, int32_t* ids_out, float* probs_out, i2l_stream_t stream);
 
+/* BRACKET-CONSTRAINED step-batched decode: a greedy or sampled row whose groups nest and which ends on END within
+ * `steps` (csrc/bracket_rules.inc.h holds the rules, once, for device and host).
+ *   cls    (device, vocab bytes) one class byte per column: 0 neutral, 1..4 opens a group of kind 0..3, 5..8 closes a
+ *          group of kind 0..3, 255 -- and every other value -- is never emitted.  END is end_id, whatever its byte says.
+ *   state  (device, >= i2l_bracket_state_bytes(rows) = 16 bytes per row) uint64 stack (2 bits per open group, the
+ *          outermost in the low bits), int32 depth (0..32), int32 ended.  All-zero bytes are the initial state.
+ * With rem = steps - t - 1 and d = depth, a row that has not ended may emit at step t: END iff d == 0; a neutral column
+ * iff d + 1 <= rem; an open iff d < 32 and d + 2 <= rem; a closer iff d > 0 and the innermost open group is of its kind.
+ * d + 1 <= steps - t holds throughout, so a column is always allowed and every row emits END at depth 0 within `steps`
+ * steps, each group closed by a closer of its own kind.  Only a table that lacks the closer of a kind it opens can leave
+ * no column allowed: the pick is then end_id.  A row that has emitted END is not constrained any more, under either
+ * stop rule.  What is guaranteed is nesting and the END; arity (\frac's two groups) and meaning are not.
+ * Greedy: the first-index arg max of i2l_greedy_decode_batched's rule over the allowed columns.  Sampling: i2l_sample_
+ * decode_batched's rule on the row with -INFINITY in every disallowed column -- probability exactly 0 there, the others
+ * renormalise; top-k, top-p and the draw are unchanged.  If no allowed column has a logit above -inf the pick is the
+ * first allowed column.  logits_out receives the raw, unmasked logits.
+ *
+ * i2l_greedy_decode_constrained: the arguments, dimension rules and scratch of i2l_greedy_decode_batched without
+ * `forced`, plus cls, state, state_bytes; the call zeroes the state.  end_id outside [0, vocab), cls or state NULL:
+ * I2L_ERR_ARG; state_bytes too small: I2L_ERR_WORKSPACE.  i2l_sample_decode_constrained: i2l_sample_decode_batched plus
+ * the same three.  Every refusal is decided on the host before the first HIP call; the library keeps no state. */
+size_t i2l_bracket_state_bytes(int rows);   /* 16 per row, 0 for rows <= 0 */
+int i2l_greedy_decode_constrained(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                  const int32_t* tok0, const float* h0, const float* c0, float temperature, int select,
+                                  int stop, int end_id, int32_t* ids_out, float* logits_out, float* h_out, float* c_out,
+                                  void* scratch, size_t scratch_bytes, int flags, uint32_t* resident_flag,
+                                  uint32_t resident_value, const uint8_t* cls, void* state, size_t state_bytes,
+                                  i2l_stream_t stream);
+int i2l_sample_decode_constrained(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                  const int32_t* tok0, const float* h0, const float* c0, float temperature, int top_k,
+                                  float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out, float* probs_out,
+                                  float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
+                                  const uint8_t* cls, void* state, size_t state_bytes, i2l_stream_t stream);
+
+/* One application of the same device code to the caller's logits, as i2l_sample_logits: step `step` of `steps` for
+ * (rows, ld) fp32 logits, columns >= vocab not read.  top_k == 0 && top_p == 0: the arg max under `select`
+ * (I2L_SELECT_LOGITS / _SOFTMAX); otherwise a draw at uniform01(seed, row, step) and probs_out (rows, vocab) or NULL.
+ * Reads and ADVANCES the caller's state (rows x 16 bytes; the caller zeroes it before step 0).  allowed_out (rows, vocab)
+ * uint8 or NULL receives the mask (all ones for a row that has ended).  temperature <= 0, top_k < 0, top_p < 0, an
+ * unknown select, rows / vocab / steps <= 0, ld < vocab, step outside [0, steps), end_id outside [0, vocab), a NULL
+ * logits / cls / state / ids_out: I2L_ERR_ARG; sampling with vocab > 2048: I2L_ERR_UNSUPPORTED. */
+int i2l_constrained_pick_logits(const float* logits, int ld, int rows, int vocab, float temperature, int select, int top_k,
+                                float top_p, uint64_t seed, int step, int steps, const uint8_t* cls, int end_id, void* state,
+                                int32_t* ids_out, float* probs_out, uint8_t* allowed_out, i2l_stream_t stream);
+
 /* Beam search for `images` independent images, `beam` beams each (<= I2L_MAX_BEAM):
  * per image exactly Seq2SeqModel._beam_search at batch 1 (seq2seq.py:234-298) --
  * log_softmax in fp32, top-k sorted descending with lower index first on ties, scores
