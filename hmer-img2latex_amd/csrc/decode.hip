@@ -18,6 +18,7 @@
 // LSTM pointwise, logits = h' @ W_out^T + b, first-index argmax by wave shuffles.
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "common.h"
 
@@ -785,6 +786,56 @@ size_t decode_lds_bytes(int R, int L, int H, int Vp, int select, int KL = 0) {
     return floats * sizeof(float);
 }
 
+inline int use_temp(float temperature) { return temperature != 1.0f ? 1 : 0; }
+
+// f(std::integral_constant<int, W>) for the W among Ws that equals `width`, so that a runtime width (a beam, the rows of
+// a workgroup or of a tile) names a template argument; false, and no call, when there is none.  The kernels
+// instantiated are exactly those of the list.
+template <int... Ws, class F>
+bool with_width(int width, F&& f) {
+    return ((width == Ws && (f(std::integral_constant<int, Ws>{}), true)) || ...);
+}
+
+// The refusals the decode-loop entries share, each stated once and 0 (I2L_OK) when it passes: an entry chains the ones
+// it needs with ||.  Their order is part of an entry's contract: it decides which code two bad arguments return.
+inline int check_select(int select) {
+    return select == I2L_SELECT_LOGITS || select == I2L_SELECT_SOFTMAX ? I2L_OK : I2L_ERR_ARG;
+}
+inline int check_loop(int rows, int steps) { return rows > 0 && steps > 0 ? I2L_OK : I2L_ERR_ARG; }
+inline int check_sample(float temperature, int top_k, float top_p) {
+    return sample_args_ok(temperature, top_k, top_p) ? I2L_OK : I2L_ERR_ARG;
+}
+inline int check_sample_vocab(int vocab) { return vocab > SB_MAXV ? I2L_ERR_UNSUPPORTED : I2L_OK; }
+// the constraint's own arguments; rows > 0 and vocab > 0 are checked before it
+int check_constraint(int rows, int vocab, int end_id, const uint8_t* cls, const void* state, size_t state_bytes) {
+    if (end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
+    if (state_bytes < (size_t)rows * sizeof(BracketState)) return I2L_ERR_WORKSPACE;
+    return I2L_OK;
+}
+
+// What a caller asks of a decode loop, the row / grouped one (launch_decode) or the step-batched one (launch_batched):
+// an entry zero-initialises the record and fills what it takes.  Null or 0 is "absent" throughout.
+struct DecodeCall {
+    const i2l_decoder_weights* w;
+    const void* workspace;
+    int rows, steps;
+    const int32_t *tok0, *forced;
+    const float *h0, *c0;
+    float temperature;
+    int select, stop, end_id;
+    SampleRule sample;                 // select == I2L_SELECT_SAMPLE: the masks, the seed, the probabilities out
+    int32_t* ids_out;
+    float *logits_out, *h_out, *c_out;
+    int flags;
+    uint32_t* resident_flag;
+    uint32_t resident_value;
+    i2l_stream_t stream;
+    int rows_per_wg;                   // launch_decode: 0 = its own choice
+    ConstrainRule con;                 // launch_batched: con.cls != null asks for the bracket-constrained selection
+    void* scratch;                     // launch_batched
+    size_t scratch_bytes;
+};
+
 }  // namespace
 
 extern "C" size_t i2l_decoder_workspace_bytes(int rows, int vocab, int embed, int hidden, int layers) {
@@ -854,127 +905,78 @@ extern "C" int i2l_decoder_prepare(const i2l_decoder_weights* w, const float* en
 }
 
 namespace {
-int launch_decode(const i2l_decoder_weights* w, const void* workspace, int rows, int steps, const int32_t* tok0,
-                  const int32_t* forced, const float* h0, const float* c0, float temperature, int select, int stop,
-                  int end_id, int top_k, float top_p, unsigned long long seed, int32_t* ids_out, float* logits_out,
-                  float* probs_out, float* h_out, float* c_out, i2l_stream_t stream, int rows_per_wg = 0, int flags = 0,
-                  uint32_t* resident_flag = nullptr, uint32_t resident_value = 0);
-}
-
-extern "C" int i2l_greedy_decode_ex(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
-                                    const int32_t* tok0, const int32_t* forced, const float* h0, const float* c0,
-                                    float temperature, int select, int stop, int end_id, int rows_per_workgroup,
-                                    int32_t* ids_out, float* logits_out, float* h_out, float* c_out, int flags,
-                                    uint32_t* resident_flag, uint32_t resident_value, i2l_stream_t stream) {
-    if (select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
-    if (rows_per_workgroup != 0 && rows_per_workgroup != 1 && rows_per_workgroup != 2 && rows_per_workgroup != 4)
-        return I2L_ERR_ARG;
-    return launch_decode(w, workspace, rows, steps, tok0, forced, h0, c0, temperature, select, stop, end_id, 0, 0.f, 0ull,
-                         ids_out, logits_out, nullptr, h_out, c_out, stream, rows_per_workgroup, flags, resident_flag,
-                         resident_value);
-}
-
-extern "C" int i2l_greedy_decode(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
-                                 const int32_t* tok0, const int32_t* forced, const float* h0, const float* c0,
-                                 float temperature, int select, int stop, int end_id, int32_t* ids_out,
-                                 float* logits_out, float* h_out, float* c_out, i2l_stream_t stream) {
-    if (select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
-    return launch_decode(w, workspace, rows, steps, tok0, forced, h0, c0, temperature, select, stop, end_id, 0, 0.f, 0ull,
-                         ids_out, logits_out, nullptr, h_out, c_out, stream);
-}
-
-extern "C" int i2l_sample_decode(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
-                                 const int32_t* tok0, const float* h0, const float* c0, float temperature, int top_k,
-                                 float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out, float* probs_out,
-                                 float* h_out, float* c_out, i2l_stream_t stream) {
-    if (!sample_args_ok(temperature, top_k, top_p)) return I2L_ERR_ARG;
-    if (w && w->vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
-    return launch_decode(w, workspace, rows, steps, tok0, nullptr, h0, c0, temperature, I2L_SELECT_SAMPLE, stop, end_id,
-                         top_k, top_p, (unsigned long long)seed, ids_out, nullptr, probs_out, h_out, c_out, stream);
-}
-
-namespace {
 // the residency signal of a launch that does NOT run a grouped kernel (other dimensions, row-per-workgroup request): its
 // workgroups need no partners, so "resident" is said at once -- a waiter never pays its time-out for a kernel choice;
 // like the grouped kernels it never moves the word backwards (publish_max32)
 __global__ void publish_value32_kernel(unsigned* flag, unsigned value) { publish_max32(flag, value); }
 
-int launch_decode(const i2l_decoder_weights* w, const void* workspace, int rows, int steps, const int32_t* tok0,
-                  const int32_t* forced, const float* h0, const float* c0, float temperature, int select, int stop,
-                  int end_id, int top_k, float top_p, unsigned long long seed, int32_t* ids_out, float* logits_out,
-                  float* probs_out, float* h_out, float* c_out, i2l_stream_t stream, int rows_per_wg, int flags,
-                  uint32_t* resident_flag, uint32_t resident_value) {
-    int rc = check_weights(w);
+// the persistent loop of i2l_greedy_decode[_ex] and i2l_sample_decode: a grouped kernel where one takes the call, else
+// decode_kernel, one workgroup per a.rows_per_wg rows
+int launch_decode(const DecodeCall& a) {
+    int rc = check_weights(a.w);
     if (rc != I2L_OK) return rc;
-    if (!workspace || !tok0 || rows <= 0 || steps <= 0) return I2L_ERR_ARG;
-    if ((h0 == nullptr) != (c0 == nullptr)) return I2L_ERR_ARG;
-    if (stop != I2L_STOP_NONE && stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
-    const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
+    if (!a.workspace || !a.tok0 || check_loop(a.rows, a.steps)) return I2L_ERR_ARG;
+    if ((a.h0 == nullptr) != (a.c0 == nullptr)) return I2L_ERR_ARG;
+    if (a.stop != I2L_STOP_NONE && a.stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
+    const int rows = a.rows, steps = a.steps, select = a.select;
+    const int V = a.w->vocab, E = a.w->embed, H = a.w->hidden, L = a.w->layers;
     const Layout lo = make_layout(rows, V, E, H, L);
-    const char* base = static_cast<const char*>(workspace);
+    const char* base = static_cast<const char*>(a.workspace);
 
     DecodeParams p{};
     p.w = step_weights(lo, base, V, H, L);
     p.B = rows; p.T = steps;
-    p.tok0 = tok0; p.forced = forced; p.h0 = h0; p.c0 = c0;
-    p.h_out = h_out; p.c_out = c_out; p.ids = ids_out; p.logits = logits_out;
-    p.temperature = temperature; p.use_temp = (temperature != 1.0f) ? 1 : 0;
-    p.select = select; p.stop = stop; p.end_id = end_id;
-    p.top_k = top_k; p.top_p = top_p; p.seed = seed; p.probs = probs_out;
+    p.tok0 = a.tok0; p.forced = a.forced; p.h0 = a.h0; p.c0 = a.c0;
+    p.h_out = a.h_out; p.c_out = a.c_out; p.ids = a.ids_out; p.logits = a.logits_out;
+    p.temperature = a.temperature; p.use_temp = use_temp(a.temperature);
+    p.select = select; p.stop = a.stop; p.end_id = a.end_id;
+    p.top_k = a.sample.top_k; p.top_p = a.sample.top_p; p.seed = a.sample.seed; p.probs = a.sample.probs;
 
     // grouped kernels (group_variant): the workgroups of a group share its rows, weights fully on chip
     // I2L_SELECT_SOFTMAX takes them too: softmax is monotone, so its arg max is the logits' arg max unless fp32 rounding
     // makes two DIFFERENT scaled logits equal probabilities, which needs the two largest to be adjacent floats AND the
     // largest below 2 in magnitude (exp(x2 - x1) is then within 2 ulp of 1); the row-per-workgroup kernel evaluates
     // the probabilities literally and is one argument away (rows_per_workgroup != 0)
-    if (rows_per_wg == 0 && lo.xchg_bytes && (select == I2L_SELECT_LOGITS || select == I2L_SELECT_SOFTMAX) && !h0 &&
-        !h_out && !c_out &&
+    if (a.rows_per_wg == 0 && lo.xchg_bytes && check_select(select) == I2L_OK && !a.h0 && !a.h_out && !a.c_out &&
         steps >= 8 && steps <= 65000) {   // the candidate granule carries step + 1 in 16 bits
         GroupParams gp{};
         gp.w = p.w; gp.B = rows; gp.T = steps;
-        gp.tok0 = tok0; gp.forced = forced; gp.ids = ids_out; gp.logits = logits_out;
-        gp.temperature = temperature; gp.use_temp = p.use_temp; gp.stop = stop; gp.end_id = end_id;
+        gp.tok0 = a.tok0; gp.forced = a.forced; gp.ids = a.ids_out; gp.logits = a.logits_out;
+        gp.temperature = a.temperature; gp.use_temp = p.use_temp; gp.stop = a.stop; gp.end_id = a.end_id;
         char* xb = const_cast<char*>(base) + lo.xchg;           // scratch region of the workspace
         gp.status = reinterpret_cast<unsigned*>(xb);
         gp.xchg = reinterpret_cast<u64_t*>(xb + GROUP_STATUS_BYTES);
-        gp.opts = group_opts(steps, flags);
-        gp.resident_flag = resident_flag; gp.resident_value = resident_value;
-        hipStream_t gs = i2l_s(stream);
-        const bool ids_only = ids_out && !logits_out && !forced;
+        gp.opts = group_opts(steps, a.flags);
+        gp.resident_flag = a.resident_flag; gp.resident_value = a.resident_value;
+        hipStream_t gs = i2l_s(a.stream);
+        const bool ids_only = a.ids_out && !a.logits_out && !a.forced;
         static std::atomic<unsigned> attr[GROUP_VARIANTS]{};   // per variant and device
         for (int i = 0; i < GROUP_VARIANTS; ++i) {
             const GroupVariant g = group_variant(i);
-            if (g.flag && !((flags & g.flag) && ids_only)) continue;
+            if (g.flag && !((a.flags & g.flag) && ids_only)) continue;
             if (!i2l_lds_attr(reinterpret_cast<const void*>(g.kernel), g.lds, attr[i])) continue;   // try the next one
-            if (!(flags & I2L_FLAG_DECODE_REGION_CLEARED) && hipMemsetAsync(xb, 0, lo.xchg_bytes, gs) != hipSuccess) return I2L_ERR_LAUNCH;
+            if (!(a.flags & I2L_FLAG_DECODE_REGION_CLEARED) && hipMemsetAsync(xb, 0, lo.xchg_bytes, gs) != hipSuccess) return I2L_ERR_LAUNCH;
             gp.n_groups = i2l_cdiv(rows, g.rows);
             hipLaunchKernelGGL(g.kernel, dim3(group_grid(gp.n_groups, g.rows)), dim3(g.threads), g.lds, gs, gp);
             I2L_CHECK_LAUNCH();
             return I2L_OK;
         }
     }
-    if (resident_flag) {
-        hipLaunchKernelGGL(publish_value32_kernel, dim3(1), dim3(1), 0, i2l_s(stream), resident_flag, resident_value);
+    hipStream_t s = i2l_s(a.stream);
+    if (a.resident_flag) {
+        hipLaunchKernelGGL(publish_value32_kernel, dim3(1), dim3(1), 0, s, a.resident_flag, a.resident_value);
         I2L_CHECK_LAUNCH();
     }
     // rows per workgroup: fill the 256 CUs first, then stack rows (weights are streamed once per workgroup per step)
     int R = rows <= 256 ? 1 : (rows <= 512 ? 2 : 4);
-    if (rows_per_wg > 0) R = rows_per_wg;
+    if (a.rows_per_wg > 0) R = a.rows_per_wg;
     while (R > 1 && decode_lds_bytes(R, L, H, lo.Vp, select) > 64 * 1024) R >>= 1;
     const size_t lds = decode_lds_bytes(R, L, H, lo.Vp, select);
     if (lds > 64 * 1024) return I2L_ERR_UNSUPPORTED;
     const dim3 grid(i2l_cdiv(rows, R));
-    hipStream_t s = i2l_s(stream);
+    const bool sampled = select == I2L_SELECT_SAMPLE;
     // fast path: weights partly resident on chip; pays a one-off fill, so only for real loops
-    if (select == I2L_SELECT_SAMPLE) {
-        if (R == 1) hipLaunchKernelGGL((decode_kernel<1, 0, 0, true>), grid, dim3(NT), lds, s, p);
-        else if (R == 2) hipLaunchKernelGGL((decode_kernel<2, 0, 0, true>), grid, dim3(NT), lds, s, p);
-        else hipLaunchKernelGGL((decode_kernel<4, 0, 0, true>), grid, dim3(NT), lds, s, p);
-        I2L_CHECK_LAUNCH();
-        return I2L_OK;
-    }
-    const bool resident = (R == 1 || R == 2) && L == 1 && H == 256 && steps >= 8;
-    if (resident) {
+    if (!sampled && (R == 1 || R == 2) && L == 1 && H == 256 && steps >= 8) {
         const size_t lds_r = decode_lds_bytes(R, 1, H, lo.Vp, select, R == 1 ? RES_KL : RES2_KL);
         auto kern = R == 1 ? decode_kernel<1, RES_KR, RES_KL> : decode_kernel<2, RES2_KR, RES2_KL>;
         if (lds_r <= 160 * 1024 &&
@@ -985,13 +987,55 @@ int launch_decode(const i2l_decoder_weights* w, const void* workspace, int rows,
             return I2L_OK;
         }
     }
-    if (R == 1) hipLaunchKernelGGL((decode_kernel<1, 0, 0>), grid, dim3(NT), lds, s, p);
-    else if (R == 2) hipLaunchKernelGGL((decode_kernel<2, 0, 0>), grid, dim3(NT), lds, s, p);
-    else hipLaunchKernelGGL((decode_kernel<4, 0, 0>), grid, dim3(NT), lds, s, p);
+    with_width<1, 2, 4>(R, [&](auto r) {
+        if (sampled) hipLaunchKernelGGL((decode_kernel<r, 0, 0, true>), grid, dim3(NT), lds, s, p);
+        else hipLaunchKernelGGL((decode_kernel<r, 0, 0>), grid, dim3(NT), lds, s, p);
+    });
     I2L_CHECK_LAUNCH();
     return I2L_OK;
 }
 }  // namespace
+
+extern "C" int i2l_greedy_decode_ex(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                    const int32_t* tok0, const int32_t* forced, const float* h0, const float* c0,
+                                    float temperature, int select, int stop, int end_id, int rows_per_workgroup,
+                                    int32_t* ids_out, float* logits_out, float* h_out, float* c_out, int flags,
+                                    uint32_t* resident_flag, uint32_t resident_value, i2l_stream_t stream) {
+    if (check_select(select)) return I2L_ERR_ARG;
+    if (rows_per_workgroup != 0 && rows_per_workgroup != 1 && rows_per_workgroup != 2 && rows_per_workgroup != 4)
+        return I2L_ERR_ARG;
+    DecodeCall a{};
+    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
+    a.tok0 = tok0; a.forced = forced; a.h0 = h0; a.c0 = c0;
+    a.temperature = temperature; a.select = select; a.stop = stop; a.end_id = end_id;
+    a.ids_out = ids_out; a.logits_out = logits_out; a.h_out = h_out; a.c_out = c_out;
+    a.flags = flags; a.resident_flag = resident_flag; a.resident_value = resident_value; a.stream = stream;
+    a.rows_per_wg = rows_per_workgroup;
+    return launch_decode(a);
+}
+
+extern "C" int i2l_greedy_decode(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                 const int32_t* tok0, const int32_t* forced, const float* h0, const float* c0,
+                                 float temperature, int select, int stop, int end_id, int32_t* ids_out,
+                                 float* logits_out, float* h_out, float* c_out, i2l_stream_t stream) {
+    return i2l_greedy_decode_ex(w, workspace, rows, steps, tok0, forced, h0, c0, temperature, select, stop, end_id, 0,
+                                ids_out, logits_out, h_out, c_out, 0, nullptr, 0, stream);
+}
+
+extern "C" int i2l_sample_decode(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                 const int32_t* tok0, const float* h0, const float* c0, float temperature, int top_k,
+                                 float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out, float* probs_out,
+                                 float* h_out, float* c_out, i2l_stream_t stream) {
+    int rc;
+    if ((rc = check_sample(temperature, top_k, top_p)) || (rc = w ? check_sample_vocab(w->vocab) : I2L_OK)) return rc;
+    DecodeCall a{};
+    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
+    a.tok0 = tok0; a.h0 = h0; a.c0 = c0;
+    a.temperature = temperature; a.select = I2L_SELECT_SAMPLE; a.stop = stop; a.end_id = end_id;
+    a.sample = SampleRule{top_k, top_p, (unsigned long long)seed, probs_out};
+    a.ids_out = ids_out; a.h_out = h_out; a.c_out = c_out; a.stream = stream;
+    return launch_decode(a);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Two batches per 16-member grouped launch, a range of the steps of each (decode_group16_kernel<2>).
@@ -1044,7 +1088,7 @@ extern "C" int i2l_greedy_decode_halves(const i2l_decoder_weights* w, const i2l_
     GroupParams gp{};
     gp.w = step_weights(lo, base, V, H, L);
     gp.n_groups = n_groups;
-    gp.temperature = temperature; gp.use_temp = (temperature != 1.0f) ? 1 : 0; gp.stop = stop; gp.end_id = end_id;
+    gp.temperature = temperature; gp.use_temp = use_temp(temperature); gp.stop = stop; gp.end_id = end_id;
     char* xb = base + lo.xchg;
     gp.status = reinterpret_cast<unsigned*>(xb);
     gp.xchg = reinterpret_cast<u64_t*>(xb + GROUP_STATUS_BYTES);
@@ -1089,65 +1133,63 @@ void launch_batched_logits(const BatchedParams& p, int t, hipStream_t s) {
 }
 // the L LSTM launches and the logits launch of step t on p's rows; tb_*: batched_tile_rows of either grid
 void launch_batched_step(const BatchedParams& p, int tb_lstm, int tb_logits, int t, hipStream_t s) {
-    if (tb_lstm == 16) launch_batched_lstm<16>(p, t, s);
-    else if (tb_lstm == 32) launch_batched_lstm<32>(p, t, s);
-    else launch_batched_lstm<64>(p, t, s);
-    if (tb_logits == 16) launch_batched_logits<16>(p, t, s);
-    else if (tb_logits == 32) launch_batched_logits<32>(p, t, s);
-    else launch_batched_logits<64>(p, t, s);
+    with_width<16, 32, 64>(tb_lstm, [&](auto tb) { launch_batched_lstm<tb>(p, t, s); });
+    with_width<16, 32, 64>(tb_logits, [&](auto tb) { launch_batched_logits<tb>(p, t, s); });
 }
 
-// the loop of the step-batched entries; `sample` != null: sample_batched_kernel selects (select is I2L_SELECT_SAMPLE);
-// `con` != null: the constrained twin of either selection kernel, on the rows' zeroed bracket state.
-// The caller has checked the weights and its own arguments; every other refusal is decided here, before the first HIP call.
-int launch_batched(const i2l_decoder_weights* w, const void* workspace, int rows, int steps, const int32_t* tok0,
-                   const int32_t* forced, const float* h0, const float* c0, float temperature, int select, int stop,
-                   int end_id, const SampleRule* sample, const ConstrainRule* con, int32_t* ids_out, float* logits_out,
-                   float* h_out, float* c_out, void* scratch, size_t scratch_bytes, uint32_t* resident_flag,
-                   uint32_t resident_value, i2l_stream_t stream) {
-    if (!workspace || !tok0 || rows <= 0 || steps <= 0) return I2L_ERR_ARG;
-    if ((h0 == nullptr) != (c0 == nullptr)) return I2L_ERR_ARG;
-    if (stop != I2L_STOP_NONE && stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
-    const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
+// the last launch of a step: the arg max, or the draw when the call samples, under the rule's pick policy
+template <class Rule>
+void launch_batched_select(const BatchedParams& p, const DecodeCall& a, const Rule& rule, int t, hipStream_t s) {
+    if (a.select == I2L_SELECT_SAMPLE)
+        hipLaunchKernelGGL(sample_batched_kernel<Rule>, dim3(p.B), dim3(NT), 0, s, p, a.sample, rule, t);
+    else
+        hipLaunchKernelGGL(select_batched_kernel<Rule>, dim3(i2l_cdiv(p.B, DB_NT / 64)), dim3(DB_NT), 0, s, p, rule, t);
+}
+
+// The loop of the step-batched entries.  The caller has checked the weights and its own arguments; every other refusal
+// is decided here, before the first HIP call.  A constrained call starts from the rows' zeroed bracket state.
+int launch_batched(const DecodeCall& a) {
+    if (!a.workspace || !a.tok0 || check_loop(a.rows, a.steps)) return I2L_ERR_ARG;
+    if ((a.h0 == nullptr) != (a.c0 == nullptr)) return I2L_ERR_ARG;
+    if (a.stop != I2L_STOP_NONE && a.stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
+    const int rows = a.rows, steps = a.steps;
+    const int V = a.w->vocab, E = a.w->embed, H = a.w->hidden, L = a.w->layers;
     const Layout lo = make_layout(rows, V, E, H, L);
     const BatchedLayout bl = batched_layout(rows, lo.Vp, H, L);
-    if (!scratch || scratch_bytes < bl.total) return I2L_ERR_WORKSPACE;
+    if (!a.scratch || a.scratch_bytes < bl.total) return I2L_ERR_WORKSPACE;
 
-    char* sb = static_cast<char*>(scratch);
+    char* sb = static_cast<char*>(a.scratch);
     BatchedParams p{};
-    p.w = step_weights(lo, static_cast<const char*>(workspace), V, H, L);
-    p.B = rows; p.T = steps; p.genc_div = 1; p.forced = forced;
+    p.w = step_weights(lo, static_cast<const char*>(a.workspace), V, H, L);
+    p.B = rows; p.T = steps; p.genc_div = 1; p.forced = a.forced;
     p.h = reinterpret_cast<float*>(sb + bl.h); p.c = reinterpret_cast<float*>(sb + bl.c);
     p.lg = reinterpret_cast<float*>(sb + bl.lg);
     p.tok = reinterpret_cast<int*>(sb + bl.tok); p.fin = reinterpret_cast<int*>(sb + bl.fin);
     p.live = reinterpret_cast<unsigned*>(sb + bl.live);
-    p.ids = ids_out; p.logits_out = logits_out;
-    p.temperature = temperature; p.use_temp = (temperature != 1.0f) ? 1 : 0;
-    p.select = select; p.stop = stop; p.end_id = end_id;
+    p.ids = a.ids_out; p.logits_out = a.logits_out;
+    p.temperature = a.temperature; p.use_temp = use_temp(a.temperature);
+    p.select = a.select; p.stop = a.stop; p.end_id = a.end_id;
 
-    hipStream_t s = i2l_s(stream);
-    if (resident_flag) {      // nothing here waits for a partner: "resident" is said at once
-        hipLaunchKernelGGL(publish_value32_kernel, dim3(1), dim3(1), 0, s, resident_flag, resident_value);
+    hipStream_t s = i2l_s(a.stream);
+    if (a.resident_flag) {      // nothing here waits for a partner: "resident" is said at once
+        hipLaunchKernelGGL(publish_value32_kernel, dim3(1), dim3(1), 0, s, a.resident_flag, a.resident_value);
         I2L_CHECK_LAUNCH();
     }
-    if (con && hipMemsetAsync(con->state, 0, (size_t)rows * sizeof(BracketState), s) != hipSuccess) return I2L_ERR_LAUNCH;
+    if (a.con.cls && hipMemsetAsync(a.con.state, 0, (size_t)rows * sizeof(BracketState), s) != hipSuccess) return I2L_ERR_LAUNCH;
     const size_t most = (size_t)L * rows * H > (size_t)rows * steps ? (size_t)L * rows * H : (size_t)rows * steps;
     const size_t copy_blocks = (most + DB_NT - 1) / DB_NT;
     const int copy_grid = (int)(copy_blocks < 1024 ? copy_blocks : 1024);
-    hipLaunchKernelGGL(init_batched_kernel, dim3(copy_grid), dim3(DB_NT), 0, s, p, tok0, h0, c0);
+    hipLaunchKernelGGL(init_batched_kernel, dim3(copy_grid), dim3(DB_NT), 0, s, p, a.tok0, a.h0, a.c0);
     I2L_CHECK_LAUNCH();
     const int tb_lstm = batched_tile_rows(H / 16, rows), tb_logits = batched_tile_rows(lo.Vp / DB_COLS, rows);
-    const int sel_grid = i2l_cdiv(rows, DB_NT / 64);
     for (int t = 0; t < steps; ++t) {
         launch_batched_step(p, tb_lstm, tb_logits, t, s);
-        if (con && sample) hipLaunchKernelGGL(sample_constrained_kernel, dim3(rows), dim3(NT), 0, s, p, *sample, *con, t);
-        else if (con) hipLaunchKernelGGL(select_constrained_kernel, dim3(sel_grid), dim3(DB_NT), 0, s, p, *con, t);
-        else if (sample) hipLaunchKernelGGL(sample_batched_kernel, dim3(rows), dim3(NT), 0, s, p, *sample, t);
-        else hipLaunchKernelGGL(select_batched_kernel, dim3(sel_grid), dim3(DB_NT), 0, s, p, t);
+        if (a.con.cls) launch_batched_select(p, a, a.con, t, s);
+        else launch_batched_select(p, a, NoRule{}, t, s);
         I2L_CHECK_LAUNCH();
     }
-    if (h_out || c_out) {
-        hipLaunchKernelGGL(state_out_batched_kernel, dim3(copy_grid), dim3(DB_NT), 0, s, p, h_out, c_out);
+    if (a.h_out || a.c_out) {
+        hipLaunchKernelGGL(state_out_batched_kernel, dim3(copy_grid), dim3(DB_NT), 0, s, p, a.h_out, a.c_out);
         I2L_CHECK_LAUNCH();
     }
     return I2L_OK;
@@ -1160,64 +1202,62 @@ extern "C" int i2l_greedy_decode_batched(const i2l_decoder_weights* w, const voi
                                          float* logits_out, float* h_out, float* c_out, void* scratch,
                                          size_t scratch_bytes, int flags, uint32_t* resident_flag,
                                          uint32_t resident_value, i2l_stream_t stream) {
-    (void)flags;
-    int rc = check_weights(w);
-    if (rc != I2L_OK) return rc;
-    if (select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
-    return launch_batched(w, workspace, rows, steps, tok0, forced, h0, c0, temperature, select, stop, end_id, nullptr,
-                          nullptr, ids_out, logits_out, h_out, c_out, scratch, scratch_bytes, resident_flag, resident_value,
-                          stream);
+    int rc;
+    if ((rc = check_weights(w)) || (rc = check_select(select))) return rc;
+    DecodeCall a{};
+    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
+    a.tok0 = tok0; a.forced = forced; a.h0 = h0; a.c0 = c0;
+    a.temperature = temperature; a.select = select; a.stop = stop; a.end_id = end_id;
+    a.ids_out = ids_out; a.logits_out = logits_out; a.h_out = h_out; a.c_out = c_out;
+    a.flags = flags; a.resident_flag = resident_flag; a.resident_value = resident_value; a.stream = stream;
+    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
+    return launch_batched(a);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Step-batched sampling (sample_batched.inc.h): the same loop, sample_batched_kernel as the last launch of a step.
+// Every refusal is decided on the host, here and in launch_batched, before the first HIP call.
 // ---------------------------------------------------------------------------------------------
 extern "C" int i2l_sample_decode_batched(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
                                          const int32_t* tok0, const float* h0, const float* c0, float temperature,
                                          int top_k, float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out,
                                          float* probs_out, float* h_out, float* c_out, void* scratch,
                                          size_t scratch_bytes, int flags, i2l_stream_t stream) {
-    (void)flags;
-    // every refusal is decided on the host, here and in launch_batched, before the first HIP call
-    int rc = check_weights(w);
-    if (rc != I2L_OK) return rc;
-    if (!sample_args_ok(temperature, top_k, top_p)) return I2L_ERR_ARG;
-    if (rows <= 0 || steps <= 0) return I2L_ERR_ARG;
-    if (w->vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
-    const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
-    return launch_batched(w, workspace, rows, steps, tok0, nullptr, h0, c0, temperature, I2L_SELECT_SAMPLE, stop, end_id,
-                          &rule, nullptr, ids_out, nullptr, h_out, c_out, scratch, scratch_bytes, nullptr, 0, stream);
+    int rc;
+    if ((rc = check_weights(w)) || (rc = check_sample(temperature, top_k, top_p)) || (rc = check_loop(rows, steps)) ||
+        (rc = check_sample_vocab(w->vocab)))
+        return rc;
+    DecodeCall a{};
+    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
+    a.tok0 = tok0; a.h0 = h0; a.c0 = c0;
+    a.temperature = temperature; a.select = I2L_SELECT_SAMPLE; a.stop = stop; a.end_id = end_id;
+    a.sample = SampleRule{top_k, top_p, (unsigned long long)seed, probs_out};
+    a.ids_out = ids_out; a.h_out = h_out; a.c_out = c_out; a.flags = flags; a.stream = stream;
+    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
+    return launch_batched(a);
 }
 
 extern "C" int i2l_sample_logits(const float* logits, int ld, int rows, int vocab, float temperature, int top_k,
                                  float top_p, uint64_t seed, int step, int32_t* ids_out, float* probs_out,
                                  i2l_stream_t stream) {
-    if (!sample_args_ok(temperature, top_k, top_p)) return I2L_ERR_ARG;
+    int rc;
+    if ((rc = check_sample(temperature, top_k, top_p))) return rc;
     if (rows <= 0 || vocab <= 0 || ld < vocab || step < 0) return I2L_ERR_ARG;
-    if (vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
+    if ((rc = check_sample_vocab(vocab))) return rc;
     if (!logits || !ids_out) return I2L_ERR_ARG;
     const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
-    hipLaunchKernelGGL(sample_logits_kernel, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab, temperature,
-                       (temperature != 1.0f) ? 1 : 0, rule, (unsigned)step, ids_out);
+    hipLaunchKernelGGL(sample_logits_kernel<NoRule>, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab, temperature,
+                       use_temp(temperature), rule, (unsigned)step, NoRule{}, 0, 0, ids_out);
     I2L_CHECK_LAUNCH();
     return I2L_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
-// Bracket-constrained step-batched decode (bracket_rules.inc.h, decode_constrained.inc.h): the same loop, the constrained
-// twin of either selection kernel as the last launch of a step.  Every refusal is decided on the host, here and in
+// Bracket-constrained step-batched decode (bracket_rules.inc.h, decode_constrained.inc.h): the same loop, the selection
+// kernels under ConstrainRule as the last launch of a step.  Every refusal is decided on the host, here and in
 // launch_batched, before the first HIP call; the library keeps no state -- the rows' state is the caller's buffer.
 // ---------------------------------------------------------------------------------------------
 extern "C" size_t i2l_bracket_state_bytes(int rows) { return rows > 0 ? (size_t)rows * sizeof(BracketState) : 0; }
-
-namespace {
-// the constraint's own arguments; rows > 0 and vocab > 0 are the caller's checks
-int check_constraint(int rows, int vocab, int end_id, const uint8_t* cls, const void* state, size_t state_bytes) {
-    if (end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
-    if (state_bytes < (size_t)rows * sizeof(BracketState)) return I2L_ERR_WORKSPACE;
-    return I2L_OK;
-}
-}  // namespace
 
 extern "C" int i2l_greedy_decode_constrained(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
                                              const int32_t* tok0, const float* h0, const float* c0, float temperature,
@@ -1225,16 +1265,19 @@ extern "C" int i2l_greedy_decode_constrained(const i2l_decoder_weights* w, const
                                              float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
                                              uint32_t* resident_flag, uint32_t resident_value, const uint8_t* cls,
                                              void* state, size_t state_bytes, i2l_stream_t stream) {
-    (void)flags;
-    int rc = check_weights(w);
-    if (rc != I2L_OK) return rc;
-    if (select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
-    if (rows <= 0 || steps <= 0) return I2L_ERR_ARG;
-    rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes);
-    if (rc != I2L_OK) return rc;
-    const ConstrainRule con{cls, static_cast<BracketState*>(state)};
-    return launch_batched(w, workspace, rows, steps, tok0, nullptr, h0, c0, temperature, select, stop, end_id, nullptr, &con,
-                          ids_out, logits_out, h_out, c_out, scratch, scratch_bytes, resident_flag, resident_value, stream);
+    int rc;
+    if ((rc = check_weights(w)) || (rc = check_select(select)) || (rc = check_loop(rows, steps)) ||
+        (rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes)))
+        return rc;
+    DecodeCall a{};
+    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
+    a.tok0 = tok0; a.h0 = h0; a.c0 = c0;
+    a.temperature = temperature; a.select = select; a.stop = stop; a.end_id = end_id;
+    a.ids_out = ids_out; a.logits_out = logits_out; a.h_out = h_out; a.c_out = c_out;
+    a.flags = flags; a.resident_flag = resident_flag; a.resident_value = resident_value; a.stream = stream;
+    a.con = ConstrainRule{cls, static_cast<BracketState*>(state), nullptr};
+    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
+    return launch_batched(a);
 }
 
 extern "C" int i2l_sample_decode_constrained(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
@@ -1243,18 +1286,19 @@ extern "C" int i2l_sample_decode_constrained(const i2l_decoder_weights* w, const
                                              float* probs_out, float* h_out, float* c_out, void* scratch,
                                              size_t scratch_bytes, int flags, const uint8_t* cls, void* state,
                                              size_t state_bytes, i2l_stream_t stream) {
-    (void)flags;
-    int rc = check_weights(w);
-    if (rc != I2L_OK) return rc;
-    if (!sample_args_ok(temperature, top_k, top_p)) return I2L_ERR_ARG;
-    if (rows <= 0 || steps <= 0) return I2L_ERR_ARG;
-    if (w->vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
-    rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes);
-    if (rc != I2L_OK) return rc;
-    const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
-    const ConstrainRule con{cls, static_cast<BracketState*>(state)};
-    return launch_batched(w, workspace, rows, steps, tok0, nullptr, h0, c0, temperature, I2L_SELECT_SAMPLE, stop, end_id,
-                          &rule, &con, ids_out, nullptr, h_out, c_out, scratch, scratch_bytes, nullptr, 0, stream);
+    int rc;
+    if ((rc = check_weights(w)) || (rc = check_sample(temperature, top_k, top_p)) || (rc = check_loop(rows, steps)) ||
+        (rc = check_sample_vocab(w->vocab)) || (rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes)))
+        return rc;
+    DecodeCall a{};
+    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
+    a.tok0 = tok0; a.h0 = h0; a.c0 = c0;
+    a.temperature = temperature; a.select = I2L_SELECT_SAMPLE; a.stop = stop; a.end_id = end_id;
+    a.sample = SampleRule{top_k, top_p, (unsigned long long)seed, probs_out};
+    a.ids_out = ids_out; a.h_out = h_out; a.c_out = c_out; a.flags = flags; a.stream = stream;
+    a.con = ConstrainRule{cls, static_cast<BracketState*>(state), nullptr};
+    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
+    return launch_batched(a);
 }
 
 extern "C" int i2l_constrained_pick_logits(const float* logits, int ld, int rows, int vocab, float temperature, int select,
@@ -1263,19 +1307,19 @@ extern "C" int i2l_constrained_pick_logits(const float* logits, int ld, int rows
                                            uint8_t* allowed_out, i2l_stream_t stream) {
     const bool greedy = top_k == 0 && top_p == 0.f;
     if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return I2L_ERR_ARG;
-    if (greedy && select != I2L_SELECT_LOGITS && select != I2L_SELECT_SOFTMAX) return I2L_ERR_ARG;
+    if (greedy && check_select(select)) return I2L_ERR_ARG;
     if (rows <= 0 || vocab <= 0 || ld < vocab || step < 0 || steps <= 0 || step >= steps) return I2L_ERR_ARG;
-    if (!greedy && vocab > SB_MAXV) return I2L_ERR_UNSUPPORTED;
+    if (!greedy && check_sample_vocab(vocab)) return I2L_ERR_UNSUPPORTED;
     if (!logits || !ids_out || end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
-    const ConstrainRule con{cls, static_cast<BracketState*>(state)};
-    const int use_temp = (temperature != 1.0f) ? 1 : 0, rem = steps - step - 1;
+    const ConstrainRule con{cls, static_cast<BracketState*>(state), allowed_out};
+    const int rem = steps - step - 1;
     if (greedy) {
         hipLaunchKernelGGL(pick_constrained_select_kernel, dim3(i2l_cdiv(rows, DB_NT / 64)), dim3(DB_NT), 0, i2l_s(stream),
-                           logits, ld, rows, vocab, temperature, use_temp, select, con, end_id, rem, ids_out, allowed_out);
+                           logits, ld, rows, vocab, temperature, use_temp(temperature), select, con, end_id, rem, ids_out);
     } else {
         const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
-        hipLaunchKernelGGL(pick_constrained_sample_kernel, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab,
-                           temperature, use_temp, rule, (unsigned)step, con, end_id, rem, ids_out, allowed_out);
+        hipLaunchKernelGGL(sample_logits_kernel<ConstrainRule>, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab,
+                           temperature, use_temp(temperature), rule, (unsigned)step, con, end_id, rem, ids_out);
     }
     I2L_CHECK_LAUNCH();
     return I2L_OK;
@@ -1363,14 +1407,8 @@ extern "C" int i2l_beam_decode(const i2l_decoder_weights* w, const void* workspa
         gp.xchg = reinterpret_cast<u64_t*>(xb + GROUP_STATUS_BYTES);
         gp.opts = group_opts(steps, flags);
         if (hipMemsetAsync(xb, 0, xbytes, s) != hipSuccess) return I2L_ERR_LAUNCH;
-        switch (beam) {
-            case 2: return launch_beam_group<2>(gp, s);
-            case 3: return launch_beam_group<3>(gp, s);
-            case 4: return launch_beam_group<4>(gp, s);
-            case 5: return launch_beam_group<5>(gp, s);
-            case 6: return launch_beam_group<6>(gp, s);
-            default: break;
-        }
+        with_width<2, 3, 4, 5, 6>(beam, [&](auto k) { rc = launch_beam_group<k>(gp, s); });   // beam_group_ok: one of these
+        return rc;
     }
     BeamParams p{};
     p.w = step_weights(lo, static_cast<const char*>(workspace), V, H, L);
@@ -1380,17 +1418,9 @@ extern "C" int i2l_beam_decode(const i2l_decoder_weights* w, const void* workspa
     p.seq_out = seq_out; p.len_out = len_out; p.score_out = score_out;
     const size_t lds = beam_lds_bytes(beam, L, H, lo.Vp);
     if (lds > 160 * 1024) return I2L_ERR_UNSUPPORTED;
-    switch (beam) {
-        case 1: return launch_beam<1>(p, lds, s);
-        case 2: return launch_beam<2>(p, lds, s);
-        case 3: return launch_beam<3>(p, lds, s);
-        case 4: return launch_beam<4>(p, lds, s);
-        case 5: return launch_beam<5>(p, lds, s);
-        case 6: return launch_beam<6>(p, lds, s);
-        case 7: return launch_beam<7>(p, lds, s);
-        case 8: return launch_beam<8>(p, lds, s);
-        default: return I2L_ERR_UNSUPPORTED;
-    }
+    rc = I2L_ERR_UNSUPPORTED;
+    with_width<1, 2, 3, 4, 5, 6, 7, 8>(beam, [&](auto k) { rc = launch_beam<k>(p, lds, s); });
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1452,16 +1482,9 @@ int beam_batched_enqueue(const i2l_decoder_weights* w, const void* workspace, co
         float* c_next = bp.c + (size_t)((t + 1) & 1) * LRH;
         p.c = c_cur;
         launch_batched_step(p, tb_lstm, tb_logits, 0, s);
-        switch (beam) {
-            case 1: launch_beam_step_batched<1>(bp, nb != nullptr, c_cur, c_next, t, s); break;
-            case 2: launch_beam_step_batched<2>(bp, nb != nullptr, c_cur, c_next, t, s); break;
-            case 3: launch_beam_step_batched<3>(bp, nb != nullptr, c_cur, c_next, t, s); break;
-            case 4: launch_beam_step_batched<4>(bp, nb != nullptr, c_cur, c_next, t, s); break;
-            case 5: launch_beam_step_batched<5>(bp, nb != nullptr, c_cur, c_next, t, s); break;
-            case 6: launch_beam_step_batched<6>(bp, nb != nullptr, c_cur, c_next, t, s); break;
-            case 7: launch_beam_step_batched<7>(bp, nb != nullptr, c_cur, c_next, t, s); break;
-            default: launch_beam_step_batched<8>(bp, nb != nullptr, c_cur, c_next, t, s); break;
-        }
+        with_width<1, 2, 3, 4, 5, 6, 7, 8>(beam, [&](auto k) {
+            launch_beam_step_batched<k>(bp, nb != nullptr, c_cur, c_next, t, s);
+        });
         I2L_CHECK_LAUNCH();
     }
     if (nb)

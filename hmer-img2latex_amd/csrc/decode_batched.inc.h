@@ -7,7 +7,8 @@
 //                               cell in the epilogue.  A workgroup owns TB batch rows x 64 gate columns (16 hidden units,
 //                               all four gates) and reads only its own 64-column slab of the weights.
 //   logits_mfma_kernel<TB>      logits[B x Vp] = h_top . WoutT + boutP into the scratch, same tiles.
-//   select_batched_kernel       one wave per row: the row kernel's selection rule, ids, next token, finished rows.
+//   select_batched_kernel<Rule> one wave per row (select_row): the row kernel's selection rule under the rule's pick
+//                               policy (plain, or decode_constrained.inc.h's), ids, next token, finished rows.
 //
 // Products are split-bf16 (bf16_split.inc.h): both operands are split into three bf16 pieces while they are staged into
 // LDS in the matrix cores' operand layout, six partial products v_mfma_f32_16x16x32_bf16, fp32 accumulation, the small
@@ -127,44 +128,86 @@ __device__ __forceinline__ void commit_token_batched(const BatchedParams& p, int
     }
 }
 
-// Token selection of step t, one wave per row.  The rule is decode_kernel's ("output projection + token selection" in
-// decode.hip, the first copy): raw logits out, division by the temperature when it is not 1, first-index arg max, and for
-// I2L_SELECT_SOFTMAX the probabilities evaluated literally (exp(x - max) / sum in fp32, first index wins).
-__global__ __launch_bounds__(DB_NT) void select_batched_kernel(BatchedParams p, int t) {
-    if (*p.live == 0) return;
-    const StepWeights& w = p.w;
-    const int V = w.V, lane = threadIdx.x & 63;
-    const int row = blockIdx.x * (DB_NT / 64) + (threadIdx.x >> 6);
-    if (row >= p.B) return;
-    const float* x = p.lg + (size_t)row * w.Vp;
-    float* lo = p.logits_out ? p.logits_out + ((size_t)row * p.T + t) * V : nullptr;
+// THE PICK POLICY of the selection kernels (the arg max here, the sampling of sample_batched.inc.h).  A kernel template
+// takes a rule as a launch argument -- NoRule, or ConstrainRule (decode_constrained.inc.h) -- and rule.row(...) gives
+// each thread the policy of its row at this step:
+//   allows(v, c), operator()(v)   may column v be picked (c = cls(v), its class byte)
+//   mask()                        where the row's allowed set is written, or null
+//   winner_cls(c, v)              in every lane of the wave: the c of the lane that owns column v (v & 63)
+//   finish_argmax, finish_sample  by ONE thread: the token to commit from what the selection returned, and the policy's
+//                                 own state, if it keeps any
+// AllowAll is the plain model: every column, no class byte, no state.  It must cost nothing -- each member is a constant
+// that folds, so a plain instantiation is the kernel as one would write it without a policy, register for register.
+struct AllowAll {
+    __device__ __forceinline__ uint8_t cls(int) const { return 0; }
+    __device__ __forceinline__ bool allows(int, uint8_t) const { return true; }
+    __device__ __forceinline__ bool operator()(int) const { return true; }
+    __device__ __forceinline__ uint8_t* mask() const { return nullptr; }
+    __device__ __forceinline__ int winner_cls(int, int) const { return 0; }
+    __device__ __forceinline__ int finish_argmax(int V, int pick, int) const { return pick < V ? pick : 0; }
+    __device__ __forceinline__ int finish_sample(int, int pick) const { return pick; }
+};
+struct NoRule {
+    __device__ __forceinline__ AllowAll row(int, int, int, int) const { return {}; }
+};
+
+// One row by one wave.  The rule is decode_kernel's ("output projection + token selection" in decode.hip, the first
+// copy) over the allowed columns of x[0, V): raw logits out (lo, V floats or null), division by the temperature when it
+// is not 1, first-index arg max, and for I2L_SELECT_SOFTMAX the probabilities evaluated literally (exp(x - max) / sum in
+// fp32, first index wins).  Every lane returns the arg max and in *pick_cls its class byte -- the winner is the local
+// best of the lane that owns its column, which hands the class over, so that nothing is loaded between the selection
+// and the commit -- or 0x7fffffff and -1 if no allowed column holds a logit above -inf.
+template <class Pick>
+__device__ __forceinline__ int select_row(const float* __restrict__ x, int V, float temperature, int use_temp, int select,
+                                          const Pick& al, float* __restrict__ lo, int lane, int* pick_cls) {
+    uint8_t* mask = al.mask();
     float best = -INFINITY;
-    int besti = 0x7fffffff;
-    for (int v = lane; v < w.Vp; v += 64) {
+    int besti = 0x7fffffff, bestc = 0;
+    for (int v = lane; v < V; v += 64) {
         float a = x[v];
-        if (lo && v < V) lo[v] = a;
-        if (p.use_temp) a = a / p.temperature;
-        if (a > best) { best = a; besti = v; }
+        const uint8_t c = al.cls(v);
+        const bool ok = al.allows(v, c);
+        if (lo) lo[v] = a;
+        if (mask) mask[v] = ok ? 1 : 0;
+        if (use_temp) a = a / temperature;
+        if (ok && a > best) { best = a; besti = v; bestc = c; }
     }
     wave_argmax(best, besti);
-    if (p.select == I2L_SELECT_SOFTMAX) {
+    if (select == I2L_SELECT_SOFTMAX && besti < V) {
         float s = 0.f;
         for (int v = lane; v < V; v += 64) {
-            const float a = p.use_temp ? x[v] / p.temperature : x[v];
-            s += expf(a - best);
+            const float a = use_temp ? x[v] / temperature : x[v];
+            if (al(v)) s += expf(a - best);
         }
         s = wave_sum(s);
         float pbest = -1.f;
         int pbesti = 0x7fffffff;
         for (int v = lane; v < V; v += 64) {
-            const float a = p.use_temp ? x[v] / p.temperature : x[v];
+            const float a = use_temp ? x[v] / temperature : x[v];
             const float pr = expf(a - best) / s;
-            if (pr > pbest) { pbest = pr; pbesti = v; }
+            const uint8_t c = al.cls(v);
+            if (al.allows(v, c) && pr > pbest) { pbest = pr; pbesti = v; bestc = c; }
         }
         wave_argmax(pbest, pbesti);
         besti = pbesti;
     }
-    if (lane == 0) commit_token_batched(p, row, t, besti < V ? besti : 0);
+    const int c = al.winner_cls(bestc, besti);
+    *pick_cls = besti < V ? c : -1;
+    return besti;
+}
+
+// Token selection of step t, one wave per row, under NoRule or ConstrainRule.  grid cdiv(B, DB_NT / 64).
+template <class Rule>
+__global__ __launch_bounds__(DB_NT) void select_batched_kernel(BatchedParams p, Rule r, int t) {
+    if (*p.live == 0) return;
+    const int V = p.w.V, lane = threadIdx.x & 63;
+    const int row = blockIdx.x * (DB_NT / 64) + (threadIdx.x >> 6);
+    if (row >= p.B) return;
+    const auto al = r.row(row, V, p.end_id, p.T - t - 1);
+    float* lo = p.logits_out ? p.logits_out + ((size_t)row * p.T + t) * V : nullptr;
+    int pick_cls;
+    const int pick = select_row(p.lg + (size_t)row * p.w.Vp, V, p.temperature, p.use_temp, p.select, al, lo, lane, &pick_cls);
+    if (lane == 0) commit_token_batched(p, row, t, al.finish_argmax(V, pick, pick_cls));
 }
 
 // state in, tokens, finished marks, the live-row count and ids = -1 (steps an early end never runs)

@@ -6,8 +6,9 @@
 //                         of the k-th largest probability (four 8-bit digits of the bit pattern, a 256-bin count each),
 //                         the top-p mask from a BITONIC SORT of (bit pattern, index) keys and a scan of the sorted
 //                         masses, the draw from a scan of the final distribution in index order.
-//   sample_batched_kernel the last launch of a step of i2l_sample_decode_batched, in select_batched_kernel's place.
-//   sample_logits_kernel  the same row function over a caller's logits (i2l_sample_logits).
+//   sample_batched_kernel<Rule>  the last launch of a step of i2l_sample_decode_batched, in select_batched_kernel's place.
+//   sample_logits_kernel<Rule>   the same row function over a caller's logits (i2l_sample_logits).
+// Rule is NoRule or ConstrainRule: the pick policy of decode_batched.inc.h, which sample_row takes as `allow`.
 //
 // Probabilities are >= 0, so their bit patterns order as the values do.  A key is (pattern << 32) | ~index: descending
 // keys are descending values with the lower index first among equal ones, and no two keys are equal.  Every sum is a
@@ -135,11 +136,6 @@ __device__ __forceinline__ void bitonic_desc(unsigned long long* key, int N, int
     }
 }
 
-// every column may be drawn: the plain kernels' `allow`
-struct AllowAll {
-    __device__ __forceinline__ bool operator()(int) const { return true; }
-};
-
 // One row: x[0, V) raw logits, u the row's uniform of this step.  Every thread returns the pick; po (V floats or null)
 // receives the final distribution.  V <= SB_MAXV, blockDim.x == NT.  A column v with !allow(v) enters as -INFINITY: its
 // probability is exactly 0 and the others renormalise (decode_constrained.inc.h); the result is 0x7fffffff or a
@@ -216,26 +212,34 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ x, int V, fl
     return pick < V ? pick : besti[0];          // rounding corner: fall back to the arg max
 }
 
-// Token selection of step t by sampling, one workgroup per row.  ids, next token, finished rows and the live-row count as
-// select_batched_kernel.
-__global__ __launch_bounds__(NT) void sample_batched_kernel(BatchedParams p, SampleRule r, int t) {
+// Token selection of step t by sampling, one workgroup per row, under NoRule or ConstrainRule.  ids, next token, finished
+// rows and the live-row count as select_batched_kernel.
+template <class Rule>
+__global__ __launch_bounds__(NT) void sample_batched_kernel(BatchedParams p, SampleRule r, Rule c, int t) {
     __shared__ SampleLds s;
     if (*p.live == 0) return;
     const int V = p.w.V, row = blockIdx.x, tid = threadIdx.x;
+    const auto al = c.row(row, V, p.end_id, p.T - t - 1);
     float* po = r.probs ? r.probs + ((size_t)row * p.T + t) * V : nullptr;
     const int pick = sample_row(p.lg + (size_t)row * p.w.Vp, V, p.temperature, p.use_temp, r.top_k, r.top_p,
-                                uniform01(r.seed, (unsigned)row, (unsigned)t), po, s, tid, AllowAll{});
-    if (tid == 0) commit_token_batched(p, row, t, pick);
+                                uniform01(r.seed, (unsigned)row, (unsigned)t), po, s, tid, al);
+    // every thread took its copy of the policy before the first barrier of sample_row; thread 0 stores behind the last one
+    if (tid == 0) commit_token_batched(p, row, t, al.finish_sample(V, pick));
 }
 
-// i2l_sample_logits: the rule applied once to (rows, ld) logits of the caller, one workgroup per row.
+// i2l_sample_logits, and under ConstrainRule the sampling branch of i2l_constrained_pick_logits: the rule applied once
+// to (rows, ld) logits of the caller, one workgroup per row.  end_id and rem are the constraint's (NoRule reads neither).
+template <class Rule>
 __global__ __launch_bounds__(NT) void sample_logits_kernel(const float* __restrict__ logits, int ld, int V, float temperature,
-                                                           int use_temp, SampleRule r, unsigned step,
-                                                           int32_t* __restrict__ ids) {
+                                                           int use_temp, SampleRule r, unsigned step, Rule c, int end_id,
+                                                           int rem, int32_t* __restrict__ ids) {
     __shared__ SampleLds s;
     const int row = blockIdx.x, tid = threadIdx.x;
+    const auto al = c.row(row, V, end_id, rem);
+    if (uint8_t* mask = al.mask())
+        for (int v = tid; v < V; v += NT) mask[v] = al(v) ? 1 : 0;
     float* po = r.probs ? r.probs + (size_t)row * V : nullptr;
     const int pick = sample_row(logits + (size_t)row * ld, V, temperature, use_temp, r.top_k, r.top_p,
-                                uniform01(r.seed, (unsigned)row, step), po, s, tid, AllowAll{});
-    if (tid == 0) ids[row] = pick;
+                                uniform01(r.seed, (unsigned)row, step), po, s, tid, al);
+    if (tid == 0) ids[row] = al.finish_sample(V, pick);
 }

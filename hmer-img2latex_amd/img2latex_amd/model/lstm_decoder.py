@@ -183,6 +183,35 @@ class LSTMDecoder(nn.Module):
         st = self._ws[off:off + 16].view(torch.int32).cpu().tolist()
         return {"timed_out": bool(st[0]), "groups": st[1], "groups_on_one_xcd": st[2]}
 
+    def _hidden(self, hidden: Optional[Hidden], rows: int):
+        """(h0, c0) of a caller's state on the device, each (layers, rows, hidden_dim) -- the kernels read exactly that
+        many floats behind the pointer -- or (None, None)."""
+        if hidden is None:
+            return None, None
+        h0, c0 = _lib.require_gpu(hidden[0], "h0"), _lib.require_gpu(hidden[1], "c0")
+        shp = (self.lstm_layers, rows, self.hidden_dim)
+        if tuple(h0.shape) != shp or tuple(c0.shape) != shp:
+            raise RuntimeError(f"hidden state must be {shp}, got {tuple(h0.shape)} / {tuple(c0.shape)}")
+        return h0, c0
+
+    def _outputs(self, rows: int, steps: int, dev, want_ids: bool, want_dist: bool, want_state: bool):
+        """(ids, logits or probs, h, c) of one decode loop: uninitialised tensors for what is wanted, None for the rest."""
+        ids = torch.empty((rows, steps), dtype=torch.int32, device=dev) if want_ids else None
+        dist = torch.empty((rows, steps, self.vocab_size), dtype=torch.float32, device=dev) if want_dist else None
+        h = c = None
+        if want_state:
+            h = torch.empty((self.lstm_layers, rows, self.hidden_dim), dtype=torch.float32, device=dev)
+            c = torch.empty_like(h)
+        return ids, dist, h, c
+
+    def _batched_scratch(self, rows: int, dev):
+        """(scratch, its size) of one step-batched call (decode_batched.inc.h): it lives for that call only, on this
+        stream -- the caching allocator hands the block out again only in stream order."""
+        nbytes = _lib.lib().i2l_decode_batched_scratch_bytes(rows, self.vocab_size, self.hidden_dim, self.lstm_layers)
+        if nbytes == 0:
+            raise RuntimeError("img2latex_amd: decoder dimensions not supported by the step-batched decode")
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
     def run_steps(self, encoder_output: torch.Tensor, steps: int, tok0: torch.Tensor,
                   forced: Optional[torch.Tensor] = None, hidden: Optional[Hidden] = None,
                   temperature: float = 1.0, select: int = _lib.SELECT_LOGITS, stop: int = _lib.STOP_NONE,
@@ -208,19 +237,8 @@ class LSTMDecoder(nn.Module):
             forced = _lib.require_gpu(forced, "forced", torch.int32)
             if forced.shape != (rows, steps):
                 raise RuntimeError(f"forced tokens must be ({rows},{steps}), got {tuple(forced.shape)}")
-        h0 = c0 = None
-        if hidden is not None:
-            h0 = _lib.require_gpu(hidden[0], "h0")
-            c0 = _lib.require_gpu(hidden[1], "c0")
-            shp = (self.lstm_layers, rows, self.hidden_dim)
-            if tuple(h0.shape) != shp or tuple(c0.shape) != shp:
-                raise RuntimeError(f"hidden state must be {shp}, got {tuple(h0.shape)} / {tuple(c0.shape)}")
-        ids = torch.empty((rows, steps), dtype=torch.int32, device=dev) if want_ids else None
-        logits = torch.empty((rows, steps, self.vocab_size), dtype=torch.float32, device=dev) if want_logits else None
-        h = c = None
-        if want_state:
-            h = torch.empty((self.lstm_layers, rows, self.hidden_dim), dtype=torch.float32, device=dev)
-            c = torch.empty_like(h)
+        h0, c0 = self._hidden(hidden, rows)
+        ids, logits, h, c = self._outputs(rows, steps, dev, want_ids, want_logits, want_state)
         all_flags = int(flags) | int(self.kernel_flags)
         res_ptr = None if resident is None else resident[0].data_ptr()
         res_val = 0 if resident is None else int(resident[1]) & 0xFFFFFFFF
@@ -234,28 +252,22 @@ class LSTMDecoder(nn.Module):
                 scratch.data_ptr(), nbytes, all_flags, res_ptr, res_val, cls.data_ptr(), state.data_ptr(), state.numel(),
                 _lib.stream_ptr()), "greedy_decode_constrained")
             _lib.mark("decode")
-            del keep, scratch, state   # the caching allocator hands the blocks out again only in stream order
+            del keep, scratch, state
             return ids, logits, ((h, c) if want_state else None)
         if all_flags & _lib.FLAG_DECODE_BATCHED:
-            # step-batched matrix-core path (decode_batched.inc.h): its scratch lives for this call only, on this stream
-            nbytes = _lib.lib().i2l_decode_batched_scratch_bytes(rows, self.vocab_size, self.hidden_dim, self.lstm_layers)
-            if nbytes == 0:
-                raise RuntimeError("img2latex_amd: decoder dimensions not supported by the step-batched decode")
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            scratch, nbytes = self._batched_scratch(rows, dev)      # step-batched matrix-core path
             _lib.check(_lib.lib().i2l_greedy_decode_batched(
                 ctypes.byref(w), ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(forced), _lib.ptr(h0),
                 _lib.ptr(c0), float(temperature), select, stop, int(end_id), _lib.ptr(ids), _lib.ptr(logits),
                 _lib.ptr(h), _lib.ptr(c), scratch.data_ptr(), nbytes, all_flags, res_ptr, res_val, _lib.stream_ptr()),
                 "greedy_decode_batched")
             _lib.mark("decode")
-            del keep, scratch      # the caching allocator hands the block out again only in stream order
+            del keep, scratch
             return ids, logits, ((h, c) if want_state else None)
         _lib.check(_lib.lib().i2l_greedy_decode_ex(
             ctypes.byref(w), ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(forced), _lib.ptr(h0),
             _lib.ptr(c0), float(temperature), select, stop, int(end_id), int(rows_per_workgroup), _lib.ptr(ids),
-            _lib.ptr(logits), _lib.ptr(h), _lib.ptr(c), int(flags) | int(self.kernel_flags),
-            None if resident is None else resident[0].data_ptr(), 0 if resident is None else int(resident[1]) & 0xFFFFFFFF,
-            _lib.stream_ptr()), "greedy_decode")
+            _lib.ptr(logits), _lib.ptr(h), _lib.ptr(c), all_flags, res_ptr, res_val, _lib.stream_ptr()), "greedy_decode")
         _lib.mark("decode")
         del keep
         return ids, logits, ((h, c) if want_state else None)
@@ -266,11 +278,9 @@ class LSTMDecoder(nn.Module):
             raise RuntimeError(f"img2latex_amd: the constraint's table has {constraint.vocab} columns, the decoder's "
                                f"vocabulary {self.vocab_size}")
         constraint._end(end_id)                            # inside the table, and neutral there
-        nbytes = _lib.lib().i2l_decode_batched_scratch_bytes(rows, self.vocab_size, self.hidden_dim, self.lstm_layers)
-        if nbytes == 0:
-            raise RuntimeError("img2latex_amd: decoder dimensions not supported by the step-batched decode")
+        scratch, nbytes = self._batched_scratch(rows, dev)
         state = torch.empty(_lib.lib().i2l_bracket_state_bytes(rows), dtype=torch.uint8, device=dev)   # zeroed by the call
-        return constraint.device(dev), state, torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+        return constraint.device(dev), state, scratch, nbytes
 
     def halves_supported(self, stop: int = _lib.STOP_NONE) -> bool:
         """True where ``decode_halves`` has a kernel: the 16-member grouped decode's dimensions, no sticky stop."""
@@ -317,43 +327,33 @@ class LSTMDecoder(nn.Module):
         FLAG_DECODE_BATCHED`` the step-batched i2l_sample_decode_batched.  Returns (ids, probs or None), with
         ``want_state`` (ids, probs or None, (h, c)).  ``constraint`` = a BracketTable: the bracket-constrained
         i2l_sample_decode_constrained, whatever the flags say (see ``run_steps``)."""
+        h0, c0 = self._hidden(hidden, encoder_output.shape[0])     # refused before anything is launched
         w, keep, enc = self.prepare(encoder_output)
         rows, dev = enc.shape[0], enc.device
         tok0 = _lib.require_gpu(tok0, "tok0", torch.int32)
-        h0 = c0 = None
-        if hidden is not None:
-            h0, c0 = _lib.require_gpu(hidden[0], "h0"), _lib.require_gpu(hidden[1], "c0")
-        ids = torch.empty((rows, steps), dtype=torch.int32, device=dev)
-        probs = torch.empty((rows, steps, self.vocab_size), dtype=torch.float32, device=dev) if want_probs else None
-        h = c = None
-        if want_state:
-            h = torch.empty((self.lstm_layers, rows, self.hidden_dim), dtype=torch.float32, device=dev)
-            c = torch.empty_like(h)
+        ids, probs, h, c = self._outputs(rows, steps, dev, True, want_probs, want_state)
         all_flags = int(flags) | int(self.kernel_flags)
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         if constraint is not None:
             cls, state, scratch, nbytes = self._constraint_buffers(constraint, rows, end_id, dev)
             _lib.check(_lib.lib().i2l_sample_decode_constrained(
                 ctypes.byref(w), self._ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
-                float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, stop, int(end_id),
+                float(temperature), int(top_k), float(top_p), seed, stop, int(end_id),
                 ids.data_ptr(), _lib.ptr(probs), _lib.ptr(h), _lib.ptr(c), scratch.data_ptr(), nbytes, all_flags,
                 cls.data_ptr(), state.data_ptr(), state.numel(), _lib.stream_ptr()), "sample_decode_constrained")
             del scratch, state
         elif all_flags & _lib.FLAG_DECODE_BATCHED:
-            # step-batched matrix-core path (sample_batched.inc.h): its scratch lives for this call only, on this stream
-            nbytes = _lib.lib().i2l_decode_batched_scratch_bytes(rows, self.vocab_size, self.hidden_dim, self.lstm_layers)
-            if nbytes == 0:
-                raise RuntimeError("img2latex_amd: decoder dimensions not supported by the step-batched decode")
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            scratch, nbytes = self._batched_scratch(rows, dev)      # step-batched matrix-core path
             _lib.check(_lib.lib().i2l_sample_decode_batched(
                 ctypes.byref(w), self._ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
-                float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, stop, int(end_id),
+                float(temperature), int(top_k), float(top_p), seed, stop, int(end_id),
                 ids.data_ptr(), _lib.ptr(probs), _lib.ptr(h), _lib.ptr(c), scratch.data_ptr(), nbytes, all_flags,
                 _lib.stream_ptr()), "sample_decode_batched")
-            del scratch            # the caching allocator hands the block out again only in stream order
+            del scratch
         else:
             _lib.check(_lib.lib().i2l_sample_decode(
                 ctypes.byref(w), self._ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
-                float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, stop, int(end_id),
+                float(temperature), int(top_k), float(top_p), seed, stop, int(end_id),
                 ids.data_ptr(), _lib.ptr(probs), _lib.ptr(h), _lib.ptr(c), _lib.stream_ptr()), "sample_decode")
         del keep
         return (ids, probs, (h, c)) if want_state else (ids, probs)

@@ -302,7 +302,7 @@ def _step(m, rows=2, **kw):
 
 
 @pytest.mark.parametrize("what", ["H=96", "E=30", "L=5", "H=2112", "training H=1088", "softmax V=3073 H=2048",
-                                  "sampling V=2049", "beam Vp>2048", "beam k=8 at E=H=512 L=2", "beam k>V"])
+                                  "sampling V=2049", "sampling hidden of 1 row for 2", "beam Vp>2048", "beam k=8 at E=H=512 L=2", "beam k>V"])
 def test_decoder_refusals(what):
     """Dimensions outside DESIGN.md's table raise through the Python surface (the C ABI refuses before it launches
     anything) instead of returning numbers."""
@@ -329,6 +329,17 @@ def test_decoder_refusals(what):
         tok0 = torch.full((2,), START, dtype=torch.int32, device=DEV)
         with pytest.raises(RuntimeError):
             m.decoder.sample_steps(torch.zeros(2, 4, device=DEV), 3, tok0, 1.0, 5, 0.0, 1)
+    elif what == "sampling hidden of 1 row for 2":
+        m = _model(10, 4, 64, 1)
+        tok0 = torch.full((2,), START, dtype=torch.int32, device=DEV)
+        short, right = torch.zeros(1, 1, 64, device=DEV), torch.zeros(1, 2, 64, device=DEV)
+        for hidden in ((short, short), (right, short), (short, right)):
+            for flags in (0, _lib.FLAG_DECODE_BATCHED):
+                with pytest.raises(RuntimeError, match="hidden state must be"):      # run_steps' refusal, same words
+                    m.decoder.sample_steps(torch.zeros(2, 4, device=DEV), 3, tok0, 1.0, 5, 0.0, 1, hidden=hidden, flags=flags)
+        assert m.decoder._ws is None                                 # refused before the workspace: nothing was launched
+        with pytest.raises(RuntimeError, match="hidden state must be"):
+            _step(m, hidden=(short, short))
     elif what == "beam Vp>2048":
         m = _model(2049, 4, 64, 1)
         with pytest.raises(RuntimeError):
