@@ -1,7 +1,7 @@
 // Step-batched beam search on the MATRIX CORES for decoders the grouped beam kernel does not take (the shipped 2 x 512
 // one): the K slots of every image are rows of ONE batched step, R = images * K rows, row r = slot r % K of image r / K
-// (included by decode.hip inside its anonymous namespace, after decode_batched.inc.h and beam_rules.inc.h).  Reference
-// seq2seq.py:234-298.
+// (included by decode.hip inside its anonymous namespace, after decode_constrained.inc.h and beam_bracket_rules.inc.h).
+// Reference seq2seq.py:234-298.
 //
 // Per step the host enqueues L launches of lstm_step_mfma_kernel<TB> and one of logits_mfma_kernel<TB> on the R rows
 // (decode_batched.inc.h, unchanged but for the Genc row: a beam row reads the encoder half of its image, row / K), then
@@ -66,16 +66,22 @@ __global__ __launch_bounds__(DB_NT) void beam_init_batched_kernel(BeamBatchedPar
 
 // Ranking, gather and retirement of step t (after its logits launch).  grid images; c_cur: the buffer the step's LSTM
 // launches updated, c_next: the one the next step's get.  NBEST: the kernel of i2l_beam_decode_nbest, the same step with
-// the image's list as the sink.
-template <int K, bool NBEST = false>
+// the image's list as the sink.  Rule: the slots' pick policy (decode_batched.inc.h) -- NoRule, or ConstrainRule for the
+// well-formed search (beam_constrained.inc.h), where slot r0 + q keeps 16 bytes of bracket state in rule.state: phase (c)
+// ranks the columns the slot's state allows, (d) gets the slots' candidate counts, and after (d) new slot q takes its
+// parent's state advanced by its token.  Everything of it is under `if constexpr`: with NoRule this is the kernel without.
+template <int K, bool NBEST = false, class Rule = NoRule>
 __global__ __launch_bounds__(DB_NT) void beam_step_batched_kernel(BeamBatchedParams p, float* __restrict__ c_cur,
-                                                                  float* __restrict__ c_next, int t) {
+                                                                  float* __restrict__ c_next, int t, Rule rule) {
+    constexpr bool CON = std::is_same_v<Rule, ConstrainRule>;
     __shared__ double nscore[K];
     __shared__ float topv[K * K];                        // [K][K] log-probs, descending
     __shared__ int topi[K * K];
     __shared__ int npar[K], ntok[K], ctl[1];
     __shared__ double oscore[K];                         // the slots' scores and live flags as the step found them: the
     __shared__ int olive[K];                             // serial ranking of (d) reads them K * K times over
+    __shared__ BracketState ostate[CON ? K : 1];         // and their bracket states: a parent's is read after (d)
+    __shared__ int ncand[CON ? K : 1];                   // candidates of each live slot, 1 .. K
     if (*p.live == 0) return;
     const int img = blockIdx.x;
     BeamImage* im = p.img + img;
@@ -88,17 +94,28 @@ __global__ __launch_bounds__(DB_NT) void beam_step_batched_kernel(BeamBatchedPar
     int32_t* tokhist = p.tokhist + (size_t)img * T * K;
     int32_t* parhist = p.parhist + (size_t)img * T * K;
 
-    if (tid < K) { oscore[tid] = score[tid]; olive[tid] = slot_live[tid]; }
+    if (tid < K) {
+        oscore[tid] = score[tid]; olive[tid] = slot_live[tid];
+        if constexpr (CON) ostate[tid] = rule.state[r0 + tid];
+    }
 
-    // (c) log_softmax and top-K, a wave per live slot
+    // (c) log_softmax and top-K, a wave per live slot; the policy's state is the slot's in global memory, loaded once
     for (int r = wave; r < K; r += DB_NT / 64)
-        if (slot_live[r]) beam_topk_row(p.lg + (r0 + r) * Vp, V, K, lane, topv + r * K, topi + r * K);   // wave-uniform
+        if (slot_live[r]) {                              // wave-uniform
+            const auto al = rule.row((int)r0 + r, V, p.end_id, T - t - 1);
+            [[maybe_unused]] const int n = beam_topk_row(p.lg + (r0 + r) * Vp, V, K, lane, al, topv + r * K, topi + r * K);
+            if constexpr (CON)
+                if (lane == 0) ncand[r] = bb_close_list(n, p.end_id, topv + r * K, topi + r * K);
+        }
     __syncthreads();
 
     // (d) the ranking of the K x K candidates and the history rows
     if (tid == 0)
-        ctl[0] = beam_rank(olive, oscore, topv, topi, K, npar, ntok, nscore, tokhist + (size_t)t * K, parhist + (size_t)t * K);
+        ctl[0] = beam_rank(olive, oscore, topv, topi, K, CON ? ncand : nullptr, npar, ntok, nscore, tokhist + (size_t)t * K,
+                           parhist + (size_t)t * K);
     __syncthreads();
+    if constexpr (CON)
+        if (tid < ctl[0]) rule.state[r0 + tid] = bb_inherit(ostate, npar[tid], ntok[tid], p.end_id, rule.cls);
 
     // (e) new slot q inherits the fresh state of its parent (hidden.clone(), :272): h[1] -> h[0], c_cur -> c_next
     {

@@ -1,8 +1,9 @@
 // The serial rules of the beam search (reference seq2seq.py:249-297), stated once: what retires into `completed`, how
 // the K x K candidates of a step are ranked, how a step ends, how a result is read back from the histories.  These are
 // the decisions whose tie behaviour is pinned to the reference token for token: first on ties, strict >, stable order.
-// Shared by beam_kernel<K> (decode.hip), the step-batched kernels (beam_batched.inc.h, beam_nbest.inc.h) and a
-// stand-alone host program (beam_rules_host_main.cpp) that a host test feeds with exact score ties.
+// Shared by beam_kernel<K> (decode.hip), the step-batched kernels (beam_batched.inc.h, beam_nbest.inc.h), the
+// well-formed search's rules (beam_bracket_rules.inc.h) and two stand-alone host programs (beam_rules_host_main.cpp,
+// beam_constrained_host_main.cpp) that host tests feed with exact score ties.
 //
 // Plain C++, no HIP: BEAM_HD is `__host__ __device__` under hipcc and empty elsewhere.  Every function is called by ONE
 // thread; the arrays it gets are the caller's (LDS, registers or global memory on the device, vectors on the host).
@@ -103,13 +104,24 @@ BEAM_HD void beam_start(BeamImage& im, const Sink& completed, double* score, int
 // selection of K by K rounds of strict > (:268-280).  topv / topi: [K][K], the top K log-probs of each live slot's row,
 // descending, and their tokens.  Writes the new beams' parent slots, tokens and scores, the step's two history rows
 // and zeroes in the slots nnew .. K - 1; returns nnew.  K * K <= 64.
-BEAM_HD int beam_rank(const int* live, const double* score, const float* topv, const int* topi, int K, int* npar,
-                      int* ntok, double* nscore, int32_t* tokrow, int32_t* parrow) {
-    int nlive = 0;
-    for (int q = 0; q < K; ++q) nlive += live[q];
-    const int ncand = nlive * K;
-    const int nnew = ncand < K ? ncand : K;
-    unsigned long long used = 0ull;                      // candidate flags
+// ncand: [K], how many of its K entries live slot s really has, 0 .. K (the bracket-constrained search,
+// beam_bracket_rules.inc.h: a slot may extend by fewer than K columns); entries j >= ncand[s] are never read and
+// nnew = min(K, sum over the live slots of ncand[s]).  Null: K for every slot, the unconstrained search.
+BEAM_HD int beam_rank(const int* live, const double* score, const float* topv, const int* topi, int K, const int* ncand,
+                      int* npar, int* ntok, double* nscore, int32_t* tokrow, int32_t* parrow) {
+    int nlive = 0, counted = 0;
+    for (int q = 0; q < K; ++q) {
+        nlive += live[q];
+        if (ncand && live[q]) counted += ncand[q];
+    }
+    const int total = ncand ? counted : nlive * K;       // a null count folds to the arithmetic of the unconstrained search
+    const int nnew = total < K ? total : K;
+    unsigned long long used = 0ull;                      // candidate flags; an entry a slot does not have counts as used,
+    if (ncand)                                           // so the rounds below keep their constant bounds
+        for (int s0 = 0; s0 < K; ++s0) {
+            if (!live[s0]) continue;
+            for (int j = ncand[s0]; j < K; ++j) used |= 1ull << (s0 * K + j);
+        }
     for (int q = 0; q < nnew; ++q) {
         double bs = 0.0;
         int bc = -1;

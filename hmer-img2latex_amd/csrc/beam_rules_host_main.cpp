@@ -40,7 +40,7 @@ struct Search {
         beam_start(im, completed, score.data(), last.data(), live.data(), K, c.start_id, c.end_id);
         for (int t = 0; t < c.T && !im.done; ++t) {
             const size_t at = (size_t)t * K * K;
-            const int nnew = beam_rank(live.data(), score.data(), c.logp.data() + at, c.token.data() + at, K, npar.data(),
+            const int nnew = beam_rank(live.data(), score.data(), c.logp.data() + at, c.token.data() + at, K, nullptr, npar.data(),
                                        ntok.data(), nscore.data(), tokhist.data() + (size_t)t * K, parhist.data() + (size_t)t * K);
             beam_step_end(im, completed, nnew, ntok.data(), nscore.data(), score.data(), last.data(), live.data(), K,
                           c.end_id, t, c.T);

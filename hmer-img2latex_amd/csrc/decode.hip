@@ -242,15 +242,31 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned row
 // Phase (c) of a beam step for one live slot, by one wave: log_softmax of the row x[0, V) in fp32 (seq2seq.py:266) and
 // its top K (:267: descending, the lower index first on ties) by K rounds of first-index wave arg max.  Lane 0 writes
 // topv[0, K) / topi[0, K).  V <= 2048: the taken-mask has 32 bits per lane.
-__device__ __forceinline__ void beam_topk_row(const float* x, int V, int K, int lane, float* topv, int* topi) {
+//
+// `al` is the slot's pick policy, the one select_row takes (decode_batched.inc.h).  Under AllowAll every test of it is a
+// constant and this is the function as written above.  Under a policy that forbids columns (beam_constrained.inc.h) the
+// class byte is read beside the logit ONCE, in the max pass, into a 32-bit mask per lane; max, sum, log and the arg-max
+// rounds run over the allowed columns only -- a forbidden column enters the softmax as -inf, the constrained sampler's
+// convention.
+// Returns, in every lane, how many rounds found a column: the list ends at the first one that finds none (every later
+// round finds none either; the plain list is read to K all the same, as it always was).
+template <class Pick>
+__device__ __forceinline__ int beam_topk_row(const float* x, int V, int K, int lane, const Pick& al, float* topv, int* topi) {
+    unsigned off = 0;                                    // bit i: element lane + 64*i is not allowed
     float m = -INFINITY;
-    for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
+    for (int v = lane, i = 0; v < V; v += 64, ++i) {
+        const float a = x[v];
+        if (al.allows(v, al.cls(v))) m = fmaxf(m, a);
+        else off |= 1u << i;
+    }
     m = wave_max(m);
     float s = 0.f;
-    for (int v = lane; v < V; v += 64) s += expf(x[v] - m);
+    for (int v = lane, i = 0; v < V; v += 64, ++i)
+        if (!((off >> i) & 1u)) s += expf(x[v] - m);
     s = wave_sum(s);
     const float lse = logf(s);
-    unsigned taken = 0;                                  // bit i: element lane + 64*i already selected
+    unsigned taken = off;                                // bit i: element lane + 64*i already selected, or not allowed
+    int n = 0;
     for (int j = 0; j < K; ++j) {
         float bv = -INFINITY;
         int bi = 0x7fffffff;
@@ -259,7 +275,9 @@ __device__ __forceinline__ void beam_topk_row(const float* x, int V, int K, int 
         wave_argmax(bv, bi);
         if (bi < V && (bi & 63) == lane) taken |= 1u << (bi >> 6);
         if (lane == 0) { topv[j] = (bv - m) - lse; topi[j] = bi < V ? bi : 0; }
+        if (bi < V) ++n;                                 // a round without a column: so are all later ones
     }
+    return n;
 }
 
 #include "decode_group.inc.h"
@@ -269,9 +287,10 @@ __device__ __forceinline__ void beam_topk_row(const float* x, int V, int K, int 
 #include "sample_batched.inc.h"
 #include "bracket_rules.inc.h"
 #include "decode_constrained.inc.h"
-#include "beam_rules.inc.h"
+#include "beam_bracket_rules.inc.h"
 #include "beam_batched.inc.h"
 #include "beam_nbest.inc.h"
+#include "beam_constrained.inc.h"
 
 // KR / KL > 0 (fast path for R == 1, L == 1, H <= 256: thread j owns hidden unit j for the whole loop):
 // rows [0,KR) of WhhT stay in the thread's registers and rows [KR,KR+KL) in LDS for all steps, so only
@@ -636,12 +655,12 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamParams p) {
 
         // (c) log_softmax and top-K, a wave per live slot
         for (int r = wave; r < K; r += NT / 64)
-            if (live[r]) beam_topk_row(lg + (size_t)r * Vp, V, K, lane, topv + r * K, topi + r * K);   // wave-uniform
+            if (live[r]) beam_topk_row(lg + (size_t)r * Vp, V, K, lane, AllowAll{}, topv + r * K, topi + r * K);   // wave-uniform
         __syncthreads();
 
         // (d) the ranking of the K x K candidates and the history rows
         if (tid == 0)
-            nnew = beam_rank(live, score, topv, topi, K, npar, ntok, nscore, tokhist + (size_t)t * K, parhist + (size_t)t * K);
+            nnew = beam_rank(live, score, topv, topi, K, nullptr, npar, ntok, nscore, tokhist + (size_t)t * K, parhist + (size_t)t * K);
         __syncthreads();
 
         // (e) new beam q inherits the fresh state of its parent (hidden.clone(), :272): gather into the other buffers
@@ -1433,19 +1452,27 @@ extern "C" size_t i2l_beam_batched_scratch_bytes(int images, int beam, int vocab
 }
 
 namespace {
-// nbest: the step that keeps every completed beam (beam_nbest.inc.h)
+// nbest: the step that keeps every completed beam (beam_nbest.inc.h); con: that step under the bracket constraint
+// (beam_constrained.inc.h)
 template <int K>
-void launch_beam_step_batched(const BeamBatchedParams& p, bool nbest, float* c_cur, float* c_next, int t, hipStream_t s) {
-    if (nbest) hipLaunchKernelGGL((beam_step_batched_kernel<K, true>), dim3(p.images), dim3(DB_NT), 0, s, p, c_cur, c_next, t);
-    else hipLaunchKernelGGL((beam_step_batched_kernel<K, false>), dim3(p.images), dim3(DB_NT), 0, s, p, c_cur, c_next, t);
+void launch_beam_step_batched(const BeamBatchedParams& p, bool nbest, const ConstrainRule* con, float* c_cur, float* c_next,
+                              int t, hipStream_t s) {
+    if (con)
+        hipLaunchKernelGGL((beam_step_batched_kernel<K, true, ConstrainRule>), dim3(p.images), dim3(DB_NT), 0, s, p, c_cur,
+                           c_next, t, *con);
+    else if (nbest)
+        hipLaunchKernelGGL((beam_step_batched_kernel<K, true>), dim3(p.images), dim3(DB_NT), 0, s, p, c_cur, c_next, t, NoRule{});
+    else
+        hipLaunchKernelGGL((beam_step_batched_kernel<K, false>), dim3(p.images), dim3(DB_NT), 0, s, p, c_cur, c_next, t, NoRule{});
 }
 
 // The launches of both step-batched beam entries, arguments already checked: init, per step the GEMM launches of
 // decode_batched.inc.h on the images * beam rows and the step kernel, then the final kernel.  `nb` (the outputs of the
-// n-best entry; bp then carries N, norm and list) selects the n-best kernels (beam_nbest.inc.h).
+// n-best entry; bp then carries N, norm and list) selects the n-best kernels (beam_nbest.inc.h), `con` (with nb: the class
+// bytes and the slots' bracket states) the well-formed search (beam_constrained.inc.h).
 int beam_batched_enqueue(const i2l_decoder_weights* w, const void* workspace, const Layout& lo, const BeamBatchedLayout& bl,
                          int images, int beam, int steps, int start_id, int end_id, char* sb, BeamBatchedParams bp,
-                         const BeamNbestOut* nb, hipStream_t s) {
+                         const BeamNbestOut* nb, const ConstrainRule* con, hipStream_t s) {
     const int V = w->vocab, H = w->hidden, L = w->layers;
     const int R = images * beam;
     const size_t LRH = (size_t)L * R * H;
@@ -1476,6 +1503,10 @@ int beam_batched_enqueue(const i2l_decoder_weights* w, const void* workspace, co
         hipLaunchKernelGGL(beam_nbest_init_kernel, dim3(i2l_cdiv(images, DB_NT)), dim3(DB_NT), 0, s, bp);
         I2L_CHECK_LAUNCH();
     }
+    if (con) {
+        hipLaunchKernelGGL(beam_constrained_init_kernel, dim3(i2l_cdiv(R, DB_NT)), dim3(DB_NT), 0, s, con->state, (size_t)R);
+        I2L_CHECK_LAUNCH();
+    }
     const int tb_lstm = batched_tile_rows(H / 16, R), tb_logits = batched_tile_rows(lo.Vp / DB_COLS, R);
     for (int t = 0; t < steps; ++t) {
         float* c_cur = bp.c + (size_t)(t & 1) * LRH;
@@ -1483,7 +1514,7 @@ int beam_batched_enqueue(const i2l_decoder_weights* w, const void* workspace, co
         p.c = c_cur;
         launch_batched_step(p, tb_lstm, tb_logits, 0, s);
         with_width<1, 2, 3, 4, 5, 6, 7, 8>(beam, [&](auto k) {
-            launch_beam_step_batched<k>(bp, nb != nullptr, c_cur, c_next, t, s);
+            launch_beam_step_batched<k>(bp, nb != nullptr, con, c_cur, c_next, t, s);
         });
         I2L_CHECK_LAUNCH();
     }
@@ -1515,7 +1546,7 @@ extern "C" int i2l_beam_decode_batched(const i2l_decoder_weights* w, const void*
     BeamBatchedParams bp{};
     bp.seq_out = seq_out; bp.len_out = len_out; bp.score_out = score_out;
     return beam_batched_enqueue(w, workspace, lo, bl, images, beam, steps, start_id, end_id, static_cast<char*>(scratch), bp,
-                                nullptr, i2l_s(stream));
+                                nullptr, nullptr, i2l_s(stream));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1553,7 +1584,49 @@ extern "C" int i2l_beam_decode_nbest(const i2l_decoder_weights* w, const void* w
     BeamNbestOut nb{};
     nb.seq_out = seq_out; nb.len_out = len_out; nb.score_out = score_out; nb.key_out = key_out;
     nb.finished_out = finished_out; nb.count_out = count_out;
-    return beam_batched_enqueue(w, workspace, lo, nl.b, images, beam, steps, start_id, end_id, sb, bp, &nb, i2l_s(stream));
+    return beam_batched_enqueue(w, workspace, lo, nl.b, images, beam, steps, start_id, end_id, sb, bp, &nb, nullptr,
+                                i2l_s(stream));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Well-formed N-best beam search (beam_bracket_rules.inc.h, beam_constrained.inc.h): the search above in which a slot
+// extends only by columns its bracket state allows, so every returned row nests and ends on END.
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t i2l_beam_nbest_constrained_scratch_bytes(int images, int beam, int nbest, int vocab, int hidden, int layers,
+                                                           int steps) {
+    if (!beam_nbest_dims_ok(images, beam, nbest, vocab, hidden, layers, steps)) return 0;
+    return beam_constrained_layout(images, beam, nbest, i2l_cdiv(vocab, VCHUNK) * VCHUNK, hidden, layers, steps).total;
+}
+
+extern "C" int i2l_beam_decode_nbest_constrained(const i2l_decoder_weights* w, const void* workspace, int images, int beam,
+                                                 int nbest, int steps, int start_id, int end_id, const double* length_norm,
+                                                 void* scratch, size_t scratch_bytes, int32_t* seq_out, int32_t* len_out,
+                                                 double* score_out, double* key_out, int32_t* finished_out,
+                                                 int32_t* count_out, int flags, const uint8_t* cls, i2l_stream_t stream) {
+    (void)flags;
+    // every refusal is decided here, before the first HIP call
+    int rc = check_weights(w);
+    if (rc != I2L_OK) return rc;
+    if (!workspace || !scratch || !seq_out || !len_out || !score_out || !count_out || !cls || images <= 0 || steps <= 0 ||
+        beam <= 0 || nbest <= 0)
+        return I2L_ERR_ARG;
+    const int V = w->vocab, E = w->embed, H = w->hidden, L = w->layers;
+    if (end_id < 0 || end_id >= V) return I2L_ERR_ARG;
+    if (!beam_nbest_dims_ok(images, beam, nbest, V, H, L, steps)) return I2L_ERR_UNSUPPORTED;
+    const Layout lo = make_layout(images, V, E, H, L);
+    const BeamConstrainedLayout cl = beam_constrained_layout(images, beam, nbest, lo.Vp, H, L, steps);
+    if (scratch_bytes < cl.total) return I2L_ERR_WORKSPACE;
+
+    char* sb = static_cast<char*>(scratch);
+    BeamBatchedParams bp{};
+    bp.N = nbest; bp.norm = length_norm;
+    bp.list = reinterpret_cast<NbestEntry*>(sb + cl.n.list);
+    BeamNbestOut nb{};
+    nb.seq_out = seq_out; nb.len_out = len_out; nb.score_out = score_out; nb.key_out = key_out;
+    nb.finished_out = finished_out; nb.count_out = count_out;
+    const ConstrainRule con{cls, reinterpret_cast<BracketState*>(sb + cl.state), nullptr};
+    return beam_batched_enqueue(w, workspace, lo, cl.n.b, images, beam, steps, start_id, end_id, sb, bp, &nb, &con,
+                                i2l_s(stream));
 }
 
 extern "C" size_t i2l_decoder_group_status_offset(int rows, int vocab, int embed, int hidden, int layers) {

@@ -138,6 +138,10 @@ _SIGNATURES = {
     "i2l_beam_decode_nbest": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p]),
+    "i2l_beam_nbest_constrained_scratch_bytes": (c_size_t, [c_int] * 7),
+    "i2l_beam_decode_nbest_constrained": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                  c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "i2l_attention_context_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                           c_int, c_int, c_void_p]),
     "i2l_decoder_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

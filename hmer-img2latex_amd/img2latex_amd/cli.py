@@ -3,6 +3,7 @@
 
     python -m img2latex_amd predict CHECKPOINT IMAGE [--beam-size N] [--max-length N] [--temperature T]
                                                      [--nbest N --length-penalty A]  (this package: N-best beam search)
+                                                     [--well-formed]  (this package: greedy, sampling or --nbest)
                                                      [--top-k K] [--top-p P] [--device cuda]
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
                                   [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
@@ -102,12 +103,13 @@ def predict(checkpoint_path: str, image_path: str, beam_size: int = 0, max_lengt
 
 
 def predict_nbest(checkpoint_path: str, image_path: str, beam_size: int, nbest: int, max_length: int = 141,
-                  length_penalty: float = 0.0, device: Optional[str] = None):
-    """(this package) the ``nbest`` best beam-search hypotheses of the image as (latex, score, key), in rank order."""
+                  length_penalty: float = 0.0, device: Optional[str] = None, well_formed: bool = False):
+    """(this package) the ``nbest`` best beam-search hypotheses of the image as (latex, score, key), in rank order.
+    ``well_formed``: the bracket-constrained search, every hypothesis nesting its groups and ending on END."""
     from .training import Predictor
     predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device))
     return predictor.predict_nbest(image=image_path, beam_size=beam_size, nbest=nbest, max_length=max_length,
-                                   length_penalty=length_penalty)
+                                   length_penalty=length_penalty, well_formed=bool(well_formed))
 
 
 def vocab(formulas_file: str, out_path: str, max_sequence_length: int = 150, device: Optional[str] = None):
@@ -408,7 +410,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                    help="(this package) decode kernel, greedy and --top-k / --top-p sampling: auto, or the step-batched matrix-core decode")
     p.add_argument("--well-formed", action="store_true",
                    help="(this package) bracket-constrained decode: { }, \\left \\right and \\begin \\end nest and the formula "
-                        "ends within the maximum length (nesting only: no arity, no semantics)")
+                        "ends within the maximum length (nesting only: no arity, no semantics); greedy, sampling, or beam "
+                        "search with --nbest N (--nbest 1: the single best well-formed formula)")
     p.add_argument("--nbest", type=int, default=0,
                    help="(this package) with --beam-size K > 0: print the N best hypotheses, one key<TAB>latex line each, "
                         "in rank order (0: the single result as before)")
@@ -463,13 +466,15 @@ def main(argv: Optional[List[str]] = None) -> int:
     args = ap.parse_args(argv)
     if args.command == "predict" and args.nbest < 0:
         ap.error("--nbest must be >= 0")
-    if args.command == "predict" and args.well_formed and (args.nbest > 0 or args.beam_size > 0):
-        ap.error("--well-formed covers the greedy and sampling decode, not beam search")
+    if args.command == "predict" and args.well_formed and args.beam_size > 0 and args.nbest == 0:
+        ap.error("--well-formed with --beam-size needs --nbest: add --nbest 1 for the single best well-formed formula "
+                 "(plain --beam-size runs the grouped beam kernels, which carry no constraint)")
     if args.command == "predict" and args.nbest > 0:
         if args.beam_size <= 0:
             ap.error("--nbest needs --beam-size above 0")
         for latex, _, key in predict_nbest(args.checkpoint_path, args.image_path, args.beam_size, args.nbest,
-                                           args.max_length, args.length_penalty, args.device):
+                                           args.max_length, args.length_penalty, args.device,
+                                           well_formed=args.well_formed):
             print(f"{key!r}\t{latex}")
         return 0
     if args.command == "predict":

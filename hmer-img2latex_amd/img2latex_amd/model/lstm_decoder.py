@@ -272,15 +272,21 @@ class LSTMDecoder(nn.Module):
         del keep
         return ids, logits, ((h, c) if want_state else None)
 
-    def _constraint_buffers(self, constraint, rows: int, end_id: int, dev):
-        """(class bytes on ``dev``, the rows' 16 state bytes, the step-batched scratch, its size) of one constrained call."""
+    def _constraint_table(self, constraint, end_id: int, dev):
+        """The class bytes of ``constraint`` on ``dev``, checked against this decoder: as wide as the vocabulary, the end
+        id inside the table and neutral there."""
         if constraint.vocab != self.vocab_size:
             raise RuntimeError(f"img2latex_amd: the constraint's table has {constraint.vocab} columns, the decoder's "
                                f"vocabulary {self.vocab_size}")
-        constraint._end(end_id)                            # inside the table, and neutral there
+        constraint._end(end_id)
+        return constraint.device(dev)
+
+    def _constraint_buffers(self, constraint, rows: int, end_id: int, dev):
+        """(class bytes on ``dev``, the rows' 16 state bytes, the step-batched scratch, its size) of one constrained call."""
+        cls = self._constraint_table(constraint, end_id, dev)
         scratch, nbytes = self._batched_scratch(rows, dev)
         state = torch.empty(_lib.lib().i2l_bracket_state_bytes(rows), dtype=torch.uint8, device=dev)   # zeroed by the call
-        return constraint.device(dev), state, scratch, nbytes
+        return cls, state, scratch, nbytes
 
     def halves_supported(self, stop: int = _lib.STOP_NONE) -> bool:
         """True where ``decode_halves`` has a kernel: the 16-member grouped decode's dimensions, no sticky stop."""

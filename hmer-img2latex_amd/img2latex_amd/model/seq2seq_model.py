@@ -102,7 +102,9 @@ class Seq2SeqModel(nn.Module):
             encoder_output = encoder_output.unsqueeze(0)
         if beam_size > 0:
             if constraint is not None:
-                raise RuntimeError("img2latex_amd: beam search has no bracket-constrained form; use beam_size=0")
+                raise RuntimeError("img2latex_amd: inference(beam_size > 0) runs the grouped beam kernels, which carry no "
+                                   "bracket constraint; use beam_search_nbest(..., constraint=table), nbest=1 for the "
+                                   "single best, or beam_size=0")
             return self._beam_search(encoder_output, start_token_id, end_token_id, max_length, beam_size)
         return self._greedy_search(encoder_output, start_token_id, end_token_id, max_length, temperature, top_k, top_p,
                                    constraint=constraint)
@@ -238,20 +240,28 @@ class Seq2SeqModel(nn.Module):
 
     def beam_search_nbest(self, encoder_output: torch.Tensor, start_token_id: int, end_token_id: int, max_length: int,
                           beam_size: int, nbest: Optional[int] = None, length_penalty: float = 0.0,
-                          length_norm: Optional[Sequence[float]] = None) -> List[List[BeamHypothesis]]:
+                          length_norm: Optional[Sequence[float]] = None, constraint=None) -> List[List[BeamHypothesis]]:
         """Per image the ``nbest`` (default ``beam_size``) best hypotheses of the beam search above, ranked by
         ``score / norm[n]``, n = tokens after START with END (``length_norm_table``): the completed beams in rank order,
         then, when the search ran out of steps, its final beams.  With ``nbest = 1`` and no normalisation, row 0 is
         ``beam_search_batch``'s result under _lib.FLAG_BEAM_BATCHED.  Always the step-batched search
-        (i2l_beam_decode_nbest); dimensions it refuses raise RuntimeError."""
+        (i2l_beam_decode_nbest); dimensions it refuses raise RuntimeError.
+
+        ``constraint``: a BracketTable (training/constraint.py) selects the well-formed search
+        (i2l_beam_decode_nbest_constrained): a beam extends only by tokens its bracket state allows, with the log-probs
+        renormalised over them, so every hypothesis nests its groups, ends on END (``finished`` is always True) and its
+        score is its log-probability under the constrained model.  ``nbest=1`` gives the single best one."""
         nbest = int(beam_size if nbest is None else nbest)
         table = length_norm_table(int(max_length), float(length_penalty), length_norm)
         dec = self.decoder
         w, keep, enc = dec.prepare(encoder_output)
         n, dev = enc.shape[0], enc.device
         L = _lib.lib()
-        nbytes = L.i2l_beam_nbest_scratch_bytes(n, int(beam_size), nbest, dec.vocab_size, dec.hidden_dim, dec.lstm_layers,
-                                                int(max_length))
+        cls = None
+        if constraint is not None:
+            cls = dec._constraint_table(constraint, int(end_token_id), dev)
+        size_query = L.i2l_beam_nbest_scratch_bytes if cls is None else L.i2l_beam_nbest_constrained_scratch_bytes
+        nbytes = size_query(n, int(beam_size), nbest, dec.vocab_size, dec.hidden_dim, dec.lstm_layers, int(max_length))
         if nbytes == 0:
             raise RuntimeError(f"img2latex_amd: dimensions not supported by the n-best beam search (beam_size <= "
                                f"{_lib.MAX_BEAM}, nbest <= {_lib.MAX_NBEST}, vocabulary <= 2048)")
@@ -263,12 +273,16 @@ class Seq2SeqModel(nn.Module):
         key = torch.empty((n, nbest), dtype=torch.float64, device=dev)
         fin = torch.empty((n, nbest), dtype=torch.int32, device=dev)
         count = torch.empty((n,), dtype=torch.int32, device=dev)
-        _lib.check(L.i2l_beam_decode_nbest(ctypes.byref(w), dec._ws.data_ptr(), n, int(beam_size), nbest, int(max_length),
-                                           int(start_token_id), int(end_token_id), _lib.ptr(norm), scratch.data_ptr(),
-                                           nbytes, seq.data_ptr(), ln.data_ptr(), score.data_ptr(), key.data_ptr(),
-                                           fin.data_ptr(), count.data_ptr(), 0, _lib.stream_ptr()), "beam_decode_nbest")
+        args = (ctypes.byref(w), dec._ws.data_ptr(), n, int(beam_size), nbest, int(max_length), int(start_token_id),
+                int(end_token_id), _lib.ptr(norm), scratch.data_ptr(), nbytes, seq.data_ptr(), ln.data_ptr(), score.data_ptr(),
+                key.data_ptr(), fin.data_ptr(), count.data_ptr(), 0)
+        if cls is None:
+            _lib.check(L.i2l_beam_decode_nbest(*args, _lib.stream_ptr()), "beam_decode_nbest")
+        else:
+            _lib.check(L.i2l_beam_decode_nbest_constrained(*args, cls.data_ptr(), _lib.stream_ptr()),
+                       "beam_decode_nbest_constrained")
         seq_h, ln_h, sc_h = seq.cpu().tolist(), ln.cpu().tolist(), score.cpu().tolist()
         key_h, fin_h, cnt_h = key.cpu().tolist(), fin.cpu().tolist(), count.cpu().tolist()
-        del keep, scratch, norm
+        del keep, scratch, norm, cls
         return [[BeamHypothesis(seq_h[j][r][:ln_h[j][r]], sc_h[j][r], key_h[j][r], bool(fin_h[j][r]))
                  for r in range(cnt_h[j])] for j in range(n)]

@@ -1,10 +1,11 @@
-"""Well-formed LaTeX out of the decoder: the bracket constraint of the step-batched greedy and sampling decode.
+"""Well-formed LaTeX out of the decoder: the bracket constraint of the step-batched greedy and sampling decode and of
+the N-best beam search.
 
 ``BracketTable`` holds one class byte per vocabulary column (csrc/bracket_rules.inc.h): 0 neutral, 1..4 opens a group of
 kind 0..3, 5..8 closes one, 255 never emitted.  ``from_tokenizer`` classifies token strings -- ``{ }`` kind 0,
 ``\\left… \\right…`` kind 1, ``\\begin{…} \\end{…}`` kind 2 -- ``device`` uploads the bytes once per device, and
-``allowed`` / ``advance`` / ``replay`` / ``well_formed`` restate the rules on the host, which is what the tests hold the
-kernels and the stand-alone host program to.
+``allowed`` / ``advance`` / ``candidates`` / ``replay`` / ``well_formed`` restate the rules on the host, which is what the
+tests hold the kernels and the stand-alone host programs to.
 
 What a constrained decode guarantees: every row emits END within ``steps`` steps, at depth 0, and every group it opened
 is closed, innermost first, by a closer of its own kind.  What it does not: arity (``\\frac`` still needs its two
@@ -198,6 +199,27 @@ class BracketTable:
             return int(np.argmax(x))
         on = np.flatnonzero(mask)
         return int(on[0]) if on.size else int(end_id)
+
+    def candidates(self, state: BracketState, row, end_id: int, rem: int, beam: int, logits: bool = False):
+        """The slot policy of the well-formed beam search (csrc/beam_bracket_rules.inc.h): the candidates of a live slot
+        in ``state`` at ``rem`` emissions left after this one, as ``[(column, log-prob)]`` -- its top ``min(beam,
+        #allowed)`` allowed columns of ``row``, descending, the lower index first on ties; the list stops at the first
+        column without a value above -inf, and an empty list becomes ``[(end_id, 0.0)]`` (defined, not well formed).
+        ``logits=True``: ``row`` holds logits and the log-probs are its log-softmax over the allowed columns only, in the
+        row's dtype (the device's phase (c)); otherwise ``row`` holds log-probs that are taken as they are."""
+        x = np.asarray(row)
+        x = x if x.dtype in (np.float32, np.float64) else x.astype(np.float64)
+        mask = self.allowed(state, end_id, rem).astype(bool)
+        sel = np.where(mask & ~np.isnan(x), x, -np.inf)                # the kernel's `x > best` is false for a NaN
+        lp = sel
+        if logits:
+            masked = np.where(mask, x, -np.inf).astype(x.dtype)
+            m = masked.max() if mask.any() else -np.inf
+            with np.errstate(invalid="ignore"):
+                lp = (masked - m) - np.log(np.exp(masked - m).sum(dtype=x.dtype))
+        order = np.argsort(-sel, kind="stable")[:int(beam)]
+        out = [(int(v), float(lp[v])) for v in order if sel[v] > -np.inf]
+        return out if out else [(int(end_id), 0.0)]
 
     def replay(self, logits_per_step, end_id: Optional[int] = None, steps: Optional[int] = None,
                state: Optional[BracketState] = None, first_step: int = 0) -> List[dict]:

@@ -245,8 +245,8 @@ class Predictor:
         # decode_flags (_lib.FLAG_DECODE_BATCHED: the step-batched matrix-core decode) are OR-ed into the flags of every
         # greedy and every sampling decode this predictor launches; 0 = the automatic kernel choice
         self.decode_flags = int(decode_flags)
-        # well_formed: every greedy and sampling decode of this predictor is the bracket-constrained one (training/constraint.py:
-        # groups nest, END within max_length) -- True: the table BracketTable.from_tokenizer gives, or a BracketTable of the
+        # well_formed: every greedy and sampling decode and every N-best beam search (predict_nbest, predict_batch_nbest) of
+        # this predictor is the bracket-constrained one (training/constraint.py: groups nest, END within max_length) -- True: the table BracketTable.from_tokenizer gives, or a BracketTable of the
         # caller's; each call's own ``well_formed=`` overrides it.  Off by default: nothing changes without it.
         self.well_formed = well_formed
         self.device = torch.device("cuda") if device is None else torch.device(device)
@@ -743,10 +743,13 @@ class Predictor:
         return self.tokenizer.decode(seq)
 
     def predict_batch_nbest(self, images, beam_size: int = 5, nbest: Optional[int] = None, max_length: int = 141,
-                            length_penalty: float = 0.0, batch_size: int = 16) -> List[List[Tuple[str, float, float]]]:
+                            length_penalty: float = 0.0, batch_size: int = 16,
+                            well_formed=None) -> List[List[Tuple[str, float, float]]]:
         """Per image the (latex, score, key) of its ``nbest`` (default ``beam_size``) best beam-search hypotheses in rank
         order (Seq2SeqModel.beam_search_nbest: key = score / length ** length_penalty), every image through
-        ``_prepare_image`` as in ``predict_batch``, the ids through the tokenizer's own ``decode``."""
+        ``_prepare_image`` as in ``predict_batch``, the ids through the tokenizer's own ``decode``.  ``well_formed``: the
+        well-formed search, every hypothesis nesting its groups and ending on END (None: the predictor's own setting)."""
+        constraint = self._constraint(well_formed)
         if isinstance(images, torch.Tensor):
             images = [images] if images.dim() <= 3 else list(images)
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
@@ -757,11 +760,12 @@ class Predictor:
                 x = x.squeeze(1)
             with torch.no_grad():
                 rows = self.model.beam_search_nbest(self.model.encoder(x.to(self.device)), start, end, max_length,
-                                                    beam_size, nbest=nbest, length_penalty=length_penalty)
+                                                    beam_size, nbest=nbest, length_penalty=length_penalty,
+                                                    constraint=constraint)
             results.extend([(self.tokenizer.decode(h.tokens), h.score, h.key) for h in hyps] for hyps in rows)
         return results
 
     def predict_nbest(self, image, beam_size: int = 5, nbest: Optional[int] = None, max_length: int = 141,
-                      length_penalty: float = 0.0) -> List[Tuple[str, float, float]]:
+                      length_penalty: float = 0.0, well_formed=None) -> List[Tuple[str, float, float]]:
         """``predict_batch_nbest`` for one image (path / PIL / ndarray / tensor)."""
-        return self.predict_batch_nbest([image], beam_size, nbest, max_length, length_penalty)[0]
+        return self.predict_batch_nbest([image], beam_size, nbest, max_length, length_penalty, well_formed=well_formed)[0]

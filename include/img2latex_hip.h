@@ -562,6 +562,30 @@ int i2l_beam_decode_nbest(const i2l_decoder_weights* w, const void* workspace, i
                           int32_t* seq_out, int32_t* len_out, double* score_out, double* key_out, int32_t* finished_out,
                           int32_t* count_out, int flags, i2l_stream_t stream);
 
+/* Well-formed N-best beam search: i2l_beam_decode_nbest in which every hypothesis ever ranked is a prefix the bracket rules
+ * of i2l_greedy_decode_constrained allow, so every returned row nests its groups and ends on END.  A live slot at step t
+ * extends only by the columns its bracket state allows at rem = steps - t - 1; its candidates are the top
+ * min(beam, #allowed) of them, and their log-probs are the log-softmax over the allowed columns only (a forbidden column
+ * enters the softmax as -inf, as in i2l_sample_decode_constrained), so scores are log-probabilities under the constrained
+ * model and a forced closer or END costs 0.  A new beam inherits its parent's state advanced by its token.  At step
+ * steps - 1 the only candidate of every live slot is END: the search never runs out of steps, every filled row has
+ * finished = 1.  If a slot has no allowed column with a logit above -inf (a table in which an open kind has no closer, or
+ * non-finite logits) its single candidate is (end_id, 0.0): defined, but that row is not well formed.
+ *   cls          DEVICE array of `vocab` class bytes, as for i2l_greedy_decode_constrained; end_id's entry is ignored
+ *   scratch      i2l_beam_nbest_constrained_scratch_bytes(...) bytes: that of i2l_beam_decode_nbest plus 16 bytes of
+ *                bracket state per slot, zeroed by the call
+ * Everything else -- outputs, length_norm, ranking, accepted dimensions, refusals -- as i2l_beam_decode_nbest; a NULL cls or
+ * an end_id outside [0, vocab) is I2L_ERR_ARG.  nbest = 1 with a NULL length_norm is the constrained single-best search.
+ * The same launches per step as i2l_beam_decode_nbest; every refusal is decided on the host before the first HIP call.
+ * flags: none used.  The library keeps no state. */
+size_t i2l_beam_nbest_constrained_scratch_bytes(int images, int beam, int nbest, int vocab, int hidden, int layers,
+                                                int steps);
+int i2l_beam_decode_nbest_constrained(const i2l_decoder_weights* w, const void* workspace, int images, int beam, int nbest,
+                                      int steps, int start_id, int end_id, const double* length_norm, void* scratch,
+                                      size_t scratch_bytes, int32_t* seq_out, int32_t* len_out, double* score_out,
+                                      double* key_out, int32_t* finished_out, int32_t* count_out, int flags,
+                                      const uint8_t* cls, i2l_stream_t stream);
+
 /* Additive attention, general source length S (Attention.forward, decoder.py:312-343):
  * context[b] = softmax_s(v . tanh(W [hidden[b] ; enc[b,s]] + b_a)) @ enc[b].
  * hidden (B,H)  enc (B,S,E)  w_attn (H, H+E)  b_attn (H)  v (H)  context (B,E). */
