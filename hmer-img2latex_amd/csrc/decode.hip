@@ -287,6 +287,8 @@ __device__ __forceinline__ int beam_topk_row(const float* x, int V, int K, int l
 #include "sample_batched.inc.h"
 #include "bracket_rules.inc.h"
 #include "decode_constrained.inc.h"
+#include "argument_rules.inc.h"
+#include "decode_arguments.inc.h"
 #include "beam_bracket_rules.inc.h"
 #include "beam_batched.inc.h"
 #include "beam_nbest.inc.h"
@@ -826,9 +828,11 @@ inline int check_sample(float temperature, int top_k, float top_p) {
 }
 inline int check_sample_vocab(int vocab) { return vocab > SB_MAXV ? I2L_ERR_UNSUPPORTED : I2L_OK; }
 // the constraint's own arguments; rows > 0 and vocab > 0 are checked before it
-int check_constraint(int rows, int vocab, int end_id, const uint8_t* cls, const void* state, size_t state_bytes) {
+// (row_bytes: sizeof(BracketState), or sizeof(ArgumentState) under the argument rules)
+int check_constraint(int rows, int vocab, int end_id, const uint8_t* cls, const void* state, size_t state_bytes,
+                     size_t row_bytes = sizeof(BracketState)) {
     if (end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
-    if (state_bytes < (size_t)rows * sizeof(BracketState)) return I2L_ERR_WORKSPACE;
+    if (state_bytes < (size_t)rows * row_bytes) return I2L_ERR_WORKSPACE;
     return I2L_OK;
 }
 
@@ -851,6 +855,7 @@ struct DecodeCall {
     i2l_stream_t stream;
     int rows_per_wg;                   // launch_decode: 0 = its own choice
     ConstrainRule con;                 // launch_batched: con.cls != null asks for the bracket-constrained selection
+    ArgumentRule arg;                  // launch_batched: arg.cls != null asks for the argument-complete one (not with con)
     void* scratch;                     // launch_batched
     size_t scratch_bytes;
 };
@@ -1166,11 +1171,12 @@ void launch_batched_select(const BatchedParams& p, const DecodeCall& a, const Ru
 }
 
 // The loop of the step-batched entries.  The caller has checked the weights and its own arguments; every other refusal
-// is decided here, before the first HIP call.  A constrained call starts from the rows' zeroed bracket state.
+// is decided here, before the first HIP call.  A constrained call starts from the rows' zeroed bracket or argument state.
 int launch_batched(const DecodeCall& a) {
     if (!a.workspace || !a.tok0 || check_loop(a.rows, a.steps)) return I2L_ERR_ARG;
     if ((a.h0 == nullptr) != (a.c0 == nullptr)) return I2L_ERR_ARG;
     if (a.stop != I2L_STOP_NONE && a.stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
+    if (a.con.cls && a.arg.cls) return I2L_ERR_ARG;
     const int rows = a.rows, steps = a.steps;
     const int V = a.w->vocab, E = a.w->embed, H = a.w->hidden, L = a.w->layers;
     const Layout lo = make_layout(rows, V, E, H, L);
@@ -1195,6 +1201,7 @@ int launch_batched(const DecodeCall& a) {
         I2L_CHECK_LAUNCH();
     }
     if (a.con.cls && hipMemsetAsync(a.con.state, 0, (size_t)rows * sizeof(BracketState), s) != hipSuccess) return I2L_ERR_LAUNCH;
+    if (a.arg.cls && hipMemsetAsync(a.arg.state, 0, (size_t)rows * sizeof(ArgumentState), s) != hipSuccess) return I2L_ERR_LAUNCH;
     const size_t most = (size_t)L * rows * H > (size_t)rows * steps ? (size_t)L * rows * H : (size_t)rows * steps;
     const size_t copy_blocks = (most + DB_NT - 1) / DB_NT;
     const int copy_grid = (int)(copy_blocks < 1024 ? copy_blocks : 1024);
@@ -1204,6 +1211,7 @@ int launch_batched(const DecodeCall& a) {
     for (int t = 0; t < steps; ++t) {
         launch_batched_step(p, tb_lstm, tb_logits, t, s);
         if (a.con.cls) launch_batched_select(p, a, a.con, t, s);
+        else if (a.arg.cls) launch_batched_select(p, a, a.arg, t, s);
         else launch_batched_select(p, a, NoRule{}, t, s);
         I2L_CHECK_LAUNCH();
     }
@@ -1339,6 +1347,80 @@ extern "C" int i2l_constrained_pick_logits(const float* logits, int ld, int rows
         const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
         hipLaunchKernelGGL(sample_logits_kernel<ConstrainRule>, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab,
                            temperature, use_temp(temperature), rule, (unsigned)step, con, end_id, rem, ids_out);
+    }
+    I2L_CHECK_LAUNCH();
+    return I2L_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Argument-complete step-batched decode (argument_rules.inc.h, decode_arguments.inc.h): the bracket-constrained entries
+// above under the stronger rule set -- every command gets the arguments it demands -- with the same argument lists and
+// the same refusals, 32 bytes of caller-owned state per row in the place of 16.
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t i2l_argument_state_bytes(int rows) { return rows > 0 ? (size_t)rows * sizeof(ArgumentState) : 0; }
+
+extern "C" int i2l_greedy_decode_arguments(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                           const int32_t* tok0, const float* h0, const float* c0, float temperature,
+                                           int select, int stop, int end_id, int32_t* ids_out, float* logits_out,
+                                           float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
+                                           uint32_t* resident_flag, uint32_t resident_value, const uint8_t* cls,
+                                           void* state, size_t state_bytes, i2l_stream_t stream) {
+    int rc;
+    if ((rc = check_weights(w)) || (rc = check_select(select)) || (rc = check_loop(rows, steps)) ||
+        (rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes, sizeof(ArgumentState))))
+        return rc;
+    DecodeCall a{};
+    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
+    a.tok0 = tok0; a.h0 = h0; a.c0 = c0;
+    a.temperature = temperature; a.select = select; a.stop = stop; a.end_id = end_id;
+    a.ids_out = ids_out; a.logits_out = logits_out; a.h_out = h_out; a.c_out = c_out;
+    a.flags = flags; a.resident_flag = resident_flag; a.resident_value = resident_value; a.stream = stream;
+    a.arg = ArgumentRule{cls, static_cast<ArgumentState*>(state), nullptr};
+    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
+    return launch_batched(a);
+}
+
+extern "C" int i2l_sample_decode_arguments(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                           const int32_t* tok0, const float* h0, const float* c0, float temperature,
+                                           int top_k, float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out,
+                                           float* probs_out, float* h_out, float* c_out, void* scratch,
+                                           size_t scratch_bytes, int flags, const uint8_t* cls, void* state,
+                                           size_t state_bytes, i2l_stream_t stream) {
+    int rc;
+    if ((rc = check_weights(w)) || (rc = check_sample(temperature, top_k, top_p)) || (rc = check_loop(rows, steps)) ||
+        (rc = check_sample_vocab(w->vocab)) ||
+        (rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes, sizeof(ArgumentState))))
+        return rc;
+    DecodeCall a{};
+    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
+    a.tok0 = tok0; a.h0 = h0; a.c0 = c0;
+    a.temperature = temperature; a.select = I2L_SELECT_SAMPLE; a.stop = stop; a.end_id = end_id;
+    a.sample = SampleRule{top_k, top_p, (unsigned long long)seed, probs_out};
+    a.ids_out = ids_out; a.h_out = h_out; a.c_out = c_out; a.flags = flags; a.stream = stream;
+    a.arg = ArgumentRule{cls, static_cast<ArgumentState*>(state), nullptr};
+    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
+    return launch_batched(a);
+}
+
+extern "C" int i2l_arguments_pick_logits(const float* logits, int ld, int rows, int vocab, float temperature, int select,
+                                         int top_k, float top_p, uint64_t seed, int step, int steps, const uint8_t* cls,
+                                         int end_id, void* state, int32_t* ids_out, float* probs_out,
+                                         uint8_t* allowed_out, i2l_stream_t stream) {
+    const bool greedy = top_k == 0 && top_p == 0.f;
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return I2L_ERR_ARG;
+    if (greedy && check_select(select)) return I2L_ERR_ARG;
+    if (rows <= 0 || vocab <= 0 || ld < vocab || step < 0 || steps <= 0 || step >= steps) return I2L_ERR_ARG;
+    if (!greedy && check_sample_vocab(vocab)) return I2L_ERR_UNSUPPORTED;
+    if (!logits || !ids_out || end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
+    const ArgumentRule arg{cls, static_cast<ArgumentState*>(state), allowed_out};
+    const int rem = steps - step - 1;
+    if (greedy) {
+        hipLaunchKernelGGL(pick_arguments_select_kernel, dim3(i2l_cdiv(rows, DB_NT / 64)), dim3(DB_NT), 0, i2l_s(stream),
+                           logits, ld, rows, vocab, temperature, use_temp(temperature), select, arg, end_id, rem, ids_out);
+    } else {
+        const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
+        hipLaunchKernelGGL(sample_logits_kernel<ArgumentRule>, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab,
+                           temperature, use_temp(temperature), rule, (unsigned)step, arg, end_id, rem, ids_out);
     }
     I2L_CHECK_LAUNCH();
     return I2L_OK;

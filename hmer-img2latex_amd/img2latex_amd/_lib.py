@@ -128,6 +128,16 @@ _SIGNATURES = {
                                               c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "i2l_constrained_pick_logits": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_uint64, c_int,
                                             c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "i2l_argument_state_bytes": (c_size_t, [c_int]),
+    "i2l_greedy_decode_arguments": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_size_t, c_int, c_void_p, ctypes.c_uint32, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
+    "i2l_sample_decode_arguments": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_float, c_int, c_float, c_uint64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2l_arguments_pick_logits": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_uint64, c_int,
+                                          c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "i2l_beam_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "i2l_beam_decode": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                 c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

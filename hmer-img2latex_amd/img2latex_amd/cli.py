@@ -4,6 +4,7 @@
     python -m img2latex_amd predict CHECKPOINT IMAGE [--beam-size N] [--max-length N] [--temperature T]
                                                      [--nbest N --length-penalty A]  (this package: N-best beam search)
                                                      [--well-formed]  (this package: greedy, sampling or --nbest)
+                                                     [--complete-arguments]  (this package: greedy or sampling)
                                                      [--top-k K] [--top-p P] [--device cuda]
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
                                   [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
@@ -89,15 +90,22 @@ def _train_flags(train_kernel: str) -> int:
     return _lib.FLAG_TRAIN_BATCHED if train_kernel == "batched" else 0
 
 
+def _well_formed(well_formed):
+    """False / True (the bracket constraint) / "arguments" (the argument rules on top) or a table, as Predictor takes it."""
+    return well_formed if isinstance(well_formed, str) or hasattr(well_formed, "vocab") else bool(well_formed)
+
+
 def predict(checkpoint_path: str, image_path: str, beam_size: int = 0, max_length: int = 141, temperature: float = 1.0,
             top_k: int = 0, top_p: float = 0.0, device: Optional[str] = None, decode_kernel: str = "auto",
             well_formed: bool = False) -> str:
     """cli.py:253-308: returns the LaTeX string the command prints.  ``decode_kernel``: see ``_decode_flags``.
     ``well_formed``: the bracket-constrained decode (training/constraint.py): braces, \\left / \\right and \\begin / \\end
-    nest and the formula ends within ``max_length`` tokens."""
+    nest and the formula ends within ``max_length`` tokens; ``"arguments"``: every command also gets the arguments it
+    demands (``\\frac`` its two groups, ``^`` its operand)."""
     from .training import Predictor
     predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device),
-                                          decode_flags=_decode_flags(decode_kernel), well_formed=bool(well_formed))
+                                          decode_flags=_decode_flags(decode_kernel),
+                                          well_formed=_well_formed(well_formed))
     return predictor.predict(image=image_path, beam_size=beam_size, max_length=max_length, temperature=temperature,
                              top_k=top_k, top_p=top_p)
 
@@ -109,7 +117,7 @@ def predict_nbest(checkpoint_path: str, image_path: str, beam_size: int, nbest: 
     from .training import Predictor
     predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device))
     return predictor.predict_nbest(image=image_path, beam_size=beam_size, nbest=nbest, max_length=max_length,
-                                   length_penalty=length_penalty, well_formed=bool(well_formed))
+                                   length_penalty=length_penalty, well_formed=_well_formed(well_formed))
 
 
 def vocab(formulas_file: str, out_path: str, max_sequence_length: int = 150, device: Optional[str] = None):
@@ -329,7 +337,8 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
     experiment_name = Path(checkpoint_path).parent.parent.name              # cli.py:340-349: outputs/<experiment>/checkpoints/<file>
     config = torch.load(checkpoint_path, map_location="cpu", weights_only=False).get("config", {}) or {}
     predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=dev,
-                                          decode_flags=_decode_flags(decode_kernel), well_formed=bool(well_formed))
+                                          decode_flags=_decode_flags(decode_kernel),
+                                          well_formed=_well_formed(well_formed))
     max_samples = {"train": None, "val": None, "test": None}
     if num_samples:
         max_samples[split] = num_samples
@@ -412,6 +421,9 @@ def main(argv: Optional[List[str]] = None) -> int:
                    help="(this package) bracket-constrained decode: { }, \\left \\right and \\begin \\end nest and the formula "
                         "ends within the maximum length (nesting only: no arity, no semantics); greedy, sampling, or beam "
                         "search with --nbest N (--nbest 1: the single best well-formed formula)")
+    p.add_argument("--complete-arguments", action="store_true",
+                   help="(this package) implies --well-formed, and every command gets the arguments it demands: \\frac its "
+                        "two groups, ^ and _ an operand (greedy and sampling only: refused with --beam-size)")
     p.add_argument("--nbest", type=int, default=0,
                    help="(this package) with --beam-size K > 0: print the N best hypotheses, one key<TAB>latex line each, "
                         "in rank order (0: the single result as before)")
@@ -458,6 +470,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     e.add_argument("--well-formed", action="store_true",
                    help="(this package) bracket-constrained decode: { }, \\left \\right and \\begin \\end nest and the formula "
                         "ends within the maximum length (nesting only: no arity, no semantics)")
+    e.add_argument("--complete-arguments", action="store_true",
+                   help="(this package) implies --well-formed, and every command gets the arguments it demands: \\frac its "
+                        "two groups, ^ and _ an operand")
     v = sub.add_parser("vocab", help="(this package) Fit the vocabulary of a formulas file on the device and save it.")
     v.add_argument("formulas_file", help="Path to the formulas file, one formula per line")
     v.add_argument("out_path", help="Path to save the vocabulary to (LaTeXTokenizer.save's layout)")
@@ -466,6 +481,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     args = ap.parse_args(argv)
     if args.command == "predict" and args.nbest < 0:
         ap.error("--nbest must be >= 0")
+    if args.command == "predict" and args.complete_arguments and args.beam_size > 0:
+        ap.error("--complete-arguments with --beam-size: the argument rules exist for the greedy and sampling decode only "
+                 "(--well-formed --nbest N is the constrained beam search)")
+    if args.command in ("predict", "evaluate") and args.complete_arguments:
+        args.well_formed = "arguments"
     if args.command == "predict" and args.well_formed and args.beam_size > 0 and args.nbest == 0:
         ap.error("--well-formed with --beam-size needs --nbest: add --nbest 1 for the single best well-formed formula "
                  "(plain --beam-size runs the grouped beam kernels, which carry no constraint)")

@@ -19,6 +19,17 @@ from .. import _lib
 Hidden = Tuple[torch.Tensor, torch.Tensor]
 
 
+def _is_argument_table(constraint) -> bool:
+    from ..training.constraint import ArgumentTable
+    return isinstance(constraint, ArgumentTable)
+
+
+def _state_bytes(constraint, rows: int) -> int:
+    """The rows' state of a constrained call: 16 bytes each under a BracketTable, 32 under an ArgumentTable."""
+    L = _lib.lib()
+    return (L.i2l_argument_state_bytes if _is_argument_table(constraint) else L.i2l_bracket_state_bytes)(rows)
+
+
 class Attention(nn.Module):
     """Additive attention (decoder.py:287-343).  General source length via the HIP
     kernel; inside LSTMDecoder the source length is 1 and the context equals the
@@ -221,7 +232,9 @@ class LSTMDecoder(nn.Module):
         """prepare + one persistent i2l_greedy_decode launch.  Returns (ids, logits, (h, c)).
         ``constraint`` = a ``training.constraint.BracketTable``: the bracket-constrained step-batched decode
         (i2l_greedy_decode_constrained) whatever the flags say -- a grouped-shape decoder is routed to the step-batched
-        kernels too; every row nests its groups and ends on END within ``steps``.  Not with ``forced``.
+        kernels too; every row nests its groups and ends on END within ``steps``.  Not with ``forced``.  An
+        ``ArgumentTable``: the same under the argument rules (i2l_greedy_decode_arguments) -- every command also gets
+        the arguments it demands.
         ``prepared`` = (w, keep, enc, workspace) of an earlier ``prepare(encoder_output, slot=...)`` whose completion the
         current stream already waits for: the launch uses that workspace and prepares nothing.
         ``resident`` = (int32 device tensor, value): the launch stores ``value`` there once its workgroups own their compute
@@ -246,11 +259,12 @@ class LSTMDecoder(nn.Module):
             if forced is not None:
                 raise RuntimeError("img2latex_amd: a constrained decode takes no forced tokens")
             cls, state, scratch, nbytes = self._constraint_buffers(constraint, rows, end_id, dev)
-            _lib.check(_lib.lib().i2l_greedy_decode_constrained(
+            entry = "greedy_decode_arguments" if _is_argument_table(constraint) else "greedy_decode_constrained"
+            _lib.check(getattr(_lib.lib(), "i2l_" + entry)(
                 ctypes.byref(w), ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
                 float(temperature), select, stop, int(end_id), _lib.ptr(ids), _lib.ptr(logits), _lib.ptr(h), _lib.ptr(c),
                 scratch.data_ptr(), nbytes, all_flags, res_ptr, res_val, cls.data_ptr(), state.data_ptr(), state.numel(),
-                _lib.stream_ptr()), "greedy_decode_constrained")
+                _lib.stream_ptr()), entry)
             _lib.mark("decode")
             del keep, scratch, state
             return ids, logits, ((h, c) if want_state else None)
@@ -282,10 +296,11 @@ class LSTMDecoder(nn.Module):
         return constraint.device(dev)
 
     def _constraint_buffers(self, constraint, rows: int, end_id: int, dev):
-        """(class bytes on ``dev``, the rows' 16 state bytes, the step-batched scratch, its size) of one constrained call."""
+        """(table bytes on ``dev``, the rows' 16 state bytes -- 32 under an ArgumentTable -- the step-batched scratch, its
+        size) of one constrained call."""
         cls = self._constraint_table(constraint, end_id, dev)
         scratch, nbytes = self._batched_scratch(rows, dev)
-        state = torch.empty(_lib.lib().i2l_bracket_state_bytes(rows), dtype=torch.uint8, device=dev)   # zeroed by the call
+        state = torch.empty(_state_bytes(constraint, rows), dtype=torch.uint8, device=dev)   # zeroed by the call
         return cls, state, scratch, nbytes
 
     def halves_supported(self, stop: int = _lib.STOP_NONE) -> bool:
@@ -332,7 +347,8 @@ class LSTMDecoder(nn.Module):
         """prepare + one i2l_sample_decode launch (predictor.py:295-331), or with ``(flags | self.kernel_flags) &
         FLAG_DECODE_BATCHED`` the step-batched i2l_sample_decode_batched.  Returns (ids, probs or None), with
         ``want_state`` (ids, probs or None, (h, c)).  ``constraint`` = a BracketTable: the bracket-constrained
-        i2l_sample_decode_constrained, whatever the flags say (see ``run_steps``)."""
+        i2l_sample_decode_constrained, an ArgumentTable: i2l_sample_decode_arguments, whatever the flags say (see
+        ``run_steps``)."""
         h0, c0 = self._hidden(hidden, encoder_output.shape[0])     # refused before anything is launched
         w, keep, enc = self.prepare(encoder_output)
         rows, dev = enc.shape[0], enc.device
@@ -342,11 +358,12 @@ class LSTMDecoder(nn.Module):
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         if constraint is not None:
             cls, state, scratch, nbytes = self._constraint_buffers(constraint, rows, end_id, dev)
-            _lib.check(_lib.lib().i2l_sample_decode_constrained(
+            entry = "sample_decode_arguments" if _is_argument_table(constraint) else "sample_decode_constrained"
+            _lib.check(getattr(_lib.lib(), "i2l_" + entry)(
                 ctypes.byref(w), self._ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
                 float(temperature), int(top_k), float(top_p), seed, stop, int(end_id),
                 ids.data_ptr(), _lib.ptr(probs), _lib.ptr(h), _lib.ptr(c), scratch.data_ptr(), nbytes, all_flags,
-                cls.data_ptr(), state.data_ptr(), state.numel(), _lib.stream_ptr()), "sample_decode_constrained")
+                cls.data_ptr(), state.data_ptr(), state.numel(), _lib.stream_ptr()), entry)
             del scratch, state
         elif all_flags & _lib.FLAG_DECODE_BATCHED:
             scratch, nbytes = self._batched_scratch(rows, dev)      # step-batched matrix-core path
@@ -388,23 +405,45 @@ class LSTMDecoder(nn.Module):
         return ids, probs
 
     @staticmethod
+    def arguments_pick_logits(logits: torch.Tensor, constraint, end_id: int, state: torch.Tensor, step: int, steps: int,
+                              *args, **kwargs):
+        """``constrained_pick_logits`` under the argument rules (i2l_arguments_pick_logits): ``constraint`` is an
+        ArgumentTable and ``state`` the rows' (rows * 32) uint8 device tensor."""
+        if not _is_argument_table(constraint):
+            raise TypeError("img2latex_amd: arguments_pick_logits needs an ArgumentTable")
+        return LSTMDecoder._pick_logits("arguments_pick_logits", logits, constraint, end_id, state, step, steps, *args,
+                                        **kwargs)
+
+    @staticmethod
     def constrained_pick_logits(logits: torch.Tensor, constraint, end_id: int, state: torch.Tensor, step: int, steps: int,
-                                temperature: float = 1.0, select: int = _lib.SELECT_LOGITS, top_k: int = 0,
-                                top_p: float = 0.0, seed: int = 0, want_probs: bool = False, want_allowed: bool = False):
+                                *args, **kwargs):
         """Step ``step`` of ``steps`` of the bracket-constrained selection applied once to (rows, V) fp32 logits on the
-        device (i2l_constrained_pick_logits; a row may be a strided view with unit column stride): the arg max under
+        device (i2l_constrained_pick_logits); the keywords and the result are ``_pick_logits``'s."""
+        if _is_argument_table(constraint):
+            raise TypeError("img2latex_amd: constrained_pick_logits needs a BracketTable; arguments_pick_logits takes an "
+                            "ArgumentTable")
+        return LSTMDecoder._pick_logits("constrained_pick_logits", logits, constraint, end_id, state, step, steps, *args,
+                                        **kwargs)
+
+    @staticmethod
+    def _pick_logits(entry: str, logits: torch.Tensor, constraint, end_id: int, state: torch.Tensor, step: int, steps: int,
+                     temperature: float = 1.0, select: int = _lib.SELECT_LOGITS, top_k: int = 0,
+                     top_p: float = 0.0, seed: int = 0, want_probs: bool = False, want_allowed: bool = False):
+        """Step ``step`` of ``steps`` of the constrained selection ``entry`` applied once to (rows, V) fp32 logits on the
+        device (a row may be a strided view with unit column stride): the arg max under
         ``select`` when ``top_k == 0 and top_p == 0``, else a draw as ``sample_logits``.  ``state`` is the rows' (rows * 16)
-        uint8 device tensor, zeroed by the caller before step 0; the call advances it.  Returns (ids (rows) int32, probs
-        (rows, V) or None, allowed (rows, V) uint8 or None)."""
+        uint8 device tensor (rows * 32 under the argument rules), zeroed by the caller before step 0; the call advances
+        it.  Returns (ids (rows) int32, probs (rows, V) or None, allowed (rows, V) uint8 or None)."""
         if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or not logits.is_cuda or logits.dtype != torch.float32:
-            raise RuntimeError("img2latex_amd: constrained_pick_logits needs a (rows, V) fp32 tensor on the ROCm device")
+            raise RuntimeError(f"img2latex_amd: {entry} needs a (rows, V) fp32 tensor on the ROCm device")
         rows, V = logits.shape
         if constraint.vocab != V:
             raise RuntimeError(f"img2latex_amd: the constraint's table has {constraint.vocab} columns, the logits {V}")
         constraint._end(end_id)
         if state.dtype != torch.uint8 or state.device != logits.device or not state.is_contiguous() \
-                or state.numel() < _lib.lib().i2l_bracket_state_bytes(rows):
-            raise RuntimeError(f"img2latex_amd: state must be a contiguous uint8 device tensor of {16 * rows} bytes")
+                or state.numel() < _state_bytes(constraint, rows):
+            raise RuntimeError(f"img2latex_amd: state must be a contiguous uint8 device tensor of "
+                               f"{_state_bytes(constraint, rows)} bytes")
         if logits.stride(1) != 1 or (rows > 1 and logits.stride(0) < V):
             logits = logits.contiguous()
         ld = max(V, logits.stride(0))
@@ -412,11 +451,10 @@ class LSTMDecoder(nn.Module):
         ids = torch.empty((rows,), dtype=torch.int32, device=logits.device)
         probs = torch.empty((rows, V), dtype=torch.float32, device=logits.device) if want_probs and sampling else None
         allowed = torch.empty((rows, V), dtype=torch.uint8, device=logits.device) if want_allowed else None
-        _lib.check(_lib.lib().i2l_constrained_pick_logits(
+        _lib.check(getattr(_lib.lib(), "i2l_" + entry)(
             logits.data_ptr(), int(ld), rows, V, float(temperature), int(select), int(top_k), float(top_p),
             int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(steps), constraint.device(logits.device).data_ptr(), int(end_id),
-            state.data_ptr(), ids.data_ptr(), _lib.ptr(probs), _lib.ptr(allowed), _lib.stream_ptr()),
-            "constrained_pick_logits")
+            state.data_ptr(), ids.data_ptr(), _lib.ptr(probs), _lib.ptr(allowed), _lib.stream_ptr()), entry)
         return ids, probs, allowed
 
     # ------------------------------------------------------------------ reference surface

@@ -90,8 +90,9 @@ class Seq2SeqModel(nn.Module):
                   temperature: float = None, top_k: int = None, top_p: float = None, beam_size: int = None,
                   constraint=None):
         """seq2seq.py:124-190: List[int] for one image, List[List[int]] for a batch.  (A ResNet encoder runs the eval
-        trunk its ``eval_precision`` selects; nothing here depends on which.)  ``constraint`` = a BracketTable: the greedy
-        search is the bracket-constrained one (LSTMDecoder.run_steps); beam search has no constrained form."""
+        trunk its ``eval_precision`` selects; nothing here depends on which.)  ``constraint`` = a BracketTable or an
+        ArgumentTable: the greedy search is the constrained one (LSTMDecoder.run_steps); beam search has no constrained
+        form."""
         max_length = 150 if max_length is None else max_length
         temperature = 1.0 if temperature is None else temperature
         top_k = 0 if top_k is None else top_k
@@ -250,7 +251,12 @@ class Seq2SeqModel(nn.Module):
         ``constraint``: a BracketTable (training/constraint.py) selects the well-formed search
         (i2l_beam_decode_nbest_constrained): a beam extends only by tokens its bracket state allows, with the log-probs
         renormalised over them, so every hypothesis nests its groups, ends on END (``finished`` is always True) and its
-        score is its log-probability under the constrained model.  ``nbest=1`` gives the single best one."""
+        score is its log-probability under the constrained model.  ``nbest=1`` gives the single best one.  An
+        ArgumentTable is refused: the beam entry reads bracket class bytes and would misread its bytes."""
+        from ..training.constraint import ArgumentTable
+        if isinstance(constraint, ArgumentTable):
+            raise RuntimeError("img2latex_amd: the argument rules exist for the greedy and sampling decode only; the N-best "
+                               "beam search takes a BracketTable (well_formed=True)")
         nbest = int(beam_size if nbest is None else nbest)
         table = length_norm_table(int(max_length), float(length_penalty), length_norm)
         dec = self.decoder

@@ -59,7 +59,7 @@ class GreedyPipeline:
                  stop: int = _lib.STOP_NONE, select: int = _lib.SELECT_LOGITS, detokenize=None,
                  split_decode: Optional[bool] = None, constraint=None):
         self.model = model
-        # constraint (training.constraint.BracketTable or None): the bracket-constrained decode.  It exists on the step-batched
+        # constraint (training.constraint.BracketTable, ArgumentTable or None): the constrained decode.  It exists on the step-batched
         # kernels only, so a pipeline that asks for a grouped co-resident decode refuses it instead of dropping it.
         self.constraint = constraint
         if constraint is not None and (int(decode_flags) & (_lib.FLAG_DECODE_GROUP8 | _lib.FLAG_DECODE_GROUP16) or split_decode):

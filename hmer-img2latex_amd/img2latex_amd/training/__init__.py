@@ -1,5 +1,5 @@
 """Training step of the hot path (reference img2latex/training/trainer.py:303-343, fp32 branch)."""
-from .constraint import BracketTable
+from .constraint import ArgumentTable, BracketTable
 from .dp import OverlappedAllReduce, all_reduce_gradients, shard_batch
 from .metrics import bleu_n_score, calculate_metrics, levenshtein_distance, masked_accuracy, token_list_accuracy
 from .predictor import DetokenizeTable, Predictor, TokenTable, detokenize_table, save_checkpoint, token_image
@@ -11,4 +11,4 @@ from .validate import BleuSampler, ValidationTimeout, Validator, teacher_forced_
 
 __all__ = ["TrainStep", "Predictor", "TokenTable", "DetokenizeTable", "detokenize_table", "token_image", "TokenizeTable", "tokenize_table", "tokenize_image", "pack_texts", "fit_vocabulary", "fit_formulas_file", "split_lines", "VocabFit", "save_checkpoint", "all_reduce_gradients", "shard_batch",
            "calculate_metrics", "levenshtein_distance", "bleu_n_score", "masked_accuracy", "token_list_accuracy",
-           "Validator", "BleuSampler", "validate", "teacher_forced_eval", "ValidationTimeout", "PlateauSchedule", "EarlyStopping", "BracketTable"]
+           "Validator", "BleuSampler", "validate", "teacher_forced_eval", "ValidationTimeout", "PlateauSchedule", "EarlyStopping", "BracketTable", "ArgumentTable"]

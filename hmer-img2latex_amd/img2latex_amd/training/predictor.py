@@ -70,7 +70,7 @@ class TokenTable:
         reference's warning about rows longer than ``max_sequence_length`` (tokenizer.py:106-113)."""
         from . import constraint as _constraint, tokenizer as _tokenizer
         self._set_vocabulary(fitted.token_to_id)
-        for cache in (_TABLES, _tokenizer._TABLES, _constraint._TABLES):
+        for cache in (_TABLES, _tokenizer._TABLES, _constraint._TABLES, _constraint._ARGUMENT_TABLES):
             cache.pop(self, None)
         if self.max_sequence_length is not None and fitted.longest_row > self.max_sequence_length:
             warnings.warn(f"Found sequences of length {fitted.longest_row}, which is longer than max_sequence_length "
@@ -248,6 +248,8 @@ class Predictor:
         # well_formed: every greedy and sampling decode and every N-best beam search (predict_nbest, predict_batch_nbest) of
         # this predictor is the bracket-constrained one (training/constraint.py: groups nest, END within max_length) -- True: the table BracketTable.from_tokenizer gives, or a BracketTable of the
         # caller's; each call's own ``well_formed=`` overrides it.  Off by default: nothing changes without it.
+        # "arguments" (or an ArgumentTable): the argument rules on top -- every command also gets the arguments it demands
+        # (ArgumentTable.from_tokenizer) -- for the greedy and sampling decodes; the N-best beam search refuses it.
         self.well_formed = well_formed
         self.device = torch.device("cuda") if device is None else torch.device(device)
         if self.device.type != "cuda":
@@ -271,7 +273,8 @@ class Predictor:
                    well_formed=well_formed)
 
     def _constraint(self, well_formed=None):
-        """The BracketTable of a call: its own ``well_formed`` (None: the predictor's), True meaning the tokenizer's table."""
+        """The BracketTable or ArgumentTable of a call: its own ``well_formed`` (None: the predictor's), True meaning the
+        tokenizer's bracket table, "arguments" its argument table."""
         from .constraint import as_table
         return as_table(self.well_formed if well_formed is None else well_formed, self.tokenizer)
 
@@ -750,6 +753,10 @@ class Predictor:
         ``_prepare_image`` as in ``predict_batch``, the ids through the tokenizer's own ``decode``.  ``well_formed``: the
         well-formed search, every hypothesis nesting its groups and ending on END (None: the predictor's own setting)."""
         constraint = self._constraint(well_formed)
+        from .constraint import ArgumentTable
+        if isinstance(constraint, ArgumentTable):
+            raise RuntimeError("img2latex_amd: the argument rules exist for the greedy and sampling decode only; the N-best "
+                               "beam search takes well_formed=True")
         if isinstance(images, torch.Tensor):
             images = [images] if images.dim() <= 3 else list(images)
         start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id

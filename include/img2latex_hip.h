@@ -491,6 +491,40 @@ int i2l_constrained_pick_logits(const float* logits, int ld, int rows, int vocab
                                 float top_p, uint64_t seed, int step, int steps, const uint8_t* cls, int end_id, void* state,
                                 int32_t* ids_out, float* probs_out, uint8_t* allowed_out, i2l_stream_t stream);
 
+/* ARGUMENT-COMPLETE step-batched decode: the bracket-constrained decode above under a stronger rule set
+ * (csrc/argument_rules.inc.h holds the rules, once, for device and host): groups nest, END arrives within `steps`, and
+ * every column that demands arguments gets them.
+ *   cls    (device, vocab bytes) bits 0..3 the class of the bracket table (0 neutral, 1..4 open, 5..8 close), bits 4..5
+ *          the number of arguments the column demands (0..3), bit 6 "loose": each argument is a brace group or ONE plain
+ *          token (class 0, no demand, not END); without it each is a brace group (opened by a class 1 column that
+ *          demands nothing).  Valid iff the low nibble is <= 8, bit 7 is clear, loose comes with a count > 0 and a
+ *          closer demands nothing; every other byte is never emitted.  A byte without argument bits means what it means
+ *          to i2l_greedy_decode_constrained, and a table of such bytes gives that entry's picks.
+ *   state  (device, >= i2l_argument_state_bytes(rows) = 32 bytes per row) uint64 stack, uint64 pending (2 bits per level
+ *          0..31: arguments owed there), uint32 loose (1 bit per level), int32 depth, int32 owed (the fewest tokens that
+ *          discharge every owed argument), int32 ended.  All-zero bytes are the initial state.
+ * Where an argument is owed only an argument opener -- or a plain token, if it is loose -- may be emitted; elsewhere the
+ * bracket rules hold, and a column is refused when owed + depth + 1 after it would exceed the emissions left, or when
+ * its demand would land on level 32.  Guaranteed beyond nesting and the END: every demanded argument is present.  Not
+ * guaranteed: double scripts, a sensible single-token argument, delimiters after \left, matching environment names,
+ * meaning.  The three entries take the argument lists of i2l_greedy_decode_constrained, i2l_sample_decode_constrained
+ * and i2l_constrained_pick_logits and refuse what they refuse, state_bytes < 32 * rows included. */
+size_t i2l_argument_state_bytes(int rows);   /* 32 per row, 0 for rows <= 0 */
+int i2l_greedy_decode_arguments(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                const int32_t* tok0, const float* h0, const float* c0, float temperature, int select,
+                                int stop, int end_id, int32_t* ids_out, float* logits_out, float* h_out, float* c_out,
+                                void* scratch, size_t scratch_bytes, int flags, uint32_t* resident_flag,
+                                uint32_t resident_value, const uint8_t* cls, void* state, size_t state_bytes,
+                                i2l_stream_t stream);
+int i2l_sample_decode_arguments(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                const int32_t* tok0, const float* h0, const float* c0, float temperature, int top_k,
+                                float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out, float* probs_out,
+                                float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
+                                const uint8_t* cls, void* state, size_t state_bytes, i2l_stream_t stream);
+int i2l_arguments_pick_logits(const float* logits, int ld, int rows, int vocab, float temperature, int select, int top_k,
+                              float top_p, uint64_t seed, int step, int steps, const uint8_t* cls, int end_id, void* state,
+                              int32_t* ids_out, float* probs_out, uint8_t* allowed_out, i2l_stream_t stream);
+
 /* Beam search for `images` independent images, `beam` beams each (<= I2L_MAX_BEAM):
  * per image exactly Seq2SeqModel._beam_search at batch 1 (seq2seq.py:234-298) --
  * log_softmax in fp32, top-k sorted descending with lower index first on ties, scores
