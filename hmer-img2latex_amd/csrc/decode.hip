@@ -1426,6 +1426,55 @@ extern "C" int i2l_arguments_pick_logits(const float* logits, int ld, int rows, 
     return I2L_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Ensemble decode (ensemble_rules.inc.h, decode_ensemble.inc.h; this package): the step-batched loop over M decoders of
+// one vocabulary, one combine launch per step, the selection kernels above on the combined row.  Every refusal is
+// decided on the host, here and in launch_ensemble, before the first HIP call; the library keeps no state.
+// ---------------------------------------------------------------------------------------------
+namespace {
+#include "decode_ensemble.inc.h"
+}  // namespace
+
+extern "C" size_t i2l_ensemble_scratch_bytes(const i2l_ensemble_member* members, int n, int rows) {
+    if (check_members(members, n) != I2L_OK) return 0;
+    for (int m = 0; m < n; ++m)
+        if (!batched_dims_ok(rows, members[m].w->vocab, members[m].w->hidden, members[m].w->layers)) return 0;
+    return ensemble_layout(members, n, rows, i2l_cdiv(members[0].w->vocab, VCHUNK) * VCHUNK).total;
+}
+
+extern "C" int i2l_ensemble_decode(const i2l_ensemble_member* members, int n, int combine, int rows, int steps,
+                                   const int32_t* tok0, const int32_t* forced, float temperature, int select, int top_k,
+                                   float top_p, uint64_t seed, int stop, int end_id, const uint8_t* cls, int cls_kind,
+                                   void* state, size_t state_bytes, int32_t* ids_out, float* dist_out, void* scratch,
+                                   size_t scratch_bytes, int flags, i2l_stream_t stream) {
+    int rc;
+    if ((rc = check_members(members, n))) return rc;
+    if (combine != I2L_ENSEMBLE_LOGPROB && combine != I2L_ENSEMBLE_PROB) return I2L_ERR_ARG;
+    const int vocab = members[0].w->vocab;
+    const bool sampling = select == I2L_SELECT_SAMPLE;
+    if (sampling ? (rc = check_sample(temperature, top_k, top_p)) : (rc = check_select(select))) return rc;
+    if ((rc = check_loop(rows, steps)) || (sampling && (rc = check_sample_vocab(vocab)))) return rc;
+    if (cls_kind != I2L_CONSTRAIN_NONE && cls_kind != I2L_CONSTRAIN_BRACKETS && cls_kind != I2L_CONSTRAIN_ARGUMENTS)
+        return I2L_ERR_ARG;
+    if (cls_kind != I2L_CONSTRAIN_NONE &&
+        (rc = check_constraint(rows, vocab, end_id, cls, state, state_bytes,
+                               cls_kind == I2L_CONSTRAIN_ARGUMENTS ? sizeof(ArgumentState) : sizeof(BracketState))))
+        return rc;
+    if (forced && (sampling || cls_kind != I2L_CONSTRAIN_NONE)) return I2L_ERR_ARG;
+    EnsembleCall c{};
+    c.members = members; c.n = n; c.combine = combine;
+    DecodeCall& a = c.shared;
+    a.rows = rows; a.steps = steps; a.tok0 = tok0; a.forced = forced;
+    a.temperature = temperature; a.select = select; a.stop = stop; a.end_id = end_id;
+    a.ids_out = ids_out; a.flags = flags; a.stream = stream;
+    if (sampling) a.sample = SampleRule{top_k, top_p, (unsigned long long)seed, dist_out};
+    else a.logits_out = dist_out;
+    if (cls_kind == I2L_CONSTRAIN_BRACKETS) a.con = ConstrainRule{cls, static_cast<BracketState*>(state), nullptr};
+    if (cls_kind == I2L_CONSTRAIN_ARGUMENTS) a.arg = ArgumentRule{cls, static_cast<ArgumentState*>(state), nullptr};
+    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
+    return launch_ensemble(c);
+}
+
 namespace {
 
 size_t beam_lds_bytes(int K, int L, int H, int Vp) {

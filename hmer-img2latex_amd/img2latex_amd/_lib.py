@@ -21,6 +21,9 @@ STOP_NONE, STOP_STICKY = 0, 1
 SELECT_LOGITS, SELECT_SOFTMAX, SELECT_SAMPLE = 0, 1, 2
 PREP_WEIGHTS, PREP_ROWS, PREP_ALL = 1, 2, 3
 MAX_LSTM_LAYERS, MAX_BEAM, MAX_NBEST = 4, 8, 16
+MAX_ENSEMBLE = 8                                  # I2L_MAX_ENSEMBLE: members of one i2l_ensemble_decode call
+ENSEMBLE_LOGPROB, ENSEMBLE_PROB = 0, 1            # I2L_ENSEMBLE_*: the combination rule
+CONSTRAIN_NONE, CONSTRAIN_BRACKETS, CONSTRAIN_ARGUMENTS = 0, 1, 2   # I2L_CONSTRAIN_*: the kind of its class table
 # kernel-selection flags (include/img2latex_hip.h I2L_FLAG_*): explicit arguments, the library reads no environment
 FLAG_EXACT_FP32, FLAG_NO_GROUP, FLAG_RESNET_NO_RING, FLAG_RESNET_IM2COL_STEM = 0x1, 0x2, 0x4, 0x8
 FLAG_WEIGHTS_PACKED = 0x10          # conv forward: the workspace still holds the packed filters of these weights
@@ -58,6 +61,12 @@ class DecodeHalf(ctypes.Structure):
     """struct i2l_decode_half: one batch's share of an i2l_greedy_decode_halves launch."""
     _fields_ = [("workspace", c_void_p), ("rows", c_int), ("steps", c_int), ("first_step", c_int), ("n_steps", c_int),
                 ("tok0", c_void_p), ("ids_out", c_void_p)]
+
+
+class EnsembleMember(ctypes.Structure):
+    """struct i2l_ensemble_member: one decoder's share of an i2l_ensemble_decode call."""
+    _fields_ = [("w", POINTER(DecoderWeights)), ("workspace", c_void_p), ("h0", c_void_p), ("c0", c_void_p),
+                ("h_out", c_void_p), ("c_out", c_void_p), ("weight", c_float)]
 
 
 class DecoderGrads(ctypes.Structure):
@@ -138,6 +147,10 @@ _SIGNATURES = {
                                             c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "i2l_arguments_pick_logits": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_uint64, c_int,
                                           c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "i2l_ensemble_scratch_bytes": (c_size_t, [POINTER(EnsembleMember), c_int, c_int]),
+    "i2l_ensemble_decode": (c_int, [POINTER(EnsembleMember), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
+                                    c_int, c_int, c_float, c_uint64, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "i2l_beam_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "i2l_beam_decode": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                 c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -6,12 +6,16 @@
                                                      [--well-formed]  (this package: greedy, sampling or --nbest)
                                                      [--complete-arguments]  (this package: greedy or sampling)
                                                      [--top-k K] [--top-p P] [--device cuda]
+                                                     [--ensemble CHECKPOINT ... --ensemble-weights a,b,...
+                                                      --ensemble-rule {logprob,prob}]  (this package: greedy or sampling)
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
                                   [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
                                   [--augment] [--data {auto,native,reference}] [--decode {host,device}]
     python -m img2latex_amd evaluate CHECKPOINT DATA_DIR [--split test] [--batch-size 32] [--num-samples N]
                                                          [--beam-size 0] [--device cuda] [--output-dir outputs]
                                                          [--decode {host,device}]
+                                                         [--ensemble CHECKPOINT ... --ensemble-weights a,b,...
+                                                          --ensemble-rule {logprob,prob}]  (this package)
     python -m img2latex_amd vocab FORMULAS_FILE OUT [--max-sequence-length N] [--device cuda]
 
 ``predict`` is the reference's chain end to end on the device: Predictor.from_checkpoint (predictor.py:61-137) ->
@@ -95,17 +99,44 @@ def _well_formed(well_formed):
     return well_formed if isinstance(well_formed, str) or hasattr(well_formed, "vocab") else bool(well_formed)
 
 
+def _predictor(checkpoint_path: str, device, decode_kernel: str, well_formed, ensemble=(), ensemble_weights=None,
+               ensemble_rule: str = "logprob"):
+    """Predictor.from_checkpoint, or with ``ensemble`` (further checkpoints) Predictor.from_checkpoints over
+    ``[checkpoint_path, *ensemble]`` -- ``ensemble_weights`` one per checkpoint, the positional one first."""
+    from .training import Predictor
+    if not ensemble:
+        return Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=device,
+                                         decode_flags=_decode_flags(decode_kernel), well_formed=_well_formed(well_formed))
+    return Predictor.from_checkpoints([checkpoint_path, *ensemble], weights=ensemble_weights, combine=ensemble_rule,
+                                      device=device, decode_flags=_decode_flags(decode_kernel),
+                                      well_formed=_well_formed(well_formed))
+
+
+def _ensemble_weights(text: Optional[str], n: int):
+    """--ensemble-weights "a,b,..." -> n floats (None when absent); ValueError with the reason otherwise."""
+    if text is None:
+        return None
+    try:
+        weights = [float(t) for t in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--ensemble-weights {text}: expected comma-separated numbers")
+    if len(weights) != n:
+        raise ValueError(f"--ensemble-weights has {len(weights)} values for {n} checkpoints (the positional one first)")
+    if not all(w > 0 and w != float("inf") for w in weights):
+        raise ValueError(f"--ensemble-weights {text}: every weight must be finite and above 0")
+    return weights
+
+
 def predict(checkpoint_path: str, image_path: str, beam_size: int = 0, max_length: int = 141, temperature: float = 1.0,
             top_k: int = 0, top_p: float = 0.0, device: Optional[str] = None, decode_kernel: str = "auto",
-            well_formed: bool = False) -> str:
+            well_formed: bool = False, ensemble=(), ensemble_weights=None, ensemble_rule: str = "logprob") -> str:
     """cli.py:253-308: returns the LaTeX string the command prints.  ``decode_kernel``: see ``_decode_flags``.
     ``well_formed``: the bracket-constrained decode (training/constraint.py): braces, \\left / \\right and \\begin / \\end
     nest and the formula ends within ``max_length`` tokens; ``"arguments"``: every command also gets the arguments it
-    demands (``\\frac`` its two groups, ``^`` its operand)."""
-    from .training import Predictor
-    predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device),
-                                          decode_flags=_decode_flags(decode_kernel),
-                                          well_formed=_well_formed(well_formed))
+    demands (``\\frac`` its two groups, ``^`` its operand).  ``ensemble``: further checkpoints that choose every token
+    together with the first one (``Predictor.from_checkpoints``)."""
+    predictor = _predictor(checkpoint_path, _device(device), decode_kernel, well_formed, ensemble, ensemble_weights,
+                           ensemble_rule)
     return predictor.predict(image=image_path, beam_size=beam_size, max_length=max_length, temperature=temperature,
                              top_k=top_k, top_p=top_p)
 
@@ -315,7 +346,7 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
 def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_size: int = 32,
              num_samples: Optional[int] = None, beam_size: int = 0, device: Optional[str] = None,
              output_dir: str = "outputs", decode: Optional[str] = None, decode_kernel: str = "auto",
-             well_formed: bool = False) -> Dict:
+             well_formed: bool = False, ensemble=(), ensemble_weights=None, ensemble_rule: str = "logprob") -> Dict:
     """cli.py:315-518 on the device: returns {"bleu", "levenshtein", "batch_size"} over the whole split -- the means over
     all pairs, as ``calculate_metrics`` on the reference's two lists computes them -- after printing the three result
     lines and writing ``predictions.json``.
@@ -326,19 +357,17 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
     unreadable file.  ``_prepare_image``'s other step, the bilinear resize of a tensor that is not 64 x 800, is not
     repeated: the loaders are built at the model's own input size, and the reference's encoder cannot run any other.
     ``decode``: "host" or "device", where the page files are decoded (``data.PageStore``); None: the checkpoint's
-    config key ``data.decode``, "host" when absent.  ``well_formed``: as in ``predict``."""
+    config key ``data.decode``, "host" when absent.  ``well_formed``: as in ``predict``.  ``ensemble``: as in ``predict``;
+    the split is then walked with ``evaluate_batch``, one batch at a time (the look-ahead pipeline is single-model)."""
     import json
     import warnings
     from pathlib import Path
     from . import data as D
-    from .training import Predictor
     from .training import metrics as M
     dev = _device(device)
     experiment_name = Path(checkpoint_path).parent.parent.name              # cli.py:340-349: outputs/<experiment>/checkpoints/<file>
     config = torch.load(checkpoint_path, map_location="cpu", weights_only=False).get("config", {}) or {}
-    predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=dev,
-                                          decode_flags=_decode_flags(decode_kernel),
-                                          well_formed=_well_formed(well_formed))
+    predictor = _predictor(checkpoint_path, dev, decode_kernel, well_formed, ensemble, ensemble_weights, ensemble_rule)
     max_samples = {"train": None, "val": None, "test": None}
     if num_samples:
         max_samples[split] = num_samples
@@ -367,8 +396,13 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
             yield x, batch["formulas"]
 
     stats, predictions = [], []
-    for out in predictor.evaluate_stream(batches(), max_length=predictor.tokenizer.max_sequence_length, return_strings=True,
-                                         return_statistics=True):
+    if ensemble:
+        results = (predictor.evaluate_batch(x, formulas, predictor.tokenizer.max_sequence_length, return_strings=True,
+                                            return_statistics=True) for x, formulas in batches())
+    else:
+        results = predictor.evaluate_stream(batches(), max_length=predictor.tokenizer.max_sequence_length,
+                                            return_strings=True, return_statistics=True)
+    for out in results:
         stats.append(out["statistics"])
         predictions.extend(out["pred_text"])
     if not stats:
@@ -473,6 +507,14 @@ def main(argv: Optional[List[str]] = None) -> int:
     e.add_argument("--complete-arguments", action="store_true",
                    help="(this package) implies --well-formed, and every command gets the arguments it demands: \\frac its "
                         "two groups, ^ and _ an operand")
+    for q in (p, e):
+        q.add_argument("--ensemble", action="append", default=[], metavar="CHECKPOINT",
+                       help="(this package) a further checkpoint of the same vocabulary; repeatable.  The checkpoints choose "
+                            "every token together (greedy and sampling only: refused with --beam-size)")
+        q.add_argument("--ensemble-weights", default=None, metavar="A,B,...",
+                       help="(this package) one weight per checkpoint, the positional one first (default: equal)")
+        q.add_argument("--ensemble-rule", choices=("logprob", "prob"), default="logprob",
+                       help="(this package) logprob: weighted geometric mean of the members' distributions; prob: arithmetic mean")
     v = sub.add_parser("vocab", help="(this package) Fit the vocabulary of a formulas file on the device and save it.")
     v.add_argument("formulas_file", help="Path to the formulas file, one formula per line")
     v.add_argument("out_path", help="Path to save the vocabulary to (LaTeXTokenizer.save's layout)")
@@ -481,6 +523,16 @@ def main(argv: Optional[List[str]] = None) -> int:
     args = ap.parse_args(argv)
     if args.command == "predict" and args.nbest < 0:
         ap.error("--nbest must be >= 0")
+    ensemble_weights = None
+    if args.command in ("predict", "evaluate"):
+        if args.ensemble and args.beam_size > 0:
+            ap.error("--ensemble with --beam-size: the ensemble decode is greedy or sampling (beam search is single-model)")
+        if not args.ensemble and args.ensemble_weights is not None:
+            ap.error("--ensemble-weights needs --ensemble")
+        try:
+            ensemble_weights = _ensemble_weights(args.ensemble_weights, 1 + len(args.ensemble))
+        except ValueError as exc:
+            ap.error(str(exc))
     if args.command == "predict" and args.complete_arguments and args.beam_size > 0:
         ap.error("--complete-arguments with --beam-size: the argument rules exist for the greedy and sampling decode only "
                  "(--well-formed --nbest N is the constrained beam search)")
@@ -499,7 +551,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     if args.command == "predict":
         latex = predict(args.checkpoint_path, args.image_path, args.beam_size, args.max_length, args.temperature,
-                        args.top_k, args.top_p, args.device, args.decode_kernel, args.well_formed)
+                        args.top_k, args.top_p, args.device, args.decode_kernel, args.well_formed, args.ensemble,
+                        ensemble_weights, args.ensemble_rule)
         print("Generated LaTeX:")
         print(latex)
         return 0
@@ -508,7 +561,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     if args.command == "evaluate":
         evaluate(args.checkpoint_path, args.data_dir, args.split, args.batch_size, args.num_samples, args.beam_size,
-                 args.device, args.output_dir, args.decode, args.decode_kernel, args.well_formed)
+                 args.device, args.output_dir, args.decode, args.decode_kernel, args.well_formed, args.ensemble,
+                 ensemble_weights, args.ensemble_rule)
         return 0
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,

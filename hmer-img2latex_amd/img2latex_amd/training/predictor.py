@@ -272,6 +272,53 @@ class Predictor:
                    model_type=config.get("model", {}).get("name", "cnn_lstm"), decode_flags=decode_flags,
                    well_formed=well_formed)
 
+    @classmethod
+    def from_checkpoints(cls, checkpoint_paths: Sequence[str], weights: Optional[Sequence[float]] = None,
+                         combine: str = "logprob", device: Optional[torch.device] = None, decode_flags: int = 0,
+                         well_formed=False) -> "Predictor":
+        """An ENSEMBLE predictor (this package): the checkpoints' decoders choose every token together
+        (model/ensemble.py, i2l_ensemble_decode) under ``combine`` = "logprob" (weighted geometric mean of the members'
+        distributions) or "prob" (arithmetic mean), with ``weights`` one per checkpoint (None: equal).  The checkpoints
+        must agree on ``token_to_id``, the special tokens, the model type and the encoder's input geometry (height,
+        width, channels); the first difference raises ValueError.  ``predict``, ``predict_batch``, ``predict_batch_ids``
+        and ``evaluate_batch`` work as for one checkpoint; the stream and N-best methods raise RuntimeError."""
+        from ..model.ensemble import EnsembleModel, combine_rule, member_weights
+        paths = list(checkpoint_paths)
+        if not 1 <= len(paths) <= _lib.MAX_ENSEMBLE:
+            raise ValueError(f"img2latex_amd: an ensemble has 1 .. {_lib.MAX_ENSEMBLE} checkpoints, got {len(paths)}")
+        weights = member_weights(weights, len(paths))
+        combine_rule(combine)
+        models, first = [], None
+        for path in paths:
+            checkpoint = torch.load(path, map_location="cpu", weights_only=False)
+            config = checkpoint.get("config", {})
+            tcfg = checkpoint.get("tokenizer_config", {})
+            tokenizer = TokenTable(tcfg.get("token_to_id"), tcfg.get("special_tokens"), tcfg.get("max_sequence_length", 141))
+            model = model_from_checkpoint_config(config, tokenizer.vocab_size)
+            enc = model.encoder
+            facts = {"token_to_id": tokenizer.token_to_id, "special tokens": tokenizer.special_tokens,
+                     "model type": config.get("model", {}).get("name", "cnn_lstm"),
+                     "input geometry": (enc.img_height, enc.img_width), "channels": enc.channels}
+            if first is None:
+                first = (path, tokenizer, facts)
+            for name, value in facts.items():
+                if value != first[2][name]:
+                    shown = "" if name == "token_to_id" else f" ({first[2][name]} / {value})"
+                    raise ValueError(f"img2latex_amd: the checkpoints of an ensemble must agree on their {name}: "
+                                     f"{first[0]} and {path} differ{shown}")
+            model.load_state_dict(checkpoint["model_state_dict"])
+            models.append(model)
+        return cls(model=EnsembleModel(models, weights, combine), tokenizer=first[1], device=device,
+                   model_type=first[2]["model type"], decode_flags=decode_flags, well_formed=well_formed)
+
+    def _single_model(self, what: str) -> None:
+        """Refuses ``what`` for an ensemble predictor, before anything is launched."""
+        from ..model.ensemble import EnsembleModel
+        if isinstance(self.model, EnsembleModel):
+            raise RuntimeError(f"img2latex_amd: {what} is single-model (the look-ahead pipeline and the beam search have "
+                               "no ensemble form); an ensemble predictor has predict, predict_batch, predict_batch_ids "
+                               "and evaluate_batch")
+
     def _constraint(self, well_formed=None):
         """The BracketTable or ArgumentTable of a call: its own ``well_formed`` (None: the predictor's), True meaning the
         tokenizer's bracket table, "arguments" its argument table."""
@@ -415,6 +462,7 @@ class Predictor:
         returns for that batch (up to fp32 near-ties between the two decode kernels).  A ResNet encoder's bf16 trunk also
         picks other tile shapes with two trunks in flight, which can move ids; with ``model.encoder.eval_precision =
         "fp32"`` the features of the two paths are bit-identical."""
+        self._single_model("predict_ids_stream")
         return self._stream(batches, max_length, temperature, None)
 
     def predict_strings_stream(self, batches, max_length: int = 141, temperature: float = 1.0, well_formed=None):
@@ -423,6 +471,10 @@ class Predictor:
         behind each decode and copies the packed bytes + row offsets beside the ids; the host slices them.  A tokenizer
         without a device image (``token_image`` gives None) takes the host ``decode`` on the id stream.  ``well_formed``:
         the bracket-constrained decode; the pipeline then runs the step-batched kernels, not the grouped co-resident ones."""
+        self._single_model("predict_strings_stream")
+        return self._strings_stream(batches, max_length, temperature, well_formed)
+
+    def _strings_stream(self, batches, max_length, temperature, well_formed):
         table = detokenize_table(self.tokenizer, self.device)
         constraint = self._constraint(well_formed)
         if table is None:
@@ -459,7 +511,7 @@ class Predictor:
             pipe.close()                                     # gives its decoder workspaces back
 
     def evaluate_batch(self, images, targets: Union[torch.Tensor, Sequence[str]], max_length: Optional[int] = None,
-                       return_strings: bool = False, well_formed=None) -> Dict:
+                       return_strings: bool = False, well_formed=None, return_statistics: bool = False) -> Dict:
         """One batch of the reference's ``evaluate`` command (cli.py:449-495) with every stage on the device and
         the token ids never leaving HBM between them:
 
@@ -477,9 +529,12 @@ class Predictor:
         (device tensors) for callers that also want the strings.  ``return_strings``: also "pred_text", the
         ``tokenizer.decode`` of every row of "pred_ids", built by i2l_detokenize in the same chain (from the decode's ids
         under the compaction's own cut and drop rule: the compacted rows are zero-padded and the kernel takes no
-        lengths) and copied beside the statistics; a tokenizer without a device image decodes "pred_ids" on the host."""
-        return self._evaluate_finish(self._evaluate_launch(images, targets, max_length, return_strings=return_strings,
-                                                           constraint=self._constraint(well_formed)))
+        lengths) and copied beside the statistics; a tokenizer without a device image decodes "pred_ids" on the host.
+        ``return_statistics``: also "statistics", as in ``evaluate_stream``."""
+        launched = self._evaluate_launch(images, targets, max_length, return_strings=return_strings,
+                                         constraint=self._constraint(well_formed))
+        launched["return_statistics"] = return_statistics
+        return self._evaluate_finish(launched)
 
     def evaluate_stream(self, batches, max_length: Optional[int] = None, lookahead: int = 2, return_strings: bool = False,
                         return_statistics: bool = False, well_formed=None):
@@ -507,6 +562,10 @@ class Predictor:
         "statistics", a host copy of its (B, 9) int32 statistics rows; ``metrics.metrics_from_packed`` of the rows of all
         batches, concatenated, gives the means over all pairs of a split (not means of batch means).  ``well_formed``: the
         bracket-constrained decode (step-batched kernels) in the place of the grouped one, the schedule otherwise the same."""
+        self._single_model("evaluate_stream")
+        return self._evaluate_stream(batches, max_length, lookahead, return_strings, return_statistics, well_formed)
+
+    def _evaluate_stream(self, batches, max_length, lookahead, return_strings, return_statistics, well_formed):
         from collections import deque
         pending = deque()
         constraint = self._constraint(well_formed)
@@ -752,6 +811,7 @@ class Predictor:
         order (Seq2SeqModel.beam_search_nbest: key = score / length ** length_penalty), every image through
         ``_prepare_image`` as in ``predict_batch``, the ids through the tokenizer's own ``decode``.  ``well_formed``: the
         well-formed search, every hypothesis nesting its groups and ending on END (None: the predictor's own setting)."""
+        self._single_model("predict_batch_nbest")
         constraint = self._constraint(well_formed)
         from .constraint import ArgumentTable
         if isinstance(constraint, ArgumentTable):
@@ -775,4 +835,5 @@ class Predictor:
     def predict_nbest(self, image, beam_size: int = 5, nbest: Optional[int] = None, max_length: int = 141,
                       length_penalty: float = 0.0, well_formed=None) -> List[Tuple[str, float, float]]:
         """``predict_batch_nbest`` for one image (path / PIL / ndarray / tensor)."""
+        self._single_model("predict_nbest")
         return self.predict_batch_nbest([image], beam_size, nbest, max_length, length_penalty, well_formed=well_formed)[0]

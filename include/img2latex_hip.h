@@ -525,6 +525,54 @@ int i2l_arguments_pick_logits(const float* logits, int ld, int rows, int vocab, 
                               float top_p, uint64_t seed, int step, int steps, const uint8_t* cls, int end_id, void* state,
                               int32_t* ids_out, float* probs_out, uint8_t* allowed_out, i2l_stream_t stream);
 
+/* ENSEMBLE decode (this package: the reference decodes with one model): n decoders of ONE vocabulary choose every token
+ * together, on the step-batched loop.  Each member runs its own LSTM and logits launches on its own state along the
+ * SHARED tokens; one launch per step combines the members' rows (csrc/ensemble_rules.inc.h holds the rule, once, for
+ * device and host) and the selection kernels of the entries above pick from the combined row.  With weights w_m
+ * normalised to sum 1 and lp_m = log_softmax of member m's raw logits over [0, vocab) (no temperature):
+ *   I2L_ENSEMBLE_LOGPROB  y[v] = sum_m w_m lp_m[v]            (geometric mean, left unnormalised)
+ *   I2L_ENSEMBLE_PROB     y[v] = log(sum_m w_m exp(lp_m[v]))  (arithmetic mean)
+ * y is "the ensemble's logits": the division by the temperature, select, the top-k / top-p sampling, the constraint masks
+ * and dist_out treat it as they treat one model's logits.  A column that is -inf in one member is -inf under LOGPROB;
+ * under PROB the other members decide.  n == 1: no combination, the call is i2l_greedy_decode_batched /
+ * i2l_sample_decode_batched (or their constrained forms) bit for bit.  A step is sum(layers) + n + 2 launches on `stream`.
+ *   members     n records (this package): weights, the workspace i2l_decoder_prepare built for them and these rows,
+ *               optional h0 / c0 (both or neither) and h_out / c_out, each (layers, rows, hidden) of THAT member, and
+ *               weight (finite, > 0; normalised by the call).  Members may differ in embed, hidden and layers.
+ *   select      I2L_SELECT_LOGITS / _SOFTMAX: the arg max, top_k / top_p / seed ignored, dist_out (rows, steps, vocab) or
+ *               NULL receives the combined rows y.  I2L_SELECT_SAMPLE: i2l_sample_decode_batched's draw, dist_out receives
+ *               the sampling distributions.
+ *   cls_kind    I2L_CONSTRAIN_NONE (cls, state ignored), _BRACKETS (i2l_greedy_decode_constrained's table and 16-byte
+ *               states) or _ARGUMENTS (i2l_greedy_decode_arguments' table and 32-byte states); the call zeroes the state.
+ *   scratch     i2l_ensemble_scratch_bytes(members, n, rows) bytes of device memory (0 for members the call refuses).
+ * Refused on the host before the first HIP call: n < 1, a NULL member / weights / workspace / tok0, vocabularies that
+ * differ, a weight that is not finite and > 0, an unknown combine, select, stop or cls_kind, rows or steps <= 0, the
+ * sampling arguments i2l_sample_decode_batched refuses, `forced` together with sampling or a constraint, end_id outside
+ * [0, vocab) or a NULL cls / state under a constraint (all I2L_ERR_ARG); n > I2L_MAX_ENSEMBLE, dimensions
+ * i2l_greedy_decode_batched refuses, sampling with vocab > 2048 (I2L_ERR_UNSUPPORTED); scratch_bytes or state_bytes too
+ * small (I2L_ERR_WORKSPACE).  flags: none used.  The library keeps no state. */
+#define I2L_MAX_ENSEMBLE 8
+#define I2L_ENSEMBLE_LOGPROB 0
+#define I2L_ENSEMBLE_PROB 1
+#define I2L_CONSTRAIN_NONE 0
+#define I2L_CONSTRAIN_BRACKETS 1
+#define I2L_CONSTRAIN_ARGUMENTS 2
+typedef struct i2l_ensemble_member {
+    const i2l_decoder_weights* w;
+    const void* workspace;
+    const float* h0;
+    const float* c0;
+    float* h_out;
+    float* c_out;
+    float weight;
+} i2l_ensemble_member;
+size_t i2l_ensemble_scratch_bytes(const i2l_ensemble_member* members, int n, int rows);
+int i2l_ensemble_decode(const i2l_ensemble_member* members, int n, int combine, int rows, int steps, const int32_t* tok0,
+                        const int32_t* forced, float temperature, int select, int top_k, float top_p, uint64_t seed,
+                        int stop, int end_id, const uint8_t* cls, int cls_kind, void* state, size_t state_bytes,
+                        int32_t* ids_out, float* dist_out, void* scratch, size_t scratch_bytes, int flags,
+                        i2l_stream_t stream);
+
 /* Beam search for `images` independent images, `beam` beams each (<= I2L_MAX_BEAM):
  * per image exactly Seq2SeqModel._beam_search at batch 1 (seq2seq.py:234-298) --
  * log_softmax in fp32, top-k sorted descending with lower index first on ties, scores
