@@ -1,7 +1,7 @@
 // The argument rules of the constrained decode, stated once: bracket_rules.inc.h's nesting rules plus arity -- every
 // column that demands arguments (\frac's two groups, the operand of ^) gets them.  Which vocabulary columns a row may
 // emit at a step, what the pick does to the row's state, and what is picked when a malformed table leaves nothing.
-// Shared by the selection kernels' argument policy (decode_arguments.inc.h) and a stand-alone host program
+// Shared by the selection kernels' pick policy (decode_constrained.inc.h) and a stand-alone host program
 // (argument_rules_host_main.cpp) that a host test compares with the Python restatement (training/constraint.py
 // ArgumentTable) step by step and with an independent recogniser over every short sequence.
 //
@@ -39,7 +39,7 @@
 // strict argument is owed, a plain token when a loose one is, else the innermost closer (d > 0) or END (d == 0).  So
 // every row ends on END at depth 0 with nothing owed within `steps` steps -- provided the table has {, } and a plain
 // token wherever it demands strict / loose arguments, and a closer for every open kind; ArgumentTable (constraint.py)
-// builds no other.  A table that breaks this can leave NO column allowed; the pick is then end_id (ar_fallback) --
+// builds no other.  A table that breaks this can leave NO column allowed; the pick is then end_id (constraint_fallback) --
 // defined, though such a row is not complete.  With no demanding column owed is 0 throughout and the lines above are
 // bracket_rules.inc.h's: neutral iff d + 1 <= rem, open iff d < 32 and d + 2 <= rem.
 //
@@ -118,7 +118,7 @@ BR_HD int ar_rule(const ArgumentRow& r, bool is_end, uint8_t c) {
 BR_HD bool ar_allowed(const ArgumentRow& r, bool is_end, uint8_t c) { return ar_rule(r, is_end, c) == BR_OK; }
 
 // After the pick: the argument it was (if one was owed), push or pop, then its own demand on the level it landed on --
-// whose pending is 0 at that point.  A pick the rules would not have allowed (only ar_fallback's END) ends the row as is.
+// whose pending is 0 at that point.  A pick the rules would not have allowed (only the fallback's END) ends the row as is.
 BR_HD void ar_advance(ArgumentState& s, bool is_end, uint8_t c) {
     if (s.ended) return;
     if (is_end) { s.ended = 1; return; }
@@ -142,10 +142,11 @@ BR_HD void ar_advance(ArgumentState& s, bool is_end, uint8_t c) {
     }
 }
 
-// The pick when the selection found none among the allowed columns (no column allowed, or every allowed logit -inf /
-// NaN): the first allowed column, else end_id.
-BR_HD int ar_fallback(const ArgumentRow& r, const uint8_t* cls, int V, int end_id) {
-    for (int v = 0; v < V; ++v)
-        if (ar_allowed(r, v == end_id, cls[v])) return v;
-    return end_id;
-}
+// The rule model (bracket_rules.inc.h); the fallback pick is constraint_fallback<ArgumentModel>.
+struct ArgumentModel {
+    using State = ArgumentState;
+    using Row = ArgumentRow;
+    BR_HD static Row row(const State& s, int rem) { return ar_row(s, rem); }
+    BR_HD static bool allowed(const Row& r, bool is_end, uint8_t c) { return ar_allowed(r, is_end, c); }
+    BR_HD static void advance(State& s, bool is_end, uint8_t c) { ar_advance(s, is_end, c); }
+};

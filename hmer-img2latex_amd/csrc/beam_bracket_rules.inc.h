@@ -15,7 +15,7 @@
 //                closer or a forced END costs 0.  (The device's phase (c) renormalises; bb_candidates takes a row of
 //                log-probs as it is.)
 //   Fallback     no column allowed, or a selection round finds none (every allowed value left is -inf or NaN): the list
-//                stops there, and an EMPTY list becomes the single candidate (end_id, 0.0f) -- as br_fallback, defined
+//                stops there, and an EMPTY list becomes the single candidate (end_id, 0.0f) -- as constraint_fallback, defined
 //                but not well formed.  Only a malformed table, or a row without a finite allowed logit.  (bb_close_list)
 //   Inheritance  new slot q has br_advance(copy of parent npar[q]'s state, ntok[q] == end_id, cls[ntok[q]]); the parents
 //                are read from a copy taken before any slot is overwritten                            (bb_inherit)

@@ -17,8 +17,8 @@
 // d + 1 <= steps - t holds at t = 0 for steps >= 1 and every allowed pick keeps it, so the closer of the innermost
 // kind (d > 0) or END (d == 0) is always allowed: every row emits END at depth 0 within `steps` steps.  A row that has
 // ended is not constrained any more.  A table without the closer of an open kind can leave NO column allowed; the pick
-// is then end_id (br_fallback) -- defined, though such a row is not well formed.  BracketTable (constraint.py) never
-// builds such a table: an open without a closer becomes "never".
+// is then end_id (constraint_fallback) -- defined, though such a row is not well formed.  BracketTable (constraint.py)
+// never builds such a table: an open without a closer becomes "never".
 #pragma once
 #include <stdint.h>
 
@@ -68,7 +68,7 @@ BR_HD int br_rule(const BracketState& s, bool is_end, uint8_t c, int rem) {
 
 BR_HD bool br_allowed(const BracketState& s, bool is_end, uint8_t c, int rem) { return br_rule(s, is_end, c, rem) == BR_OK; }
 
-// after the pick: push, pop or end.  A pick the rules would not have allowed (only br_fallback's END) ends the row as is.
+// after the pick: push, pop or end.  A pick the rules would not have allowed (only the fallback's END) ends the row as is.
 BR_HD void br_advance(BracketState& s, bool is_end, uint8_t c) {
     if (s.ended) return;
     if (is_end) { s.ended = 1; return; }
@@ -82,10 +82,22 @@ BR_HD void br_advance(BracketState& s, bool is_end, uint8_t c) {
     }
 }
 
+// The rules as a RULE MODEL: the five names under which the selection kernels' pick policy (decode_constrained.inc.h),
+// constraint_fallback and the host programs' walk (rules_walk_host.inc.h) take a rule set -- the per-row State, the
+// per-step Row derived from it once, row(state, rem), allowed(row, is_end, c), advance(state&, is_end, c).
+struct BracketModel {
+    using State = BracketState;
+    struct Row { BracketState st; int rem; };
+    BR_HD static Row row(const State& s, int rem) { return {s, rem}; }
+    BR_HD static bool allowed(const Row& r, bool is_end, uint8_t c) { return br_allowed(r.st, is_end, c, r.rem); }
+    BR_HD static void advance(State& s, bool is_end, uint8_t c) { br_advance(s, is_end, c); }
+};
+
 // The pick when the selection found none among the allowed columns (no column allowed, or every allowed logit -inf /
-// NaN): the first allowed column, else end_id.
-BR_HD int br_fallback(const BracketState& s, const uint8_t* cls, int V, int end_id, int rem) {
+// NaN), under any model: the first allowed column, else end_id.
+template <class Model>
+BR_HD int constraint_fallback(const typename Model::Row& r, const uint8_t* cls, int V, int end_id) {
     for (int v = 0; v < V; ++v)
-        if (br_allowed(s, v == end_id, cls[v], rem)) return v;
+        if (Model::allowed(r, v == end_id, cls[v])) return v;
     return end_id;
 }

@@ -285,10 +285,8 @@ __device__ __forceinline__ int beam_topk_row(const float* x, int V, int K, int l
 #include "beam_group.inc.h"
 #include "decode_batched.inc.h"
 #include "sample_batched.inc.h"
-#include "bracket_rules.inc.h"
+#include "argument_rules.inc.h"      // and bracket_rules.inc.h
 #include "decode_constrained.inc.h"
-#include "argument_rules.inc.h"
-#include "decode_arguments.inc.h"
 #include "beam_bracket_rules.inc.h"
 #include "beam_batched.inc.h"
 #include "beam_nbest.inc.h"
@@ -827,12 +825,30 @@ inline int check_sample(float temperature, int top_k, float top_p) {
     return sample_args_ok(temperature, top_k, top_p) ? I2L_OK : I2L_ERR_ARG;
 }
 inline int check_sample_vocab(int vocab) { return vocab > SB_MAXV ? I2L_ERR_UNSUPPORTED : I2L_OK; }
+
+// A constrained selection: the rule set (I2L_CONSTRAIN_BRACKETS or _ARGUMENTS; 0, I2L_CONSTRAIN_NONE, is "absent"), its
+// table and the rows' state.  THE place a rule set is added: its state size here, its rule object in with_rule.
+struct Constraint {
+    int kind;
+    const uint8_t* cls;      // [V] table bytes
+    void* state;             // [rows] BracketState or ArgumentState
+    uint8_t* allowed;        // [rows][V] the allowed sets out, or null (the pick-logits entries)
+};
+inline size_t constraint_state_bytes(int kind, int rows) {
+    const size_t row_bytes = kind == I2L_CONSTRAIN_ARGUMENTS ? sizeof(ArgumentState) : sizeof(BracketState);
+    return rows > 0 ? (size_t)rows * row_bytes : 0;
+}
+// f(rule) with the rule object of c: NoRule, ConstrainRule or ArgumentRule
+template <class F>
+void with_rule(const Constraint& c, F&& f) {
+    if (c.kind == I2L_CONSTRAIN_BRACKETS) f(ConstrainRule{c.cls, static_cast<BracketState*>(c.state), c.allowed});
+    else if (c.kind == I2L_CONSTRAIN_ARGUMENTS) f(ArgumentRule{c.cls, static_cast<ArgumentState*>(c.state), c.allowed});
+    else f(NoRule{});
+}
 // the constraint's own arguments; rows > 0 and vocab > 0 are checked before it
-// (row_bytes: sizeof(BracketState), or sizeof(ArgumentState) under the argument rules)
-int check_constraint(int rows, int vocab, int end_id, const uint8_t* cls, const void* state, size_t state_bytes,
-                     size_t row_bytes = sizeof(BracketState)) {
+int check_constraint(int kind, int rows, int vocab, int end_id, const uint8_t* cls, const void* state, size_t state_bytes) {
     if (end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
-    if (state_bytes < (size_t)rows * row_bytes) return I2L_ERR_WORKSPACE;
+    if (state_bytes < constraint_state_bytes(kind, rows)) return I2L_ERR_WORKSPACE;
     return I2L_OK;
 }
 
@@ -854,10 +870,12 @@ struct DecodeCall {
     uint32_t resident_value;
     i2l_stream_t stream;
     int rows_per_wg;                   // launch_decode: 0 = its own choice
-    ConstrainRule con;                 // launch_batched: con.cls != null asks for the bracket-constrained selection
-    ArgumentRule arg;                  // launch_batched: arg.cls != null asks for the argument-complete one (not with con)
+    Constraint constraint;             // launch_batched: the constrained selection
     void* scratch;                     // launch_batched
     size_t scratch_bytes;
+    // launch_batched, i2l_ensemble_decode only: the decoders, in the place of w, workspace, h0, c0, h_out and c_out
+    const i2l_ensemble_member* members;
+    int n_members, combine;
 };
 
 }  // namespace
@@ -1170,55 +1188,93 @@ void launch_batched_select(const BatchedParams& p, const DecodeCall& a, const Ru
         hipLaunchKernelGGL(select_batched_kernel<Rule>, dim3(i2l_cdiv(p.B, DB_NT / 64)), dim3(DB_NT), 0, s, p, rule, t);
 }
 
-// The loop of the step-batched entries.  The caller has checked the weights and its own arguments; every other refusal
-// is decided here, before the first HIP call.  A constrained call starts from the rows' zeroed bracket or argument state.
+#include "decode_ensemble.inc.h"
+
+// THE loop of the step-batched entries, for one decoder (a.w .. a.c_out) or an ensemble's (a.members): every member
+// runs its own recurrences and logits on its own batched_layout slice of the scratch, tok / fin / live are member 0's,
+// and ONE selection picks per step -- from member 0's logits, or for n > 1 from the combined rows behind the slices.  A
+// single-decoder entry's scratch is batched_layout's alone, an ensemble's has the combined buffer whatever n is.  The
+// caller has checked the weights and its own arguments; every other refusal is decided here, before the first HIP
+// call.  A constrained call starts from the rows' zeroed state.
 int launch_batched(const DecodeCall& a) {
-    if (!a.workspace || !a.tok0 || check_loop(a.rows, a.steps)) return I2L_ERR_ARG;
-    if ((a.h0 == nullptr) != (a.c0 == nullptr)) return I2L_ERR_ARG;
+    const i2l_ensemble_member self{a.w, a.workspace, a.h0, a.c0, a.h_out, a.c_out, 1.f};
+    const i2l_ensemble_member* members = a.members ? a.members : &self;
+    const int n = a.members ? a.n_members : 1, rows = a.rows, steps = a.steps;
+    if (!a.tok0 || check_loop(rows, steps)) return I2L_ERR_ARG;
     if (a.stop != I2L_STOP_NONE && a.stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
-    if (a.con.cls && a.arg.cls) return I2L_ERR_ARG;
-    const int rows = a.rows, steps = a.steps;
-    const int V = a.w->vocab, E = a.w->embed, H = a.w->hidden, L = a.w->layers;
-    const Layout lo = make_layout(rows, V, E, H, L);
-    const BatchedLayout bl = batched_layout(rows, lo.Vp, H, L);
-    if (!a.scratch || a.scratch_bytes < bl.total) return I2L_ERR_WORKSPACE;
+    float weight[ENS_MAX];
+    for (int m = 0; m < n; ++m) {
+        const i2l_ensemble_member& mem = members[m];
+        if (!mem.workspace || (mem.h0 == nullptr) != (mem.c0 == nullptr) || !ens_weight_ok(mem.weight)) return I2L_ERR_ARG;
+        weight[m] = mem.weight;
+    }
+    const int V = members[0].w->vocab, Vp = i2l_cdiv(V, VCHUNK) * VCHUNK;
+    const EnsembleLayout el = ensemble_layout(members, n, rows, Vp);
+    if (!a.scratch || a.scratch_bytes < (a.members ? el.total : el.combined)) return I2L_ERR_WORKSPACE;
 
     char* sb = static_cast<char*>(a.scratch);
-    BatchedParams p{};
-    p.w = step_weights(lo, static_cast<const char*>(a.workspace), V, H, L);
-    p.B = rows; p.T = steps; p.genc_div = 1; p.forced = a.forced;
-    p.h = reinterpret_cast<float*>(sb + bl.h); p.c = reinterpret_cast<float*>(sb + bl.c);
-    p.lg = reinterpret_cast<float*>(sb + bl.lg);
-    p.tok = reinterpret_cast<int*>(sb + bl.tok); p.fin = reinterpret_cast<int*>(sb + bl.fin);
-    p.live = reinterpret_cast<unsigned*>(sb + bl.live);
-    p.ids = a.ids_out; p.logits_out = a.logits_out;
-    p.temperature = a.temperature; p.use_temp = use_temp(a.temperature);
-    p.select = a.select; p.stop = a.stop; p.end_id = a.end_id;
+    BatchedParams p[ENS_MAX];
+    int tb_lstm[ENS_MAX], tb_logits[ENS_MAX], copy_grid[ENS_MAX];
+    EnsembleRows e{};
+    for (int m = 0; m < n; ++m) {
+        const i2l_decoder_weights& w = *members[m].w;
+        const Layout lo = make_layout(rows, V, w.embed, w.hidden, w.layers);
+        const BatchedLayout bl = batched_layout(rows, Vp, w.hidden, w.layers);
+        char* mb = sb + el.member[m];
+        BatchedParams& q = p[m];
+        q = BatchedParams{};
+        q.w = step_weights(lo, static_cast<const char*>(members[m].workspace), V, w.hidden, w.layers);
+        q.B = rows; q.T = steps; q.genc_div = 1; q.forced = a.forced;
+        q.h = reinterpret_cast<float*>(mb + bl.h); q.c = reinterpret_cast<float*>(mb + bl.c);
+        q.lg = reinterpret_cast<float*>(mb + bl.lg);
+        // tok, fin and live are member 0's words for every member; ids and the distribution belong to the selection
+        q.tok = m ? p[0].tok : reinterpret_cast<int*>(mb + bl.tok);
+        q.fin = m ? p[0].fin : reinterpret_cast<int*>(mb + bl.fin);
+        q.live = m ? p[0].live : reinterpret_cast<unsigned*>(mb + bl.live);
+        q.temperature = a.temperature; q.use_temp = use_temp(a.temperature);
+        q.select = a.select; q.stop = a.stop; q.end_id = a.end_id;
+        tb_lstm[m] = batched_tile_rows(w.hidden / 16, rows);
+        tb_logits[m] = batched_tile_rows(Vp / DB_COLS, rows);
+        const size_t LBH = (size_t)w.layers * rows * w.hidden, BT = (size_t)rows * steps;
+        const size_t most = LBH > BT ? LBH : BT, copy_blocks = (most + DB_NT - 1) / DB_NT;
+        copy_grid[m] = (int)(copy_blocks < 1024 ? copy_blocks : 1024);
+        e.lg[m] = q.lg; e.ld[m] = Vp;
+    }
+    p[0].ids = a.ids_out; p[0].logits_out = a.logits_out;
+    BatchedParams pe = p[0];                                    // the selection's: member 0's, the combined rows for n > 1
+    if (n > 1) {
+        pe.lg = reinterpret_cast<float*>(sb + el.combined);
+        ens_normalise(weight, n, e.w, e.logw);
+        e.out = pe.lg; e.ld_out = Vp; e.B = rows; e.V = V; e.rule = a.combine; e.live = pe.live;
+    }
 
     hipStream_t s = i2l_s(a.stream);
     if (a.resident_flag) {      // nothing here waits for a partner: "resident" is said at once
         hipLaunchKernelGGL(publish_value32_kernel, dim3(1), dim3(1), 0, s, a.resident_flag, a.resident_value);
         I2L_CHECK_LAUNCH();
     }
-    if (a.con.cls && hipMemsetAsync(a.con.state, 0, (size_t)rows * sizeof(BracketState), s) != hipSuccess) return I2L_ERR_LAUNCH;
-    if (a.arg.cls && hipMemsetAsync(a.arg.state, 0, (size_t)rows * sizeof(ArgumentState), s) != hipSuccess) return I2L_ERR_LAUNCH;
-    const size_t most = (size_t)L * rows * H > (size_t)rows * steps ? (size_t)L * rows * H : (size_t)rows * steps;
-    const size_t copy_blocks = (most + DB_NT - 1) / DB_NT;
-    const int copy_grid = (int)(copy_blocks < 1024 ? copy_blocks : 1024);
-    hipLaunchKernelGGL(init_batched_kernel, dim3(copy_grid), dim3(DB_NT), 0, s, p, a.tok0, a.h0, a.c0);
-    I2L_CHECK_LAUNCH();
-    const int tb_lstm = batched_tile_rows(H / 16, rows), tb_logits = batched_tile_rows(lo.Vp / DB_COLS, rows);
+    const Constraint& con = a.constraint;
+    if (con.kind != I2L_CONSTRAIN_NONE && hipMemsetAsync(con.state, 0, constraint_state_bytes(con.kind, rows), s) != hipSuccess)
+        return I2L_ERR_LAUNCH;
+    for (int m = 0; m < n; ++m) {
+        hipLaunchKernelGGL(init_batched_kernel, dim3(copy_grid[m]), dim3(DB_NT), 0, s, p[m], a.tok0, members[m].h0, members[m].c0);
+        I2L_CHECK_LAUNCH();
+    }
     for (int t = 0; t < steps; ++t) {
-        launch_batched_step(p, tb_lstm, tb_logits, t, s);
-        if (a.con.cls) launch_batched_select(p, a, a.con, t, s);
-        else if (a.arg.cls) launch_batched_select(p, a, a.arg, t, s);
-        else launch_batched_select(p, a, NoRule{}, t, s);
+        for (int m = 0; m < n; ++m) launch_batched_step(p[m], tb_lstm[m], tb_logits[m], t, s);
+        if (n > 1)
+            with_width<2, 3, 4, 5, 6, 7, 8>(n, [&](auto M) {
+                hipLaunchKernelGGL(ensemble_combine_kernel<M>, dim3(i2l_cdiv(rows, DB_NT / 64)), dim3(DB_NT), 0, s, e);
+            });
+        with_rule(con, [&](const auto& rule) { launch_batched_select(pe, a, rule, t, s); });
         I2L_CHECK_LAUNCH();
     }
-    if (a.h_out || a.c_out) {
-        hipLaunchKernelGGL(state_out_batched_kernel, dim3(copy_grid), dim3(DB_NT), 0, s, p, a.h_out, a.c_out);
-        I2L_CHECK_LAUNCH();
-    }
+    for (int m = 0; m < n; ++m)
+        if (members[m].h_out || members[m].c_out) {
+            hipLaunchKernelGGL(state_out_batched_kernel, dim3(copy_grid[m]), dim3(DB_NT), 0, s, p[m], members[m].h_out,
+                               members[m].c_out);
+            I2L_CHECK_LAUNCH();
+        }
     return I2L_OK;
 }
 }  // namespace
@@ -1280,21 +1336,21 @@ extern "C" int i2l_sample_logits(const float* logits, int ld, int rows, int voca
 }
 
 // ---------------------------------------------------------------------------------------------
-// Bracket-constrained step-batched decode (bracket_rules.inc.h, decode_constrained.inc.h): the same loop, the selection
-// kernels under ConstrainRule as the last launch of a step.  Every refusal is decided on the host, here and in
-// launch_batched, before the first HIP call; the library keeps no state -- the rows' state is the caller's buffer.
+// Constrained step-batched decode (bracket_rules.inc.h, argument_rules.inc.h, decode_constrained.inc.h): the same loop,
+// the selection kernels under ConstrainRule or ArgumentRule as the last launch of a step.  The ..._constrained entries
+// (groups nest; 16 bytes of caller-owned state per row) and the ..._arguments ones (and every command gets the arguments
+// it demands; 32 bytes) are one body each, taking the kind, with the same argument lists and the same refusals.  Every
+// refusal is decided on the host, here and in launch_batched, before the first HIP call; the library keeps no state.
 // ---------------------------------------------------------------------------------------------
-extern "C" size_t i2l_bracket_state_bytes(int rows) { return rows > 0 ? (size_t)rows * sizeof(BracketState) : 0; }
-
-extern "C" int i2l_greedy_decode_constrained(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
-                                             const int32_t* tok0, const float* h0, const float* c0, float temperature,
-                                             int select, int stop, int end_id, int32_t* ids_out, float* logits_out,
-                                             float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
-                                             uint32_t* resident_flag, uint32_t resident_value, const uint8_t* cls,
-                                             void* state, size_t state_bytes, i2l_stream_t stream) {
+namespace {
+int greedy_decode_constrained(int kind, const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                              const int32_t* tok0, const float* h0, const float* c0, float temperature, int select, int stop,
+                              int end_id, int32_t* ids_out, float* logits_out, float* h_out, float* c_out, void* scratch,
+                              size_t scratch_bytes, int flags, uint32_t* resident_flag, uint32_t resident_value,
+                              const uint8_t* cls, void* state, size_t state_bytes, i2l_stream_t stream) {
     int rc;
     if ((rc = check_weights(w)) || (rc = check_select(select)) || (rc = check_loop(rows, steps)) ||
-        (rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes)))
+        (rc = check_constraint(kind, rows, w->vocab, end_id, cls, state, state_bytes)))
         return rc;
     DecodeCall a{};
     a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
@@ -1302,9 +1358,83 @@ extern "C" int i2l_greedy_decode_constrained(const i2l_decoder_weights* w, const
     a.temperature = temperature; a.select = select; a.stop = stop; a.end_id = end_id;
     a.ids_out = ids_out; a.logits_out = logits_out; a.h_out = h_out; a.c_out = c_out;
     a.flags = flags; a.resident_flag = resident_flag; a.resident_value = resident_value; a.stream = stream;
-    a.con = ConstrainRule{cls, static_cast<BracketState*>(state), nullptr};
+    a.constraint = Constraint{kind, cls, state, nullptr};
     a.scratch = scratch; a.scratch_bytes = scratch_bytes;
     return launch_batched(a);
+}
+
+int sample_decode_constrained(int kind, const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                              const int32_t* tok0, const float* h0, const float* c0, float temperature, int top_k,
+                              float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out, float* probs_out,
+                              float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
+                              const uint8_t* cls, void* state, size_t state_bytes, i2l_stream_t stream) {
+    int rc;
+    if ((rc = check_weights(w)) || (rc = check_sample(temperature, top_k, top_p)) || (rc = check_loop(rows, steps)) ||
+        (rc = check_sample_vocab(w->vocab)) ||
+        (rc = check_constraint(kind, rows, w->vocab, end_id, cls, state, state_bytes)))
+        return rc;
+    DecodeCall a{};
+    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
+    a.tok0 = tok0; a.h0 = h0; a.c0 = c0;
+    a.temperature = temperature; a.select = I2L_SELECT_SAMPLE; a.stop = stop; a.end_id = end_id;
+    a.sample = SampleRule{top_k, top_p, (unsigned long long)seed, probs_out};
+    a.ids_out = ids_out; a.h_out = h_out; a.c_out = c_out; a.flags = flags; a.stream = stream;
+    a.constraint = Constraint{kind, cls, state, nullptr};
+    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
+    return launch_batched(a);
+}
+
+int constrained_pick_logits(int kind, const float* logits, int ld, int rows, int vocab, float temperature, int select,
+                            int top_k, float top_p, uint64_t seed, int step, int steps, const uint8_t* cls, int end_id,
+                            void* state, int32_t* ids_out, float* probs_out, uint8_t* allowed_out, i2l_stream_t stream) {
+    const bool greedy = top_k == 0 && top_p == 0.f;
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return I2L_ERR_ARG;
+    if (greedy && check_select(select)) return I2L_ERR_ARG;
+    if (rows <= 0 || vocab <= 0 || ld < vocab || step < 0 || steps <= 0 || step >= steps) return I2L_ERR_ARG;
+    if (!greedy && check_sample_vocab(vocab)) return I2L_ERR_UNSUPPORTED;
+    if (!logits || !ids_out || end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
+    const int rem = steps - step - 1;
+    with_rule(Constraint{kind, cls, state, allowed_out}, [&](const auto& rule) {
+        using Rule = std::decay_t<decltype(rule)>;
+        if constexpr (!std::is_same_v<Rule, NoRule>) {      // the kind is one of the two: no plain pick kernel exists
+            if (greedy) {
+                hipLaunchKernelGGL(pick_select_kernel<Rule>, dim3(i2l_cdiv(rows, DB_NT / 64)), dim3(DB_NT), 0, i2l_s(stream),
+                                   logits, ld, rows, vocab, temperature, use_temp(temperature), select, rule, end_id, rem,
+                                   ids_out);
+            } else {
+                const SampleRule sample{top_k, top_p, (unsigned long long)seed, probs_out};
+                hipLaunchKernelGGL(sample_logits_kernel<Rule>, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab,
+                                   temperature, use_temp(temperature), sample, (unsigned)step, rule, end_id, rem, ids_out);
+            }
+        }
+    });
+    I2L_CHECK_LAUNCH();
+    return I2L_OK;
+}
+}  // namespace
+
+extern "C" size_t i2l_bracket_state_bytes(int rows) { return constraint_state_bytes(I2L_CONSTRAIN_BRACKETS, rows); }
+extern "C" size_t i2l_argument_state_bytes(int rows) { return constraint_state_bytes(I2L_CONSTRAIN_ARGUMENTS, rows); }
+
+extern "C" int i2l_greedy_decode_constrained(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                             const int32_t* tok0, const float* h0, const float* c0, float temperature,
+                                             int select, int stop, int end_id, int32_t* ids_out, float* logits_out,
+                                             float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
+                                             uint32_t* resident_flag, uint32_t resident_value, const uint8_t* cls,
+                                             void* state, size_t state_bytes, i2l_stream_t stream) {
+    return greedy_decode_constrained(I2L_CONSTRAIN_BRACKETS, w, workspace, rows, steps, tok0, h0, c0, temperature, select, stop,
+                                     end_id, ids_out, logits_out, h_out, c_out, scratch, scratch_bytes, flags, resident_flag,
+                                     resident_value, cls, state, state_bytes, stream);
+}
+extern "C" int i2l_greedy_decode_arguments(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
+                                           const int32_t* tok0, const float* h0, const float* c0, float temperature,
+                                           int select, int stop, int end_id, int32_t* ids_out, float* logits_out,
+                                           float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
+                                           uint32_t* resident_flag, uint32_t resident_value, const uint8_t* cls,
+                                           void* state, size_t state_bytes, i2l_stream_t stream) {
+    return greedy_decode_constrained(I2L_CONSTRAIN_ARGUMENTS, w, workspace, rows, steps, tok0, h0, c0, temperature, select, stop,
+                                     end_id, ids_out, logits_out, h_out, c_out, scratch, scratch_bytes, flags, resident_flag,
+                                     resident_value, cls, state, state_bytes, stream);
 }
 
 extern "C" int i2l_sample_decode_constrained(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
@@ -1313,128 +1443,41 @@ extern "C" int i2l_sample_decode_constrained(const i2l_decoder_weights* w, const
                                              float* probs_out, float* h_out, float* c_out, void* scratch,
                                              size_t scratch_bytes, int flags, const uint8_t* cls, void* state,
                                              size_t state_bytes, i2l_stream_t stream) {
-    int rc;
-    if ((rc = check_weights(w)) || (rc = check_sample(temperature, top_k, top_p)) || (rc = check_loop(rows, steps)) ||
-        (rc = check_sample_vocab(w->vocab)) || (rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes)))
-        return rc;
-    DecodeCall a{};
-    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
-    a.tok0 = tok0; a.h0 = h0; a.c0 = c0;
-    a.temperature = temperature; a.select = I2L_SELECT_SAMPLE; a.stop = stop; a.end_id = end_id;
-    a.sample = SampleRule{top_k, top_p, (unsigned long long)seed, probs_out};
-    a.ids_out = ids_out; a.h_out = h_out; a.c_out = c_out; a.flags = flags; a.stream = stream;
-    a.con = ConstrainRule{cls, static_cast<BracketState*>(state), nullptr};
-    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
-    return launch_batched(a);
+    return sample_decode_constrained(I2L_CONSTRAIN_BRACKETS, w, workspace, rows, steps, tok0, h0, c0, temperature, top_k, top_p,
+                                     seed, stop, end_id, ids_out, probs_out, h_out, c_out, scratch, scratch_bytes, flags, cls,
+                                     state, state_bytes, stream);
 }
-
-extern "C" int i2l_constrained_pick_logits(const float* logits, int ld, int rows, int vocab, float temperature, int select,
-                                           int top_k, float top_p, uint64_t seed, int step, int steps, const uint8_t* cls,
-                                           int end_id, void* state, int32_t* ids_out, float* probs_out,
-                                           uint8_t* allowed_out, i2l_stream_t stream) {
-    const bool greedy = top_k == 0 && top_p == 0.f;
-    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return I2L_ERR_ARG;
-    if (greedy && check_select(select)) return I2L_ERR_ARG;
-    if (rows <= 0 || vocab <= 0 || ld < vocab || step < 0 || steps <= 0 || step >= steps) return I2L_ERR_ARG;
-    if (!greedy && check_sample_vocab(vocab)) return I2L_ERR_UNSUPPORTED;
-    if (!logits || !ids_out || end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
-    const ConstrainRule con{cls, static_cast<BracketState*>(state), allowed_out};
-    const int rem = steps - step - 1;
-    if (greedy) {
-        hipLaunchKernelGGL(pick_constrained_select_kernel, dim3(i2l_cdiv(rows, DB_NT / 64)), dim3(DB_NT), 0, i2l_s(stream),
-                           logits, ld, rows, vocab, temperature, use_temp(temperature), select, con, end_id, rem, ids_out);
-    } else {
-        const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
-        hipLaunchKernelGGL(sample_logits_kernel<ConstrainRule>, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab,
-                           temperature, use_temp(temperature), rule, (unsigned)step, con, end_id, rem, ids_out);
-    }
-    I2L_CHECK_LAUNCH();
-    return I2L_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Argument-complete step-batched decode (argument_rules.inc.h, decode_arguments.inc.h): the bracket-constrained entries
-// above under the stronger rule set -- every command gets the arguments it demands -- with the same argument lists and
-// the same refusals, 32 bytes of caller-owned state per row in the place of 16.
-// ---------------------------------------------------------------------------------------------
-extern "C" size_t i2l_argument_state_bytes(int rows) { return rows > 0 ? (size_t)rows * sizeof(ArgumentState) : 0; }
-
-extern "C" int i2l_greedy_decode_arguments(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
-                                           const int32_t* tok0, const float* h0, const float* c0, float temperature,
-                                           int select, int stop, int end_id, int32_t* ids_out, float* logits_out,
-                                           float* h_out, float* c_out, void* scratch, size_t scratch_bytes, int flags,
-                                           uint32_t* resident_flag, uint32_t resident_value, const uint8_t* cls,
-                                           void* state, size_t state_bytes, i2l_stream_t stream) {
-    int rc;
-    if ((rc = check_weights(w)) || (rc = check_select(select)) || (rc = check_loop(rows, steps)) ||
-        (rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes, sizeof(ArgumentState))))
-        return rc;
-    DecodeCall a{};
-    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
-    a.tok0 = tok0; a.h0 = h0; a.c0 = c0;
-    a.temperature = temperature; a.select = select; a.stop = stop; a.end_id = end_id;
-    a.ids_out = ids_out; a.logits_out = logits_out; a.h_out = h_out; a.c_out = c_out;
-    a.flags = flags; a.resident_flag = resident_flag; a.resident_value = resident_value; a.stream = stream;
-    a.arg = ArgumentRule{cls, static_cast<ArgumentState*>(state), nullptr};
-    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
-    return launch_batched(a);
-}
-
 extern "C" int i2l_sample_decode_arguments(const i2l_decoder_weights* w, const void* workspace, int rows, int steps,
                                            const int32_t* tok0, const float* h0, const float* c0, float temperature,
                                            int top_k, float top_p, uint64_t seed, int stop, int end_id, int32_t* ids_out,
                                            float* probs_out, float* h_out, float* c_out, void* scratch,
                                            size_t scratch_bytes, int flags, const uint8_t* cls, void* state,
                                            size_t state_bytes, i2l_stream_t stream) {
-    int rc;
-    if ((rc = check_weights(w)) || (rc = check_sample(temperature, top_k, top_p)) || (rc = check_loop(rows, steps)) ||
-        (rc = check_sample_vocab(w->vocab)) ||
-        (rc = check_constraint(rows, w->vocab, end_id, cls, state, state_bytes, sizeof(ArgumentState))))
-        return rc;
-    DecodeCall a{};
-    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps;
-    a.tok0 = tok0; a.h0 = h0; a.c0 = c0;
-    a.temperature = temperature; a.select = I2L_SELECT_SAMPLE; a.stop = stop; a.end_id = end_id;
-    a.sample = SampleRule{top_k, top_p, (unsigned long long)seed, probs_out};
-    a.ids_out = ids_out; a.h_out = h_out; a.c_out = c_out; a.flags = flags; a.stream = stream;
-    a.arg = ArgumentRule{cls, static_cast<ArgumentState*>(state), nullptr};
-    a.scratch = scratch; a.scratch_bytes = scratch_bytes;
-    return launch_batched(a);
+    return sample_decode_constrained(I2L_CONSTRAIN_ARGUMENTS, w, workspace, rows, steps, tok0, h0, c0, temperature, top_k, top_p,
+                                     seed, stop, end_id, ids_out, probs_out, h_out, c_out, scratch, scratch_bytes, flags, cls,
+                                     state, state_bytes, stream);
 }
 
+extern "C" int i2l_constrained_pick_logits(const float* logits, int ld, int rows, int vocab, float temperature, int select,
+                                           int top_k, float top_p, uint64_t seed, int step, int steps, const uint8_t* cls,
+                                           int end_id, void* state, int32_t* ids_out, float* probs_out,
+                                           uint8_t* allowed_out, i2l_stream_t stream) {
+    return constrained_pick_logits(I2L_CONSTRAIN_BRACKETS, logits, ld, rows, vocab, temperature, select, top_k, top_p, seed, step,
+                                   steps, cls, end_id, state, ids_out, probs_out, allowed_out, stream);
+}
 extern "C" int i2l_arguments_pick_logits(const float* logits, int ld, int rows, int vocab, float temperature, int select,
                                          int top_k, float top_p, uint64_t seed, int step, int steps, const uint8_t* cls,
                                          int end_id, void* state, int32_t* ids_out, float* probs_out,
                                          uint8_t* allowed_out, i2l_stream_t stream) {
-    const bool greedy = top_k == 0 && top_p == 0.f;
-    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return I2L_ERR_ARG;
-    if (greedy && check_select(select)) return I2L_ERR_ARG;
-    if (rows <= 0 || vocab <= 0 || ld < vocab || step < 0 || steps <= 0 || step >= steps) return I2L_ERR_ARG;
-    if (!greedy && check_sample_vocab(vocab)) return I2L_ERR_UNSUPPORTED;
-    if (!logits || !ids_out || end_id < 0 || end_id >= vocab || !cls || !state) return I2L_ERR_ARG;
-    const ArgumentRule arg{cls, static_cast<ArgumentState*>(state), allowed_out};
-    const int rem = steps - step - 1;
-    if (greedy) {
-        hipLaunchKernelGGL(pick_arguments_select_kernel, dim3(i2l_cdiv(rows, DB_NT / 64)), dim3(DB_NT), 0, i2l_s(stream),
-                           logits, ld, rows, vocab, temperature, use_temp(temperature), select, arg, end_id, rem, ids_out);
-    } else {
-        const SampleRule rule{top_k, top_p, (unsigned long long)seed, probs_out};
-        hipLaunchKernelGGL(sample_logits_kernel<ArgumentRule>, dim3(rows), dim3(NT), 0, i2l_s(stream), logits, ld, vocab,
-                           temperature, use_temp(temperature), rule, (unsigned)step, arg, end_id, rem, ids_out);
-    }
-    I2L_CHECK_LAUNCH();
-    return I2L_OK;
+    return constrained_pick_logits(I2L_CONSTRAIN_ARGUMENTS, logits, ld, rows, vocab, temperature, select, top_k, top_p, seed, step,
+                                   steps, cls, end_id, state, ids_out, probs_out, allowed_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Ensemble decode (ensemble_rules.inc.h, decode_ensemble.inc.h; this package): the step-batched loop over M decoders of
 // one vocabulary, one combine launch per step, the selection kernels above on the combined row.  Every refusal is
-// decided on the host, here and in launch_ensemble, before the first HIP call; the library keeps no state.
+// decided on the host, here and in launch_batched, before the first HIP call; the library keeps no state.
 // ---------------------------------------------------------------------------------------------
-namespace {
-#include "decode_ensemble.inc.h"
-}  // namespace
-
 extern "C" size_t i2l_ensemble_scratch_bytes(const i2l_ensemble_member* members, int n, int rows) {
     if (check_members(members, n) != I2L_OK) return 0;
     for (int m = 0; m < n; ++m)
@@ -1456,23 +1499,19 @@ extern "C" int i2l_ensemble_decode(const i2l_ensemble_member* members, int n, in
     if ((rc = check_loop(rows, steps)) || (sampling && (rc = check_sample_vocab(vocab)))) return rc;
     if (cls_kind != I2L_CONSTRAIN_NONE && cls_kind != I2L_CONSTRAIN_BRACKETS && cls_kind != I2L_CONSTRAIN_ARGUMENTS)
         return I2L_ERR_ARG;
-    if (cls_kind != I2L_CONSTRAIN_NONE &&
-        (rc = check_constraint(rows, vocab, end_id, cls, state, state_bytes,
-                               cls_kind == I2L_CONSTRAIN_ARGUMENTS ? sizeof(ArgumentState) : sizeof(BracketState))))
+    if (cls_kind != I2L_CONSTRAIN_NONE && (rc = check_constraint(cls_kind, rows, vocab, end_id, cls, state, state_bytes)))
         return rc;
     if (forced && (sampling || cls_kind != I2L_CONSTRAIN_NONE)) return I2L_ERR_ARG;
-    EnsembleCall c{};
-    c.members = members; c.n = n; c.combine = combine;
-    DecodeCall& a = c.shared;
+    DecodeCall a{};
+    a.members = members; a.n_members = n; a.combine = combine;
     a.rows = rows; a.steps = steps; a.tok0 = tok0; a.forced = forced;
     a.temperature = temperature; a.select = select; a.stop = stop; a.end_id = end_id;
     a.ids_out = ids_out; a.flags = flags; a.stream = stream;
     if (sampling) a.sample = SampleRule{top_k, top_p, (unsigned long long)seed, dist_out};
     else a.logits_out = dist_out;
-    if (cls_kind == I2L_CONSTRAIN_BRACKETS) a.con = ConstrainRule{cls, static_cast<BracketState*>(state), nullptr};
-    if (cls_kind == I2L_CONSTRAIN_ARGUMENTS) a.arg = ArgumentRule{cls, static_cast<ArgumentState*>(state), nullptr};
+    a.constraint = Constraint{cls_kind, cls, state, nullptr};
     a.scratch = scratch; a.scratch_bytes = scratch_bytes;
-    return launch_ensemble(c);
+    return launch_batched(a);
 }
 
 namespace {

@@ -129,9 +129,8 @@ __device__ __forceinline__ void commit_token_batched(const BatchedParams& p, int
 }
 
 // THE PICK POLICY of the selection kernels (the arg max here, the sampling of sample_batched.inc.h).  A kernel template
-// takes a rule as a launch argument -- NoRule, ConstrainRule (decode_constrained.inc.h) or ArgumentRule
-// (decode_arguments.inc.h) -- and rule.row(...) gives
-// each thread the policy of its row at this step:
+// takes a rule as a launch argument -- NoRule, or decode_constrained.inc.h's ConstrainRule or ArgumentRule -- and
+// rule.row(...) gives each thread the policy of its row at this step:
 //   allows(v, c), operator()(v)   may column v be picked (c = cls(v), its class byte)
 //   mask()                        where the row's allowed set is written, or null
 //   winner_cls(c, v)              in every lane of the wave: the c of the lane that owns column v (v & 63)

@@ -1,7 +1,7 @@
-// Ensemble decode on the step-batched loop (included by decode.hip inside an anonymous namespace, after launch_batched):
-// M decoders of one vocabulary read the SAME tokens, each runs its own recurrences and logits on its own state, one
-// kernel combines their rows (ensemble_rules.inc.h) and the existing selection kernels pick from the combined row.
-// (This package: the reference decodes with one model.)
+// Ensemble decode on the step-batched loop (included by decode.hip inside an anonymous namespace, before launch_batched,
+// which is the loop for one decoder and for several): M decoders of one vocabulary read the SAME tokens, each runs its
+// own recurrences and logits on its own state, one kernel combines their rows (ensemble_rules.inc.h) and the existing
+// selection kernels pick from the combined row.  (This package: the reference decodes with one model.)
 //
 //   step t:  for every member  launch_batched_step            its L LSTM launches and its logits launch, unchanged kernels
 //            ensemble_combine_kernel<M>                       the members' [B][Vp] rows -> the ensemble's [B][Vp] row
@@ -11,7 +11,8 @@
 // so a step is sum(L_m) + M + 2 launches: one more (the combine) and M - 1 fewer (the selections) than M separate
 // decodes.  tok, fin, live and ids are shared: every member's LSTM kernel reads the token the ONE selection committed,
 // and every kernel of a later step returns on the one live word under I2L_STOP_STICKY.  With M == 1 the combine is
-// skipped and the selection reads the member's own lg: the launches are launch_batched's, argument for argument.
+// skipped and the selection reads the member's own lg: a single-decoder entry's launches.  This file holds the combine
+// kernel, the ensemble's scratch layout and the check of its members.
 //
 // ensemble_combine_kernel: one wave per row (select_batched_kernel's grid and block).  The row is at most 8 x 2048
 // floats that the logits launches have just written, so the kernel is bound by the latency of its loads, not by their
@@ -85,14 +86,6 @@ __global__ __launch_bounds__(DB_NT) void ensemble_combine_kernel(EnsembleRows e)
     }
 }
 
-// What i2l_ensemble_decode asks of the loop: the members, the rule, and a DecodeCall for everything the members share
-// (rows, steps, tok0, forced, temperature, selection, stop, constraint, ids_out, the distribution out, scratch, stream).
-struct EnsembleCall {
-    const i2l_ensemble_member* members;
-    int n, combine;
-    DecodeCall shared;
-};
-
 struct EnsembleLayout {
     size_t member[ENS_MAX];      // each a batched_layout of that member's H and L
     size_t combined;             // [rows][Vp]
@@ -123,89 +116,5 @@ int check_members(const i2l_ensemble_member* members, int n) {
     }
     for (int m = 1; m < n; ++m)
         if (members[m].w->vocab != members[0].w->vocab) return I2L_ERR_ARG;
-    return I2L_OK;
-}
-
-// The loop of i2l_ensemble_decode: launch_batched's, with one BatchedParams per member and one for the selection.  The
-// entry has checked the members and its own arguments; every other refusal is decided here, before the first HIP call.
-int launch_ensemble(const EnsembleCall& c) {
-    const DecodeCall& a = c.shared;
-    const int n = c.n, rows = a.rows, steps = a.steps;
-    if (!a.tok0 || check_loop(rows, steps)) return I2L_ERR_ARG;
-    if (a.stop != I2L_STOP_NONE && a.stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
-    float weight[ENS_MAX];
-    for (int m = 0; m < n; ++m) {
-        const i2l_ensemble_member& mem = c.members[m];
-        if ((mem.h0 == nullptr) != (mem.c0 == nullptr)) return I2L_ERR_ARG;
-        if (!ens_weight_ok(mem.weight)) return I2L_ERR_ARG;
-        if (!batched_dims_ok(rows, mem.w->vocab, mem.w->hidden, mem.w->layers)) return I2L_ERR_UNSUPPORTED;
-        weight[m] = mem.weight;
-    }
-    const int V = c.members[0].w->vocab, Vp = i2l_cdiv(V, VCHUNK) * VCHUNK;
-    const EnsembleLayout el = ensemble_layout(c.members, n, rows, Vp);
-    if (!a.scratch || a.scratch_bytes < el.total) return I2L_ERR_WORKSPACE;
-
-    char* sb = static_cast<char*>(a.scratch);
-    BatchedParams p[ENS_MAX];
-    int tb_lstm[ENS_MAX], tb_logits[ENS_MAX];
-    EnsembleRows e{};
-    for (int m = 0; m < n; ++m) {
-        const i2l_decoder_weights& w = *c.members[m].w;
-        const Layout lo = make_layout(rows, V, w.embed, w.hidden, w.layers);
-        const BatchedLayout bl = batched_layout(rows, lo.Vp, w.hidden, w.layers);
-        char* mb = sb + el.member[m];
-        BatchedParams& q = p[m];
-        q = BatchedParams{};
-        q.w = step_weights(lo, static_cast<const char*>(c.members[m].workspace), V, w.hidden, w.layers);
-        q.B = rows; q.T = steps; q.genc_div = 1; q.forced = a.forced;
-        q.h = reinterpret_cast<float*>(mb + bl.h); q.c = reinterpret_cast<float*>(mb + bl.c);
-        q.lg = reinterpret_cast<float*>(mb + bl.lg);
-        // tok, fin and live are member 0's words for every member; ids and the distribution belong to the selection
-        q.tok = m ? p[0].tok : reinterpret_cast<int*>(mb + bl.tok);
-        q.fin = m ? p[0].fin : reinterpret_cast<int*>(mb + bl.fin);
-        q.live = m ? p[0].live : reinterpret_cast<unsigned*>(mb + bl.live);
-        q.temperature = a.temperature; q.use_temp = use_temp(a.temperature);
-        q.select = a.select; q.stop = a.stop; q.end_id = a.end_id;
-        tb_lstm[m] = batched_tile_rows(w.hidden / 16, rows);
-        tb_logits[m] = batched_tile_rows(lo.Vp / DB_COLS, rows);
-        e.lg[m] = q.lg; e.ld[m] = lo.Vp;
-    }
-    p[0].ids = a.ids_out; p[0].logits_out = a.logits_out;
-    BatchedParams pe = p[0];                                    // the selection's: member 0's, the combined rows for n > 1
-    if (n > 1) {
-        pe.lg = reinterpret_cast<float*>(sb + el.combined);
-        ens_normalise(weight, n, e.w, e.logw);
-        e.out = pe.lg; e.ld_out = Vp; e.B = rows; e.V = V; e.rule = c.combine; e.live = pe.live;
-    }
-
-    hipStream_t s = i2l_s(a.stream);
-    if (a.con.cls && hipMemsetAsync(a.con.state, 0, (size_t)rows * sizeof(BracketState), s) != hipSuccess) return I2L_ERR_LAUNCH;
-    if (a.arg.cls && hipMemsetAsync(a.arg.state, 0, (size_t)rows * sizeof(ArgumentState), s) != hipSuccess) return I2L_ERR_LAUNCH;
-    int copy_grid[ENS_MAX];
-    for (int m = 0; m < n; ++m) {
-        const size_t LBH = (size_t)p[m].w.L * rows * p[m].w.H, BT = (size_t)rows * steps;
-        const size_t most = LBH > BT ? LBH : BT, copy_blocks = (most + DB_NT - 1) / DB_NT;
-        copy_grid[m] = (int)(copy_blocks < 1024 ? copy_blocks : 1024);
-        hipLaunchKernelGGL(init_batched_kernel, dim3(copy_grid[m]), dim3(DB_NT), 0, s, p[m], a.tok0, c.members[m].h0,
-                           c.members[m].c0);
-        I2L_CHECK_LAUNCH();
-    }
-    for (int t = 0; t < steps; ++t) {
-        for (int m = 0; m < n; ++m) launch_batched_step(p[m], tb_lstm[m], tb_logits[m], t, s);
-        if (n > 1)
-            with_width<2, 3, 4, 5, 6, 7, 8>(n, [&](auto M) {
-                hipLaunchKernelGGL(ensemble_combine_kernel<M>, dim3(i2l_cdiv(rows, DB_NT / 64)), dim3(DB_NT), 0, s, e);
-            });
-        if (a.con.cls) launch_batched_select(pe, a, a.con, t, s);
-        else if (a.arg.cls) launch_batched_select(pe, a, a.arg, t, s);
-        else launch_batched_select(pe, a, NoRule{}, t, s);
-        I2L_CHECK_LAUNCH();
-    }
-    for (int m = 0; m < n; ++m)
-        if (c.members[m].h_out || c.members[m].c_out) {
-            hipLaunchKernelGGL(state_out_batched_kernel, dim3(copy_grid[m]), dim3(DB_NT), 0, s, p[m], c.members[m].h_out,
-                               c.members[m].c_out);
-            I2L_CHECK_LAUNCH();
-        }
     return I2L_OK;
 }

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .lstm_decoder import LSTMDecoder, _is_argument_table, _state_bytes
+from .lstm_decoder import LSTMDecoder
 from .seq2seq_model import Seq2SeqModel
 
 COMBINE = {"logprob": _lib.ENSEMBLE_LOGPROB, "prob": _lib.ENSEMBLE_PROB}
@@ -121,8 +121,8 @@ class EnsembleDecoder(nn.Module):
         kind = _lib.CONSTRAIN_NONE
         if constraint is not None:
             cls = self.members[0]._constraint_table(constraint, end_id, dev)
-            state = torch.empty(_state_bytes(constraint, rows), dtype=torch.uint8, device=dev)   # zeroed by the call
-            kind = _lib.CONSTRAIN_ARGUMENTS if _is_argument_table(constraint) else _lib.CONSTRAIN_BRACKETS
+            state = torch.empty(constraint.state_bytes(rows), dtype=torch.uint8, device=dev)   # zeroed by the call
+            kind = constraint.kind
         _lib.check(L.i2l_ensemble_decode(
             records, n, self.combine, rows, int(steps), tok0.data_ptr(), _lib.ptr(forced), float(temperature), int(select),
             int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stop), int(end_id), _lib.ptr(cls), kind,

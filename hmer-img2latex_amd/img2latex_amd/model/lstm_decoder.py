@@ -19,17 +19,6 @@ from .. import _lib
 Hidden = Tuple[torch.Tensor, torch.Tensor]
 
 
-def _is_argument_table(constraint) -> bool:
-    from ..training.constraint import ArgumentTable
-    return isinstance(constraint, ArgumentTable)
-
-
-def _state_bytes(constraint, rows: int) -> int:
-    """The rows' state of a constrained call: 16 bytes each under a BracketTable, 32 under an ArgumentTable."""
-    L = _lib.lib()
-    return (L.i2l_argument_state_bytes if _is_argument_table(constraint) else L.i2l_bracket_state_bytes)(rows)
-
-
 class Attention(nn.Module):
     """Additive attention (decoder.py:287-343).  General source length via the HIP
     kernel; inside LSTMDecoder the source length is 1 and the context equals the
@@ -259,7 +248,7 @@ class LSTMDecoder(nn.Module):
             if forced is not None:
                 raise RuntimeError("img2latex_amd: a constrained decode takes no forced tokens")
             cls, state, scratch, nbytes = self._constraint_buffers(constraint, rows, end_id, dev)
-            entry = "greedy_decode_arguments" if _is_argument_table(constraint) else "greedy_decode_constrained"
+            entry = constraint.greedy_entry
             _lib.check(getattr(_lib.lib(), "i2l_" + entry)(
                 ctypes.byref(w), ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
                 float(temperature), select, stop, int(end_id), _lib.ptr(ids), _lib.ptr(logits), _lib.ptr(h), _lib.ptr(c),
@@ -300,7 +289,7 @@ class LSTMDecoder(nn.Module):
         size) of one constrained call."""
         cls = self._constraint_table(constraint, end_id, dev)
         scratch, nbytes = self._batched_scratch(rows, dev)
-        state = torch.empty(_state_bytes(constraint, rows), dtype=torch.uint8, device=dev)   # zeroed by the call
+        state = torch.empty(constraint.state_bytes(rows), dtype=torch.uint8, device=dev)   # zeroed by the call
         return cls, state, scratch, nbytes
 
     def halves_supported(self, stop: int = _lib.STOP_NONE) -> bool:
@@ -358,7 +347,7 @@ class LSTMDecoder(nn.Module):
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         if constraint is not None:
             cls, state, scratch, nbytes = self._constraint_buffers(constraint, rows, end_id, dev)
-            entry = "sample_decode_arguments" if _is_argument_table(constraint) else "sample_decode_constrained"
+            entry = constraint.sample_entry
             _lib.check(getattr(_lib.lib(), "i2l_" + entry)(
                 ctypes.byref(w), self._ws.data_ptr(), rows, steps, tok0.data_ptr(), _lib.ptr(h0), _lib.ptr(c0),
                 float(temperature), int(top_k), float(top_p), seed, stop, int(end_id),
@@ -409,9 +398,9 @@ class LSTMDecoder(nn.Module):
                               *args, **kwargs):
         """``constrained_pick_logits`` under the argument rules (i2l_arguments_pick_logits): ``constraint`` is an
         ArgumentTable and ``state`` the rows' (rows * 32) uint8 device tensor."""
-        if not _is_argument_table(constraint):
+        if getattr(constraint, "kind", None) != _lib.CONSTRAIN_ARGUMENTS:
             raise TypeError("img2latex_amd: arguments_pick_logits needs an ArgumentTable")
-        return LSTMDecoder._pick_logits("arguments_pick_logits", logits, constraint, end_id, state, step, steps, *args,
+        return LSTMDecoder._pick_logits(constraint.pick_entry, logits, constraint, end_id, state, step, steps, *args,
                                         **kwargs)
 
     @staticmethod
@@ -419,10 +408,10 @@ class LSTMDecoder(nn.Module):
                                 *args, **kwargs):
         """Step ``step`` of ``steps`` of the bracket-constrained selection applied once to (rows, V) fp32 logits on the
         device (i2l_constrained_pick_logits); the keywords and the result are ``_pick_logits``'s."""
-        if _is_argument_table(constraint):
+        if getattr(constraint, "kind", None) != _lib.CONSTRAIN_BRACKETS:
             raise TypeError("img2latex_amd: constrained_pick_logits needs a BracketTable; arguments_pick_logits takes an "
                             "ArgumentTable")
-        return LSTMDecoder._pick_logits("constrained_pick_logits", logits, constraint, end_id, state, step, steps, *args,
+        return LSTMDecoder._pick_logits(constraint.pick_entry, logits, constraint, end_id, state, step, steps, *args,
                                         **kwargs)
 
     @staticmethod
@@ -441,9 +430,9 @@ class LSTMDecoder(nn.Module):
             raise RuntimeError(f"img2latex_amd: the constraint's table has {constraint.vocab} columns, the logits {V}")
         constraint._end(end_id)
         if state.dtype != torch.uint8 or state.device != logits.device or not state.is_contiguous() \
-                or state.numel() < _state_bytes(constraint, rows):
+                or state.numel() < constraint.state_bytes(rows):
             raise RuntimeError(f"img2latex_amd: state must be a contiguous uint8 device tensor of "
-                               f"{_state_bytes(constraint, rows)} bytes")
+                               f"{constraint.state_bytes(rows)} bytes")
         if logits.stride(1) != 1 or (rows > 1 and logits.stride(0) < V):
             logits = logits.contiguous()
         ld = max(V, logits.stride(0))

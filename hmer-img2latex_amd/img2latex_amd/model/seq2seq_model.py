@@ -253,8 +253,7 @@ class Seq2SeqModel(nn.Module):
         renormalised over them, so every hypothesis nests its groups, ends on END (``finished`` is always True) and its
         score is its log-probability under the constrained model.  ``nbest=1`` gives the single best one.  An
         ArgumentTable is refused: the beam entry reads bracket class bytes and would misread its bytes."""
-        from ..training.constraint import ArgumentTable
-        if isinstance(constraint, ArgumentTable):
+        if constraint is not None and constraint.kind != _lib.CONSTRAIN_BRACKETS:
             raise RuntimeError("img2latex_amd: the argument rules exist for the greedy and sampling decode only; the N-best "
                                "beam search takes a BracketTable (well_formed=True)")
         nbest = int(beam_size if nbest is None else nbest)

@@ -26,6 +26,8 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from .. import _lib
+
 NEUTRAL, NEVER = 0, 255
 KINDS, MAX_DEPTH = 4, 32
 KIND_BRACE, KIND_LEFT_RIGHT, KIND_ENVIRONMENT = 0, 1, 2
@@ -95,8 +97,79 @@ def classify_token(token: str) -> int:
     return NEUTRAL
 
 
-class BracketTable:
+class ConstraintTable:
+    """What the rule sets' tables share: the bytes on the device and the replay of the constrained greedy rule.  A table
+    names ``kind`` (I2L_CONSTRAIN_*), ``state_class`` and ``STATE_BYTES`` (the state of one row), ``table_bytes`` (uint8,
+    one per column: what the kernels read), the library's ``greedy_entry`` / ``sample_entry`` / ``pick_entry``, and restates
+    its rule set as ``rules`` and ``advance`` -- which the host tests compare with the C++."""
+    _unit = "byte"                                                    # what the END column's message calls a table entry
+
+    @property
+    def vocab(self) -> int:
+        return int(self.table_bytes.size)
+
+    def state_bytes(self, rows: int) -> int:
+        """The size of the rows' state buffer of a constrained call (i2l_bracket_state_bytes / i2l_argument_state_bytes)."""
+        return max(int(rows), 0) * self.STATE_BYTES
+
+    def device(self, dev):
+        """The table bytes on ``dev`` (uint8, V), uploaded once per device."""
+        import torch
+        dev = torch.device(dev)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if dev not in self._device:
+            self._device[dev] = torch.from_numpy(self.table_bytes.copy()).to(dev)
+        return self._device[dev]
+
+    def _end(self, end_id: Optional[int]) -> int:
+        end = self.end_id if end_id is None else int(end_id)
+        if end is None or not 0 <= end < self.vocab:
+            raise ValueError("img2latex_amd: the constraint needs an end_id inside the table")
+        if self.table_bytes[end] != NEUTRAL:
+            raise ValueError(f"img2latex_amd: the END column's {self._unit} must be 0: END is named by the call, not the table")
+        return end
+
+    def allowed(self, state, end_id: int, rem: int) -> np.ndarray:
+        return (self.rules(state, end_id, rem) == RULE_OK).astype(np.uint8)
+
+    def pick(self, logits: np.ndarray, mask: np.ndarray, end_id: int) -> int:
+        """The first-index arg max of ``logits`` over the columns ``mask`` allows; without one above -inf the first
+        allowed column, else ``end_id``."""
+        x = np.asarray(logits, dtype=np.float32)
+        x = np.where(mask.astype(bool) & ~np.isnan(x), x, -np.inf)   # the kernel's `a > best` is false for a NaN
+        if (x > -np.inf).any():
+            return int(np.argmax(x))
+        on = np.flatnonzero(mask)
+        return int(on[0]) if on.size else int(end_id)
+
+    def replay(self, logits_per_step, end_id: Optional[int] = None, steps: Optional[int] = None, state=None,
+               first_step: int = 0) -> List[dict]:
+        """The constrained greedy rule (temperature 1, arg max of the logits) over one row's logits, step by step:
+        ``logits_per_step`` is (n, V).  Returns per step ``{"id", "allowed" (V uint8), "state" (the table's state class,
+        after the pick), "free" (the unconstrained arg max), "rule" (the rule that forbade ``free``, 0 when it was
+        allowed)}``.  ``steps`` is the decode's length (default n); ``state`` / ``first_step`` continue an earlier replay."""
+        x = np.asarray(logits_per_step, dtype=np.float32)
+        end = self._end(end_id)
+        steps = x.shape[0] + first_step if steps is None else int(steps)
+        st = self.state_class() if state is None else state.copy()
+        out = []
+        for i in range(x.shape[0]):
+            rem = steps - (first_step + i) - 1
+            rules = self.rules(st, end, rem)
+            mask = (rules == RULE_OK).astype(np.uint8)
+            free = int(np.argmax(x[i]))
+            pick = self.pick(x[i], mask, end)
+            self.advance(st, pick, end)
+            out.append({"id": pick, "allowed": mask, "state": st.copy(), "free": free, "rule": int(rules[free])})
+        return out
+
+
+class BracketTable(ConstraintTable):
     """``classes``: one value per vocabulary column, 0..8 or 255 (anything else is stored as 255)."""
+    kind, state_class, STATE_BYTES, _unit = _lib.CONSTRAIN_BRACKETS, BracketState, STATE_BYTES, "class"
+    greedy_entry, sample_entry, pick_entry = "greedy_decode_constrained", "sample_decode_constrained", "constrained_pick_logits"
+    table_bytes = property(lambda self: self.classes)
 
     def __init__(self, classes: Sequence[int], end_id: Optional[int] = None, unclosable: Sequence[str] = ()):
         cls = np.asarray(classes, dtype=np.int64).reshape(-1)
@@ -111,10 +184,6 @@ class BracketTable:
         self.end_id = None if end_id is None else int(end_id)
         self.unclosable = list(unclosable)
         self._device: Dict = {}
-
-    @property
-    def vocab(self) -> int:
-        return int(self.classes.size)
 
     @classmethod
     def from_tokenizer(cls, tokenizer) -> "BracketTable":
@@ -140,24 +209,6 @@ class BracketTable:
                     classes[i] = NEVER
         return cls(classes, end, unclosable)
 
-    def device(self, dev):
-        """The class bytes on ``dev`` (uint8, V), uploaded once per device."""
-        import torch
-        dev = torch.device(dev)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if dev not in self._device:
-            self._device[dev] = torch.from_numpy(self.classes.copy()).to(dev)
-        return self._device[dev]
-
-    def _end(self, end_id: Optional[int]) -> int:
-        end = self.end_id if end_id is None else int(end_id)
-        if end is None or not 0 <= end < self.vocab:
-            raise ValueError("img2latex_amd: the constraint needs an end_id inside the table")
-        if self.classes[end] != NEUTRAL:
-            raise ValueError("img2latex_amd: the END column's class must be 0: END is named by the call, not the table")
-        return end
-
     # ------------------------------------------------------------------ the host restatement of bracket_rules.inc.h
     def rules(self, state: BracketState, end_id: int, rem: int) -> np.ndarray:
         """(V) uint8: per column the rule that forbids it at ``rem`` emissions left after this one, 0 = allowed."""
@@ -181,9 +232,6 @@ class BracketTable:
         out[end_id] = RULE_OK if d == 0 else RULE_END_INSIDE
         return out
 
-    def allowed(self, state: BracketState, end_id: int, rem: int) -> np.ndarray:
-        return (self.rules(state, end_id, rem) == RULE_OK).astype(np.uint8)
-
     def advance(self, state: BracketState, pick: int, end_id: int) -> None:
         if state.ended:
             return
@@ -197,16 +245,6 @@ class BracketTable:
         elif KINDS < k <= 2 * KINDS and state.depth > 0:
             state.depth -= 1
             state.stack &= ~(3 << (2 * state.depth))
-
-    def pick(self, logits: np.ndarray, mask: np.ndarray, end_id: int) -> int:
-        """The first-index arg max of ``logits`` over the columns ``mask`` allows; without one above -inf the first
-        allowed column, else ``end_id``."""
-        x = np.asarray(logits, dtype=np.float32)
-        x = np.where(mask.astype(bool) & ~np.isnan(x), x, -np.inf)   # the kernel's `a > best` is false for a NaN
-        if (x > -np.inf).any():
-            return int(np.argmax(x))
-        on = np.flatnonzero(mask)
-        return int(on[0]) if on.size else int(end_id)
 
     def candidates(self, state: BracketState, row, end_id: int, rem: int, beam: int, logits: bool = False):
         """The slot policy of the well-formed beam search (csrc/beam_bracket_rules.inc.h): the candidates of a live slot
@@ -228,27 +266,6 @@ class BracketTable:
         order = np.argsort(-sel, kind="stable")[:int(beam)]
         out = [(int(v), float(lp[v])) for v in order if sel[v] > -np.inf]
         return out if out else [(int(end_id), 0.0)]
-
-    def replay(self, logits_per_step, end_id: Optional[int] = None, steps: Optional[int] = None,
-               state: Optional[BracketState] = None, first_step: int = 0) -> List[dict]:
-        """The constrained greedy rule (temperature 1, arg max of the logits) over one row's logits, step by step:
-        ``logits_per_step`` is (n, V).  Returns per step ``{"id", "allowed" (V uint8), "state" (BracketState after the
-        pick), "free" (the unconstrained arg max), "rule" (the rule that forbade ``free``, 0 when it was allowed)}``.
-        ``steps`` is the decode's length (default n); ``state`` / ``first_step`` continue an earlier replay."""
-        x = np.asarray(logits_per_step, dtype=np.float32)
-        end = self._end(end_id)
-        steps = x.shape[0] + first_step if steps is None else int(steps)
-        st = BracketState() if state is None else state.copy()
-        out = []
-        for i in range(x.shape[0]):
-            rem = steps - (first_step + i) - 1
-            rules = self.rules(st, end, rem)
-            mask = (rules == RULE_OK).astype(np.uint8)
-            free = int(np.argmax(x[i]))
-            pick = self.pick(x[i], mask, end)
-            self.advance(st, pick, end)
-            out.append({"id": pick, "allowed": mask, "state": st.copy(), "free": free, "rule": int(rules[free])})
-        return out
 
     def well_formed(self, ids: Sequence[int], end_id: Optional[int] = None) -> bool:
         """``ids`` (START not included) reach END -- ids behind it, and the sticky stop's -1 filler, are not looked at --
@@ -347,7 +364,7 @@ class ArgumentState:
                 f"depth={self.depth}, owed={self.owed}, ended={self.ended})")
 
 
-class ArgumentTable:
+class ArgumentTable(ConstraintTable):
     """``table``: one byte per vocabulary column -- bits 0..3 the bracket class (0..8), bits 4..5 the number of arguments
     the column demands, bit 6 loose (each argument a brace group or one plain token; without it a brace group).  A byte
     that is not valid (csrc/argument_rules.inc.h) is stored as 255, never emitted.  The table must be able to discharge
@@ -359,6 +376,10 @@ class ArgumentTable:
     present -- a brace group where strict, a group or one plain token where loose.  What it does not: double scripts
     (``x ^ a ^ b``), that a loose single-token argument is a sensible one (``^ &``), delimiter tokens after a bare
     ``\\left``, environment names matching, or anything about meaning."""
+
+    kind, state_class, STATE_BYTES = _lib.CONSTRAIN_ARGUMENTS, ArgumentState, ARGUMENT_STATE_BYTES
+    greedy_entry, sample_entry, pick_entry = "greedy_decode_arguments", "sample_decode_arguments", "arguments_pick_logits"
+    table_bytes = property(lambda self: self.table)
 
     def __init__(self, table: Sequence[int], end_id: Optional[int] = None, unclosable: Sequence[str] = (),
                  unsatisfiable: Sequence[str] = ()):
@@ -397,10 +418,6 @@ class ArgumentTable:
         if ((self.counts > 0) & self.loose).any() and not self.plain.any():
             out.append("a loose argument needs a plain token")
         return out
-
-    @property
-    def vocab(self) -> int:
-        return int(self.table.size)
 
     @classmethod
     def from_brackets(cls, bracket_table: BracketTable, arguments_by_column: Dict[int, tuple],
@@ -441,24 +458,6 @@ class ArgumentTable:
         names = {int(i): tok for i, tok in tokenizer.id_to_token.items()}
         by_column = {i: arguments[tok] for i, tok in names.items() if i >= 0 and i not in special and tok in arguments}
         return cls.from_brackets(brackets, by_column, names)
-
-    def device(self, dev):
-        """The table bytes on ``dev`` (uint8, V), uploaded once per device."""
-        import torch
-        dev = torch.device(dev)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if dev not in self._device:
-            self._device[dev] = torch.from_numpy(self.table.copy()).to(dev)
-        return self._device[dev]
-
-    def _end(self, end_id: Optional[int]) -> int:
-        end = self.end_id if end_id is None else int(end_id)
-        if end is None or not 0 <= end < self.vocab:
-            raise ValueError("img2latex_amd: the constraint needs an end_id inside the table")
-        if self.table[end] != NEUTRAL:
-            raise ValueError("img2latex_amd: the END column's byte must be 0: END is named by the call, not the table")
-        return end
 
     # ------------------------------------------------------------------ the host restatement of argument_rules.inc.h
     def rules(self, state: ArgumentState, end_id: int, rem: int) -> np.ndarray:
@@ -502,9 +501,6 @@ class ArgumentTable:
         out[end_id] = RULE_OK if d == 0 else RULE_END_INSIDE
         return out
 
-    def allowed(self, state: ArgumentState, end_id: int, rem: int) -> np.ndarray:
-        return (self.rules(state, end_id, rem) == RULE_OK).astype(np.uint8)
-
     def advance(self, state: ArgumentState, pick: int, end_id: int) -> None:
         if state.ended:
             return
@@ -528,27 +524,6 @@ class ArgumentTable:
             state.pending = (state.pending & ~(3 << (2 * d))) | n << (2 * d)
             state.loose = (state.loose & ~(1 << d)) | int(self.loose[pick]) << d
             state.owed += int(self.weights[pick])
-
-    pick = BracketTable.pick
-
-    def replay(self, logits_per_step, end_id: Optional[int] = None, steps: Optional[int] = None,
-               state: Optional[ArgumentState] = None, first_step: int = 0) -> List[dict]:
-        """``BracketTable.replay`` under the argument rules: per step ``{"id", "allowed", "state" (ArgumentState after the
-        pick), "free", "rule"}``."""
-        x = np.asarray(logits_per_step, dtype=np.float32)
-        end = self._end(end_id)
-        steps = x.shape[0] + first_step if steps is None else int(steps)
-        st = ArgumentState() if state is None else state.copy()
-        out = []
-        for i in range(x.shape[0]):
-            rem = steps - (first_step + i) - 1
-            rules = self.rules(st, end, rem)
-            mask = (rules == RULE_OK).astype(np.uint8)
-            free = int(np.argmax(x[i]))
-            pick = self.pick(x[i], mask, end)
-            self.advance(st, pick, end)
-            out.append({"id": pick, "allowed": mask, "state": st.copy(), "free": free, "rule": int(rules[free])})
-        return out
 
     def enumerate(self, steps: int, end_id: Optional[int] = None) -> List[tuple]:
         """Every sequence (END last) the rules allow within ``steps``, in lexicographic order of the ids -- what the host
@@ -629,7 +604,7 @@ def as_table(constraint, tokenizer=None):
     an ArgumentTable -> itself."""
     if constraint is None or constraint is False:
         return None
-    if isinstance(constraint, (BracketTable, ArgumentTable)):
+    if isinstance(constraint, ConstraintTable):
         return constraint
     if constraint is True and tokenizer is not None:
         return _cached(_TABLES, tokenizer, BracketTable.from_tokenizer)

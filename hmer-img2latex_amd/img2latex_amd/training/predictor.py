@@ -813,8 +813,7 @@ class Predictor:
         well-formed search, every hypothesis nesting its groups and ending on END (None: the predictor's own setting)."""
         self._single_model("predict_batch_nbest")
         constraint = self._constraint(well_formed)
-        from .constraint import ArgumentTable
-        if isinstance(constraint, ArgumentTable):
+        if constraint is not None and constraint.kind != _lib.CONSTRAIN_BRACKETS:
             raise RuntimeError("img2latex_amd: the argument rules exist for the greedy and sampling decode only; the N-best "
                                "beam search takes well_formed=True")
         if isinstance(images, torch.Tensor):

@@ -176,12 +176,13 @@ def steps_run(ids, stop):
 def test_one_member_is_the_single_model_call(rows):
     m, _, _ = build(DEEP, seed=55)
     one = m.decoder
-    brackets = BracketTable(loop_table(DEEP[0]).classes, END)
+    arguments = loop_table(DEEP[0])
+    brackets = BracketTable(arguments.classes, END)
     enc = encs_of("b", rows)[1]
     sample = (0.9, 5, 0.9, 4711)
     for rule in RULES:
         dec = EnsembleDecoder([one], [3.0], rule)
-        for table in (None, brackets):
+        for table in (None, brackets, arguments):
             for stop in (_lib.STOP_NONE, _lib.STOP_STICKY):
                 kw = dict(stop=stop, end_id=END, select=_lib.SELECT_SOFTMAX, temperature=0.8, want_logits=True,
                           want_state=True, constraint=table)
