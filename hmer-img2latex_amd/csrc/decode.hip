@@ -285,6 +285,8 @@ __device__ __forceinline__ int beam_topk_row(const float* x, int V, int K, int l
 #include "beam_group.inc.h"
 #include "decode_batched.inc.h"
 #include "sample_batched.inc.h"
+#include "sample_rank_rules.inc.h"
+#include "sample_rank.inc.h"
 #include "argument_rules.inc.h"      // and bracket_rules.inc.h
 #include "decode_constrained.inc.h"
 #include "beam_bracket_rules.inc.h"
@@ -858,6 +860,7 @@ struct DecodeCall {
     const i2l_decoder_weights* w;
     const void* workspace;
     int rows, steps;
+    int samples;                       // launch_batched: > 1: `samples` consecutive rows share an encoder row and a tok0 entry
     const int32_t *tok0, *forced;
     const float *h0, *c0;
     float temperature;
@@ -1182,7 +1185,9 @@ void launch_batched_step(const BatchedParams& p, int tb_lstm, int tb_logits, int
 // the last launch of a step: the arg max, or the draw when the call samples, under the rule's pick policy
 template <class Rule>
 void launch_batched_select(const BatchedParams& p, const DecodeCall& a, const Rule& rule, int t, hipStream_t s) {
-    if (a.select == I2L_SELECT_SAMPLE)
+    if (a.select == I2L_SELECT_SAMPLE && a.sample.score)
+        hipLaunchKernelGGL((sample_batched_kernel<Rule, true>), dim3(p.B), dim3(NT), 0, s, p, a.sample, rule, t);
+    else if (a.select == I2L_SELECT_SAMPLE)
         hipLaunchKernelGGL(sample_batched_kernel<Rule>, dim3(p.B), dim3(NT), 0, s, p, a.sample, rule, t);
     else
         hipLaunchKernelGGL(select_batched_kernel<Rule>, dim3(i2l_cdiv(p.B, DB_NT / 64)), dim3(DB_NT), 0, s, p, rule, t);
@@ -1200,6 +1205,7 @@ int launch_batched(const DecodeCall& a) {
     const i2l_ensemble_member self{a.w, a.workspace, a.h0, a.c0, a.h_out, a.c_out, 1.f};
     const i2l_ensemble_member* members = a.members ? a.members : &self;
     const int n = a.members ? a.n_members : 1, rows = a.rows, steps = a.steps;
+    const int per = a.samples > 1 ? a.samples : 1;              // rows of one encoder row (the workspace's: rows / per)
     if (!a.tok0 || check_loop(rows, steps)) return I2L_ERR_ARG;
     if (a.stop != I2L_STOP_NONE && a.stop != I2L_STOP_STICKY) return I2L_ERR_ARG;
     float weight[ENS_MAX];
@@ -1218,13 +1224,13 @@ int launch_batched(const DecodeCall& a) {
     EnsembleRows e{};
     for (int m = 0; m < n; ++m) {
         const i2l_decoder_weights& w = *members[m].w;
-        const Layout lo = make_layout(rows, V, w.embed, w.hidden, w.layers);
+        const Layout lo = make_layout(rows / per, V, w.embed, w.hidden, w.layers);
         const BatchedLayout bl = batched_layout(rows, Vp, w.hidden, w.layers);
         char* mb = sb + el.member[m];
         BatchedParams& q = p[m];
         q = BatchedParams{};
         q.w = step_weights(lo, static_cast<const char*>(members[m].workspace), V, w.hidden, w.layers);
-        q.B = rows; q.T = steps; q.genc_div = 1; q.forced = a.forced;
+        q.B = rows; q.T = steps; q.genc_div = per; q.forced = a.forced;
         q.h = reinterpret_cast<float*>(mb + bl.h); q.c = reinterpret_cast<float*>(mb + bl.c);
         q.lg = reinterpret_cast<float*>(mb + bl.lg);
         // tok, fin and live are member 0's words for every member; ids and the distribution belong to the selection
@@ -1512,6 +1518,105 @@ extern "C" int i2l_ensemble_decode(const i2l_ensemble_member* members, int n, in
     a.constraint = Constraint{cls_kind, cls, state, nullptr};
     a.scratch = scratch; a.scratch_bytes = scratch_bytes;
     return launch_batched(a);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Consensus decode (sample_rank_rules.inc.h, sample_rank.inc.h): images * samples rows of the step-batched sampling loop
+// on the workspace of `images` rows, the sequence score kept by sample_batched_kernel<Rule, true>, then the two ranking
+// launches.  Every refusal is decided on the host, here and in launch_batched, before the first HIP call.
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct MultiLayout {
+    size_t loop, state, total;      // batched_layout of the rows | their constraint states
+};
+MultiLayout multi_layout(int rows, int Vp, int H, int L, int kind) {
+    MultiLayout o{};
+    o.loop = 0;
+    o.state = i2l_align(batched_layout(rows, Vp, H, L).total);
+    o.total = o.state + (kind == I2L_CONSTRAIN_NONE ? 0 : i2l_align(constraint_state_bytes(kind, rows)));
+    return o;
+}
+inline int check_rank_dims(int images, int samples, int steps, int rank) {
+    if (images <= 0 || samples <= 0 || steps <= 0) return I2L_ERR_ARG;
+    if (rank != I2L_RANK_CONSENSUS && rank != I2L_RANK_LOGPROB) return I2L_ERR_ARG;
+    if (samples > I2L_MAX_NBEST || steps > I2L_MAX_RANK_STEPS) return I2L_ERR_UNSUPPORTED;
+    if ((long long)images * samples > 0x7fffffffll / steps) return I2L_ERR_UNSUPPORTED;
+    return I2L_OK;
+}
+inline bool constrain_kind_ok(int kind) {
+    return kind == I2L_CONSTRAIN_NONE || kind == I2L_CONSTRAIN_BRACKETS || kind == I2L_CONSTRAIN_ARGUMENTS;
+}
+// the two ranking launches; arguments already checked
+int launch_sample_rank(const RankParams& p, hipStream_t s) {
+    const dim3 grid(p.images, p.samples), block(64 * p.samples);
+    const bool took = with_width<1, 2, 3, 4, 8, 16>(p.steps <= 256 ? i2l_cdiv(p.steps, 64) : p.steps <= 512 ? 8 : 16, [&](auto w) {
+        hipLaunchKernelGGL(sample_distance_kernel<w>, grid, block, 0, s, p);
+    });
+    if (!took) return I2L_ERR_UNSUPPORTED;
+    I2L_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sample_order_kernel, dim3(p.images), dim3(64), 0, s, p);
+    I2L_CHECK_LAUNCH();
+    return I2L_OK;
+}
+}  // namespace
+
+extern "C" size_t i2l_sample_multi_scratch_bytes(int images, int samples, int vocab, int hidden, int layers, int steps,
+                                                 int constrain_kind) {
+    if (check_rank_dims(images, samples, steps, I2L_RANK_CONSENSUS) != I2L_OK || !constrain_kind_ok(constrain_kind)) return 0;
+    if (!batched_dims_ok(images * samples, vocab, hidden, layers) || check_sample_vocab(vocab) != I2L_OK) return 0;
+    return multi_layout(images * samples, i2l_cdiv(vocab, VCHUNK) * VCHUNK, hidden, layers, constrain_kind).total;
+}
+
+extern "C" int i2l_sample_decode_multi(const i2l_decoder_weights* w, const void* workspace, int images, int samples,
+                                       int steps, const int32_t* tok0, float temperature, int top_k, float top_p,
+                                       uint64_t seed, int end_id, int constrain_kind, const uint8_t* cls, int rank,
+                                       const double* length_norm, void* scratch, size_t scratch_bytes, int32_t* ids_out,
+                                       int32_t* len_out, int32_t* finished_out, double* score_out, int32_t* risk_out,
+                                       double* key_out, int32_t* order_out, int flags, i2l_stream_t stream) {
+    int rc;
+    if ((rc = check_weights(w)) || (rc = check_sample(temperature, top_k, top_p)) ||
+        (rc = check_rank_dims(images, samples, steps, rank)) || (rc = check_sample_vocab(w->vocab)))
+        return rc;
+    if (!constrain_kind_ok(constrain_kind)) return I2L_ERR_ARG;
+    if (!workspace || !tok0 || !ids_out || !len_out || !finished_out || !score_out || !risk_out || !key_out || !order_out)
+        return I2L_ERR_ARG;
+    const int rows = images * samples, V = w->vocab;
+    if (constrain_kind != I2L_CONSTRAIN_NONE && (end_id < 0 || end_id >= V || !cls)) return I2L_ERR_ARG;
+    const MultiLayout ml = multi_layout(rows, i2l_cdiv(V, VCHUNK) * VCHUNK, w->hidden, w->layers, constrain_kind);
+    if (!scratch || scratch_bytes < ml.total) return I2L_ERR_WORKSPACE;
+    char* sb = static_cast<char*>(scratch);
+    hipStream_t s = i2l_s(stream);
+
+    DecodeCall a{};
+    a.w = w; a.workspace = workspace; a.rows = rows; a.steps = steps; a.samples = samples;
+    a.tok0 = tok0;
+    a.temperature = temperature; a.select = I2L_SELECT_SAMPLE; a.stop = I2L_STOP_STICKY; a.end_id = end_id;
+    a.sample = SampleRule{top_k, top_p, (unsigned long long)seed, nullptr, score_out};
+    a.ids_out = ids_out; a.flags = flags; a.stream = stream;
+    if (constrain_kind != I2L_CONSTRAIN_NONE) a.constraint = Constraint{constrain_kind, cls, sb + ml.state, nullptr};
+    a.scratch = sb + ml.loop; a.scratch_bytes = ml.state;
+    if (hipMemsetAsync(score_out, 0, (size_t)rows * sizeof(double), s) != hipSuccess) return I2L_ERR_LAUNCH;
+    if ((rc = launch_batched(a))) return rc;
+
+    RankParams p{};
+    p.ids = ids_out; p.images = images; p.samples = samples; p.steps = steps; p.end_id = end_id; p.rank = rank;
+    p.score = score_out; p.norm = length_norm;
+    p.len = len_out; p.fin = finished_out; p.risk = risk_out; p.key = key_out; p.order = order_out;
+    return launch_sample_rank(p, s);
+}
+
+extern "C" int i2l_sample_rank(const int32_t* ids, int images, int samples, int steps, int end_id, const double* score,
+                               int rank, const double* length_norm, int32_t* len_out, int32_t* finished_out,
+                               int32_t* risk_out, double* key_out, int32_t* order_out, int32_t* dist_out,
+                               i2l_stream_t stream) {
+    int rc;
+    if ((rc = check_rank_dims(images, samples, steps, rank))) return rc;
+    if (!ids || !score || !len_out || !finished_out || !risk_out || !key_out || !order_out) return I2L_ERR_ARG;
+    RankParams p{};
+    p.ids = ids; p.images = images; p.samples = samples; p.steps = steps; p.end_id = end_id; p.rank = rank;
+    p.score = score; p.norm = length_norm;
+    p.len = len_out; p.fin = finished_out; p.risk = risk_out; p.key = key_out; p.order = order_out; p.dist = dist_out;
+    return launch_sample_rank(p, i2l_s(stream));
 }
 
 namespace {

@@ -25,7 +25,8 @@
 struct BatchedParams {
     StepWeights w;
     int B, T;
-    int genc_div;        // row r reads Genc row r / genc_div: 1, or the beam width (beam_batched.inc.h: K rows per image)
+    int genc_div;        // row r reads Genc row r / genc_div: 1, the beam width (beam_batched.inc.h: K rows per image) or
+                         // the samples of an image (i2l_sample_decode_multi), which then share tok0[r / genc_div] too
     const int32_t* forced;
     float* h;            // [2][L][B][H]
     float* c;            // [L][B][H]
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(DB_NT) void init_batched_kernel(BatchedParams p, co
     }
     if (p.ids)
         for (size_t i = i0; i < BT; i += stride) p.ids[i] = -1;
-    for (size_t i = i0; i < (size_t)p.B; i += stride) { p.tok[i] = tok0[i]; p.fin[i] = 0; }
+    for (size_t i = i0; i < (size_t)p.B; i += stride) { p.tok[i] = tok0[i / p.genc_div]; p.fin[i] = 0; }
     if (i0 == 0) *p.live = (unsigned)p.B;
 }
 

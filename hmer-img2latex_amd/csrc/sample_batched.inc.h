@@ -6,7 +6,8 @@
 //                         of the k-th largest probability (four 8-bit digits of the bit pattern, a 256-bin count each),
 //                         the top-p mask from a BITONIC SORT of (bit pattern, index) keys and a scan of the sorted
 //                         masses, the draw from a scan of the final distribution in index order.
-//   sample_batched_kernel<Rule>  the last launch of a step of i2l_sample_decode_batched, in select_batched_kernel's place.
+//   sample_batched_kernel<Rule>  the last launch of a step of i2l_sample_decode_batched, in select_batched_kernel's place;
+//                         <Rule, true> also keeps the row's sequence score (i2l_sample_decode_multi).
 //   sample_logits_kernel<Rule>   the same row function over a caller's logits (i2l_sample_logits).
 // Rule is NoRule or ConstrainRule: the pick policy of decode_batched.inc.h, which sample_row takes as `allow`.
 //
@@ -30,6 +31,7 @@ struct SampleRule {
     float top_p;
     unsigned long long seed;
     float* probs;        // (B, T, V) or null
+    double* score;       // [B] sequence log-probability (sample_batched_kernel<Rule, true> only), or null
 };
 
 struct SampleLds {
@@ -139,11 +141,12 @@ __device__ __forceinline__ void bitonic_desc(unsigned long long* key, int N, int
 // One row: x[0, V) raw logits, u the row's uniform of this step.  Every thread returns the pick; po (V floats or null)
 // receives the final distribution.  V <= SB_MAXV, blockDim.x == NT.  A column v with !allow(v) enters as -INFINITY: its
 // probability is exactly 0 and the others renormalise (decode_constrained.inc.h); the result is 0x7fffffff or a
-// disallowed column only when no allowed column holds a finite logit.
+// disallowed column only when no allowed column holds a finite logit.  lse (two floats of the caller's, or null) receives
+// the maximum and the sum of exp(. - maximum) of the scaled logits over the allowed columns, as the softmax took them.
 template <class Allow>
 __device__ __forceinline__ int sample_row(const float* __restrict__ x, int V, float temperature, int use_temp, int top_k,
                                           float top_p, float u, float* __restrict__ po, SampleLds& s, int tid,
-                                          const Allow& allow) {
+                                          const Allow& allow, float* lse = nullptr) {
     float best[1] = {-INFINITY};
     int besti[1] = {0x7fffffff};
     for (int v = tid; v < V; v += NT) {
@@ -157,6 +160,7 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ x, int V, fl
     float sm = 0.f;
     for (int v = tid; v < V; v += NT) sm += expf(s.q[v] - best[0]);
     sm = block_sum(sm, s.redv, tid);
+    if (lse) { lse[0] = best[0]; lse[1] = sm; }
     for (int v = tid; v < V; v += NT) s.q[v] = expf(s.q[v] - best[0]) / sm;
     __syncthreads();
     if (top_k > 0) {
@@ -214,15 +218,48 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ x, int V, fl
 
 // Token selection of step t by sampling, one workgroup per row, under NoRule or ConstrainRule.  ids, next token, finished
 // rows and the live-row count as select_batched_kernel.
-template <class Rule>
+//
+// Score (i2l_sample_decode_multi): a row that has not finished adds the log-probability of the token it commits to
+// r.score[row] -- beam_topk_row's convention and formula, (x[pick] - m) - logf(sum expf(x - m)) in fp32 over the RAW
+// logits of the columns the policy allows, so that a sample and a beam hypothesis of the same tokens carry comparable
+// scores.  No temperature, no truncation; a pick the policy does not allow is the constraint's fallback and adds 0.
+// At temperature 1 m and the sum are the ones sample_row's softmax has just taken (the same terms, summed by its tree);
+// otherwise wave 0 takes them from the raw logits in beam_topk_row's lane order.  Thread 0 reads the row's finished
+// mark and its score before sample_row, so that only the store is left behind the pick.  A template parameter, so that
+// <Rule, false> is the kernel as it was.
+template <class Rule, bool Score = false>
 __global__ __launch_bounds__(NT) void sample_batched_kernel(BatchedParams p, SampleRule r, Rule c, int t) {
     __shared__ SampleLds s;
     if (*p.live == 0) return;
     const int V = p.w.V, row = blockIdx.x, tid = threadIdx.x;
     const auto al = c.row(row, V, p.end_id, p.T - t - 1);
     float* po = r.probs ? r.probs + ((size_t)row * p.T + t) * V : nullptr;
+    [[maybe_unused]] int scoring = 0;
+    [[maybe_unused]] double acc = 0.0;
+    [[maybe_unused]] float lse[2] = {0.f, 1.f};
+    if constexpr (Score) {
+        scoring = !p.fin[row];                  // thread 0 commits behind the pick, so this is still the last step's
+        if (tid == 0) acc = r.score[row];
+    }
     const int pick = sample_row(p.lg + (size_t)row * p.w.Vp, V, p.temperature, p.use_temp, r.top_k, r.top_p,
-                                uniform01(r.seed, (unsigned)row, (unsigned)t), po, s, tid, al);
+                                uniform01(r.seed, (unsigned)row, (unsigned)t), po, s, tid, al, Score ? lse : nullptr);
+    if constexpr (Score) {
+        if (scoring && tid < 64) {              // wave 0
+            const float* x = p.lg + (size_t)row * p.w.Vp;
+            if (p.use_temp) {
+                float m = -INFINITY;
+                for (int v = tid; v < V; v += 64)
+                    if (al(v)) m = fmaxf(m, x[v]);
+                m = wave_max(m);
+                float sum = 0.f;
+                for (int v = tid; v < V; v += 64)
+                    if (al(v)) sum += expf(x[v] - m);
+                lse[0] = m;
+                lse[1] = wave_sum(sum);
+            }
+            if (tid == 0 && pick >= 0 && pick < V && al(pick)) r.score[row] = acc + (double)((x[pick] - lse[0]) - logf(lse[1]));
+        }
+    }
     // every thread took its copy of the policy before the first barrier of sample_row; thread 0 stores behind the last one
     if (tid == 0) commit_token_batched(p, row, t, al.finish_sample(V, pick));
 }

@@ -24,6 +24,9 @@ MAX_LSTM_LAYERS, MAX_BEAM, MAX_NBEST = 4, 8, 16
 MAX_ENSEMBLE = 8                                  # I2L_MAX_ENSEMBLE: members of one i2l_ensemble_decode call
 ENSEMBLE_LOGPROB, ENSEMBLE_PROB = 0, 1            # I2L_ENSEMBLE_*: the combination rule
 CONSTRAIN_NONE, CONSTRAIN_BRACKETS, CONSTRAIN_ARGUMENTS = 0, 1, 2   # I2L_CONSTRAIN_*: the kind of its class table
+RANK_CONSENSUS, RANK_LOGPROB = 0, 1               # I2L_RANK_*: the order of i2l_sample_decode_multi / i2l_sample_rank
+MAX_RANK_STEPS = 1024                             # I2L_MAX_RANK_STEPS
+ABI_VERSION = 115                                 # the i2l_version() this binding was written against (csrc/api.hip)
 # kernel-selection flags (include/img2latex_hip.h I2L_FLAG_*): explicit arguments, the library reads no environment
 FLAG_EXACT_FP32, FLAG_NO_GROUP, FLAG_RESNET_NO_RING, FLAG_RESNET_IM2COL_STEM = 0x1, 0x2, 0x4, 0x8
 FLAG_WEIGHTS_PACKED = 0x10          # conv forward: the workspace still holds the packed filters of these weights
@@ -151,6 +154,13 @@ _SIGNATURES = {
     "i2l_ensemble_decode": (c_int, [POINTER(EnsembleMember), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                                     c_int, c_int, c_float, c_uint64, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
                                     c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "i2l_sample_multi_scratch_bytes": (c_size_t, [c_int] * 7),
+    "i2l_sample_decode_multi": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_int,
+                                        c_float, c_uint64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_void_p]),
+    "i2l_sample_rank": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "i2l_beam_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "i2l_beam_decode": (c_int, [POINTER(DecoderWeights), c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                 c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -266,6 +276,9 @@ def lib() -> ctypes.CDLL:
             fn = getattr(handle, name)          # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args
+        if handle.i2l_version() < ABI_VERSION:
+            raise RuntimeError(f"img2latex_amd: {LIB_PATH} is version {handle.i2l_version()}, this binding needs "
+                               f"{ABI_VERSION}: rebuild it with `make -C hmer-img2latex_amd/csrc`")
         _LIB = handle
     return _LIB
 

@@ -6,6 +6,8 @@
                                                      [--well-formed]  (this package: greedy, sampling or --nbest)
                                                      [--complete-arguments]  (this package: greedy or sampling)
                                                      [--top-k K] [--top-p P] [--device cuda]
+                                                     [--samples N --rank {consensus,logprob} --seed S]  (this package:
+                                                      N draws ranked on the device, with --top-k / --top-p)
                                                      [--ensemble CHECKPOINT ... --ensemble-weights a,b,...
                                                       --ensemble-rule {logprob,prob}]  (this package: greedy or sampling)
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
@@ -149,6 +151,19 @@ def predict_nbest(checkpoint_path: str, image_path: str, beam_size: int, nbest: 
     predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device))
     return predictor.predict_nbest(image=image_path, beam_size=beam_size, nbest=nbest, max_length=max_length,
                                    length_penalty=length_penalty, well_formed=_well_formed(well_formed))
+
+
+def predict_samples(checkpoint_path: str, image_path: str, samples: int, rank: str = "consensus", max_length: int = 141,
+                    temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, seed: int = 0,
+                    length_penalty: float = 0.0, device: Optional[str] = None, well_formed=False):
+    """(this package) ``samples`` top-k / top-p draws of the image as (latex, score, key), best first: the consensus
+    (minimum-Bayes-risk) order, or with ``rank="logprob"`` the length-normalised log-probability.  ``well_formed``: as in
+    ``predict``; "arguments" gives argument-complete candidates."""
+    from .training import Predictor
+    predictor = Predictor.from_checkpoint(checkpoint_path=checkpoint_path, device=_device(device))
+    return predictor.predict_samples(image=image_path, samples=samples, rank=rank, max_length=max_length,
+                                     temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                     well_formed=_well_formed(well_formed), length_penalty=length_penalty)
 
 
 def vocab(formulas_file: str, out_path: str, max_sequence_length: int = 150, device: Optional[str] = None):
@@ -463,6 +478,14 @@ def main(argv: Optional[List[str]] = None) -> int:
                         "in rank order (0: the single result as before)")
     p.add_argument("--length-penalty", type=float, default=0.0,
                    help="(this package) with --nbest: rank by score / length ** A (0: by the raw score)")
+    p.add_argument("--samples", type=int, default=0,
+                   help="(this package) with --top-k / --top-p: draw N (1..16) samples in one decode and print them best "
+                        "first, one key<TAB>latex line each (0: the single result as before); combines with "
+                        "--well-formed and --complete-arguments")
+    p.add_argument("--rank", choices=("consensus", "logprob"), default="consensus",
+                   help="(this package) with --samples: consensus = the sample closest to the others first (key: its "
+                        "summed edit distance), logprob = by score / length ** --length-penalty")
+    p.add_argument("--seed", type=int, default=0, help="(this package) with --samples: the seed of the draws")
     t = sub.add_parser("train", help="Train the image-to-LaTeX model.")
     t.add_argument("--config-path", default="img2latex/configs/config.yaml", help="Path to configuration file")
     t.add_argument("--experiment-name", default="img2latex_v1", help="Name of the experiment")
@@ -536,6 +559,17 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.command == "predict" and args.complete_arguments and args.beam_size > 0:
         ap.error("--complete-arguments with --beam-size: the argument rules exist for the greedy and sampling decode only "
                  "(--well-formed --nbest N is the constrained beam search)")
+    if args.command == "predict" and args.samples != 0:
+        if args.beam_size > 0:
+            ap.error("--samples with --beam-size: the samples are draws of the sampling decode, not beams")
+        if args.nbest > 0:
+            ap.error("--samples with --nbest: --nbest lists beam-search hypotheses (it needs --beam-size)")
+        if args.ensemble:
+            ap.error("--samples with --ensemble: the consensus decode is single-model")
+        if not 1 <= args.samples <= 16:
+            ap.error("--samples must be 1 .. 16")
+        if args.top_k <= 0 and args.top_p <= 0.0:
+            ap.error("--samples needs --top-k or --top-p: the samples are top-k / top-p draws")
     if args.command in ("predict", "evaluate") and args.complete_arguments:
         args.well_formed = "arguments"
     if args.command == "predict" and args.well_formed and args.beam_size > 0 and args.nbest == 0:
@@ -547,6 +581,12 @@ def main(argv: Optional[List[str]] = None) -> int:
         for latex, _, key in predict_nbest(args.checkpoint_path, args.image_path, args.beam_size, args.nbest,
                                            args.max_length, args.length_penalty, args.device,
                                            well_formed=args.well_formed):
+            print(f"{key!r}\t{latex}")
+        return 0
+    if args.command == "predict" and args.samples > 0:
+        for latex, _, key in predict_samples(args.checkpoint_path, args.image_path, args.samples, args.rank, args.max_length,
+                                             args.temperature, args.top_k, args.top_p, args.seed, args.length_penalty,
+                                             args.device, well_formed=args.well_formed):
             print(f"{key!r}\t{latex}")
         return 0
     if args.command == "predict":

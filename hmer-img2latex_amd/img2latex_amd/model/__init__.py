@@ -2,8 +2,8 @@
 from .cnn_encoder import CNNEncoder
 from .lstm_decoder import Attention, LSTMDecoder
 from .resnet_encoder import ResNetEncoder
-from .seq2seq_model import BeamHypothesis, Seq2SeqModel
+from .seq2seq_model import BeamHypothesis, SampleHypothesis, Seq2SeqModel
 from .ensemble import EnsembleDecoder, EnsembleModel
 
-__all__ = ["CNNEncoder", "ResNetEncoder", "LSTMDecoder", "Attention", "Seq2SeqModel", "BeamHypothesis",
+__all__ = ["CNNEncoder", "ResNetEncoder", "LSTMDecoder", "Attention", "Seq2SeqModel", "BeamHypothesis", "SampleHypothesis",
            "EnsembleDecoder", "EnsembleModel"]

@@ -216,3 +216,7 @@ class EnsembleModel(nn.Module):
 
     def beam_search_nbest(self, *args, **kwargs):
         _no_beam("beam_search_nbest")
+
+    def sample_nbest(self, *args, **kwargs):
+        raise RuntimeError("img2latex_amd: sample_nbest over an ensemble does not exist (the consensus decode is "
+                           "single-model)")

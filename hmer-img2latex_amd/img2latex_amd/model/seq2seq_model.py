@@ -24,6 +24,11 @@ from .lstm_decoder import LSTMDecoder
 # one row of beam_search_nbest: tokens (START stripped, cut at END), the raw sum of log-probabilities, the ranking key
 # score / norm[length] and whether the beam ended in END
 BeamHypothesis = namedtuple("BeamHypothesis", ["tokens", "score", "key", "finished"])
+# one row of sample_nbest: tokens (cut at END), the sum of the log-probabilities of its tokens (END included) under the
+# constraint-renormalised model, the ranking key, the summed edit distance to the image's other samples, whether it
+# ended in END, and which draw it was
+SampleHypothesis = namedtuple("SampleHypothesis", ["tokens", "score", "key", "risk", "finished", "sample"])
+RANKS = {"consensus": _lib.RANK_CONSENSUS, "logprob": _lib.RANK_LOGPROB}
 
 
 def length_norm_table(max_length: int, length_penalty: float = 0.0, length_norm: Optional[Sequence[float]] = None):
@@ -291,3 +296,62 @@ class Seq2SeqModel(nn.Module):
         del keep, scratch, norm, cls
         return [[BeamHypothesis(seq_h[j][r][:ln_h[j][r]], sc_h[j][r], key_h[j][r], bool(fin_h[j][r]))
                  for r in range(cnt_h[j])] for j in range(n)]
+
+    def sample_nbest(self, encoder_output: torch.Tensor, start_token_id: int, end_token_id: int, max_length: int,
+                     samples: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, seed: int = 0,
+                     rank: str = "consensus", length_penalty: float = 0.0,
+                     length_norm: Optional[Sequence[float]] = None, constraint=None) -> List[List[SampleHypothesis]]:
+        """Per image ``samples`` (1 .. 16) top-k / top-p draws in ONE step-batched loop (i2l_sample_decode_multi: the
+        draws of an image share its encoder row), each with its sequence log-probability, ranked on the device, best
+        first.  ``rank="consensus"``: the minimum-Bayes-risk order -- ascending ``risk``, the summed Levenshtein distance
+        to the image's other draws, then descending score; ``key`` is the risk.  ``rank="logprob"``: descending ``key =
+        score / norm[n]`` with beam_search_nbest's table (``length_norm_table``).  Duplicates are kept: every image gets
+        ``samples`` hypotheses.  ``constraint``: a BracketTable or an ArgumentTable -- every draw then keeps its rules
+        and ends on END within ``max_length``; the score is the log-probability under the constrained model."""
+        out = self.sample_multi_device(encoder_output, start_token_id, end_token_id, max_length, samples, temperature,
+                                       top_k, top_p, seed, rank, length_penalty, length_norm, constraint)
+        n = out["ids"].shape[0]
+        ids, ln, fin, risk, score, key, order = (out[k] for k in ("ids", "len", "finished", "risk", "score", "key", "order"))
+        ids_h, ln_h, fin_h, risk_h = ids.cpu().tolist(), ln.cpu().tolist(), fin.cpu().tolist(), risk.cpu().tolist()
+        sc_h, key_h, ord_h = score.cpu().tolist(), key.cpu().tolist(), order.cpu().tolist()
+        return [[SampleHypothesis(ids_h[j][s][:ln_h[j][s] - fin_h[j][s]], sc_h[j][s], key_h[j][s], risk_h[j][s],
+                                  bool(fin_h[j][s]), s) for s in ord_h[j]] for j in range(n)]
+
+    def sample_multi_device(self, encoder_output: torch.Tensor, start_token_id: int, end_token_id: int, max_length: int,
+                            samples: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, seed: int = 0,
+                            rank: str = "consensus", length_penalty: float = 0.0,
+                            length_norm: Optional[Sequence[float]] = None, constraint=None) -> Dict[str, torch.Tensor]:
+        """``sample_nbest``'s one call (i2l_sample_decode_multi) with its outputs left on the device, in SAMPLE order:
+        "ids" (images, samples, max_length) int32, -1 behind END; "len", "finished", "risk" int32 and "score", "key"
+        float64, (images, samples); "order" (images, samples) int32, the sample indices best first."""
+        if rank not in RANKS:
+            raise ValueError(f"img2latex_amd: unknown rank {rank!r}; expected one of {sorted(RANKS)}")
+        samples, max_length = int(samples), int(max_length)
+        if not 1 <= samples <= _lib.MAX_NBEST:
+            raise ValueError(f"img2latex_amd: samples must be 1 .. {_lib.MAX_NBEST}, got {samples}")
+        table = length_norm_table(max_length, float(length_penalty), length_norm)
+        dec = self.decoder
+        w, keep, enc = dec.prepare(encoder_output)
+        n, dev = enc.shape[0], enc.device
+        L = _lib.lib()
+        kind, cls = _lib.CONSTRAIN_NONE, None
+        if constraint is not None:
+            kind, cls = constraint.kind, dec._constraint_table(constraint, int(end_token_id), dev)
+        nbytes = L.i2l_sample_multi_scratch_bytes(n, samples, dec.vocab_size, dec.hidden_dim, dec.lstm_layers, max_length, kind)
+        if nbytes == 0:
+            raise RuntimeError(f"img2latex_amd: dimensions not supported by the consensus decode (samples <= "
+                               f"{_lib.MAX_NBEST}, max_length <= {_lib.MAX_RANK_STEPS}, vocabulary <= 2048)")
+        norm = None if table is None else torch.tensor(table, dtype=torch.float64, device=dev)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # lives for this call only, on this stream
+        tok0 = torch.full((n,), int(start_token_id), dtype=torch.int32, device=dev)
+        ids = torch.empty((n, samples, max_length), dtype=torch.int32, device=dev)
+        ln, fin, risk, order = (torch.empty((n, samples), dtype=torch.int32, device=dev) for _ in range(4))
+        score, key = (torch.empty((n, samples), dtype=torch.float64, device=dev) for _ in range(2))
+        _lib.check(L.i2l_sample_decode_multi(ctypes.byref(w), dec._ws.data_ptr(), n, samples, max_length, tok0.data_ptr(),
+                                             float(temperature), int(top_k), float(top_p), int(seed), int(end_token_id),
+                                             kind, _lib.ptr(cls), RANKS[rank], _lib.ptr(norm), scratch.data_ptr(), nbytes,
+                                             ids.data_ptr(), ln.data_ptr(), fin.data_ptr(), score.data_ptr(),
+                                             risk.data_ptr(), key.data_ptr(), order.data_ptr(), 0, _lib.stream_ptr()),
+                   "sample_decode_multi")
+        del keep, scratch, norm, cls, tok0
+        return {"ids": ids, "len": ln, "finished": fin, "risk": risk, "score": score, "key": key, "order": order}

@@ -836,3 +836,47 @@ class Predictor:
         """``predict_batch_nbest`` for one image (path / PIL / ndarray / tensor)."""
         self._single_model("predict_nbest")
         return self.predict_batch_nbest([image], beam_size, nbest, max_length, length_penalty, well_formed=well_formed)[0]
+
+    def predict_batch_samples(self, images, samples: int = 8, rank: str = "consensus", max_length: int = 141,
+                              temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, seed: int = 0,
+                              well_formed=None, length_penalty: float = 0.0,
+                              batch_size: int = 16) -> List[List[Tuple[str, float, float]]]:
+        """Per image the (latex, score, key) of ``samples`` (1 .. 16) top-k / top-p draws, best first
+        (Seq2SeqModel.sample_nbest: ``rank="consensus"`` puts the draw with the smallest summed edit distance to the
+        others first and ``key`` is that sum; ``rank="logprob"`` orders by ``key = score / length ** length_penalty``).
+        Every image goes through ``_prepare_image`` as in ``predict_batch``; batch i draws with ``seed + i``.  The strings
+        come from the device detokenizer where the tokenizer has a device image, else from its own ``decode``.
+        ``well_formed``: True keeps every draw's groups nested, "arguments" also gives every command its arguments, and
+        both end every draw on END (None: the predictor's own setting)."""
+        self._single_model("predict_batch_samples")
+        constraint = self._constraint(well_formed)
+        if isinstance(images, torch.Tensor):
+            images = [images] if images.dim() <= 3 else list(images)
+        start, end = self.tokenizer.start_token_id, self.tokenizer.end_token_id
+        table = detokenize_table(self.tokenizer, self.device)
+        results: List[List[Tuple[str, float, float]]] = []
+        for i in range(0, len(images), batch_size):
+            x = torch.stack([self._prepare_image(im) for im in images[i:i + batch_size]])
+            if x.dim() == 5 and x.shape[1] == 1:
+                x = x.squeeze(1)
+            with torch.no_grad():
+                out = self.model.sample_multi_device(self.model.encoder(x.to(self.device)), start, end, max_length, samples,
+                                                     temperature, top_k, top_p, seed + i, rank, length_penalty,
+                                                     constraint=constraint)
+            n, per = out["order"].shape
+            order, score, key = out["order"].cpu().tolist(), out["score"].cpu().tolist(), out["key"].cpu().tolist()
+            if table is not None:
+                text, _ = table.decode_now(out["ids"].view(n * per, -1), end)
+            else:
+                lens = (out["len"] - out["finished"]).cpu().view(-1).tolist()
+                text = [self.tokenizer.decode(row[:m]) for row, m in zip(out["ids"].view(n * per, -1).cpu().tolist(), lens)]
+            results.extend([(text[j * per + s], score[j][s], key[j][s]) for s in order[j]] for j in range(n))
+        return results
+
+    def predict_samples(self, image, samples: int = 8, rank: str = "consensus", max_length: int = 141,
+                        temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, seed: int = 0, well_formed=None,
+                        length_penalty: float = 0.0) -> List[Tuple[str, float, float]]:
+        """``predict_batch_samples`` for one image (path / PIL / ndarray / tensor)."""
+        self._single_model("predict_samples")
+        return self.predict_batch_samples([image], samples, rank, max_length, temperature, top_k, top_p, seed,
+                                          well_formed=well_formed, length_penalty=length_penalty)[0]

@@ -573,6 +573,54 @@ int i2l_ensemble_decode(const i2l_ensemble_member* members, int n, int combine, 
                         int32_t* ids_out, float* dist_out, void* scratch, size_t scratch_bytes, int flags,
                         i2l_stream_t stream);
 
+/* CONSENSUS decode (this package: the reference draws one sample per image): `samples` draws of each of `images` images
+ * in ONE step-batched loop, scored, and ranked on the device (csrc/sample_rank_rules.inc.h holds the rules, once, for
+ * device and host).  Row i * samples + s of the loop is sample s of image i: the rows of an image share its encoder row
+ * of the workspace -- prepared for `images` rows, not images * samples -- and tok0[i]; the uniform of a row stays
+ * uniform01(seed, row, step), so the samples of an image differ.  The stop rule is sticky and the start state zero.
+ *   score     per sample, fp64: the sum over its steps up to and including END of the log-probability of the committed
+ *             token under the softmax of the RAW logits over the columns the row's constraint allows (no temperature,
+ *             no top-k / top-p truncation; a forbidden column enters as -inf; a constraint's fallback pick adds 0):
+ *             (x[pick] - max) - logf(sum expf(x - max)) in fp32, the beam search's formula, so a sample and a beam
+ *             hypothesis of the same tokens carry comparable scores.
+ *   cut       a sample's sequence is its tokens before the first end_id (all `steps` without one); len = tokens after
+ *             START, END included (sequence length + 1 if it ended, else steps); finished = 1 iff it holds END.
+ *   risk      risk[s] = sum over the image's samples s' of the Levenshtein distance of the two cut sequences (int32).
+ *   rank      I2L_RANK_CONSENSUS: ascending risk, then descending score, then ascending sample index; key = (double)risk
+ *             (the minimum-Bayes-risk candidate first).  I2L_RANK_LOGPROB: descending key = score / length_norm[len]
+ *             (length_norm: i2l_beam_decode_nbest's DEVICE table of steps + 1 fp64 values, or NULL = all ones), then
+ *             ascending sample index.  Duplicates are kept: every image reports `samples` entries.
+ *   constrain_kind  I2L_CONSTRAIN_NONE (cls ignored), _BRACKETS or _ARGUMENTS with the [vocab] class table of
+ *             i2l_sample_decode_constrained / _arguments; the rows' states live in the scratch and are zeroed by the call.
+ *   scratch   i2l_sample_multi_scratch_bytes(...) bytes of device memory (0 for dimensions the call refuses).
+ *   outputs   DEVICE arrays in SAMPLE order: ids_out (images, samples, steps) int32, -1 behind END; len_out, finished_out,
+ *             risk_out int32, score_out, key_out fp64, all (images, samples); order_out (images, samples) int32: the
+ *             sample indices of an image, best first.
+ * A step is layers + 2 launches, the ranking two more at the end; no poll, no cooperative launch.
+ * Refused on the host before the first HIP call: NULL weights / workspace / tok0 or any NULL output,
+ * images, samples or steps <= 0, an unknown rank or constrain_kind, the sampling arguments i2l_sample_decode_batched
+ * refuses, a NULL cls or an end_id outside [0, vocab) under a constraint (I2L_ERR_ARG); samples > I2L_MAX_NBEST, steps >
+ * I2L_MAX_RANK_STEPS, dimensions i2l_sample_decode_batched refuses (I2L_ERR_UNSUPPORTED); scratch NULL or too small
+ * (I2L_ERR_WORKSPACE).  flags: none used.  The library keeps no state.
+ *
+ * i2l_sample_rank is the ranking alone on a caller's DEVICE ids (images, samples, steps) and scores (images, samples):
+ * the same cut, risk, key and order; dist_out (images, samples, samples) int32 or NULL receives the distances.  Same
+ * limits and refusals (NULL ids / score / outputs, images, samples or steps <= 0, unknown rank: I2L_ERR_ARG). */
+#define I2L_RANK_CONSENSUS 0
+#define I2L_RANK_LOGPROB 1
+#define I2L_MAX_RANK_STEPS 1024
+size_t i2l_sample_multi_scratch_bytes(int images, int samples, int vocab, int hidden, int layers, int steps,
+                                      int constrain_kind);
+int i2l_sample_decode_multi(const i2l_decoder_weights* w, const void* workspace, int images, int samples, int steps,
+                            const int32_t* tok0, float temperature, int top_k, float top_p, uint64_t seed, int end_id,
+                            int constrain_kind, const uint8_t* cls, int rank, const double* length_norm, void* scratch,
+                            size_t scratch_bytes, int32_t* ids_out, int32_t* len_out, int32_t* finished_out,
+                            double* score_out, int32_t* risk_out, double* key_out, int32_t* order_out, int flags,
+                            i2l_stream_t stream);
+int i2l_sample_rank(const int32_t* ids, int images, int samples, int steps, int end_id, const double* score, int rank,
+                    const double* length_norm, int32_t* len_out, int32_t* finished_out, int32_t* risk_out,
+                    double* key_out, int32_t* order_out, int32_t* dist_out, i2l_stream_t stream);
+
 /* Beam search for `images` independent images, `beam` beams each (<= I2L_MAX_BEAM):
  * per image exactly Seq2SeqModel._beam_search at batch 1 (seq2seq.py:234-298) --
  * log_softmax in fp32, top-k sorted descending with lower index first on ties, scores
