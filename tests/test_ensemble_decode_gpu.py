@@ -6,7 +6,10 @@ Bounds.  The suite holds every member's logits to 1e-4 absolute; lse is 1-Lipsch
 within 2e-4, and both rules are convex in the members: the combined rows are within 2e-4 + 1e-5 |ref| (the second term
 is the combine's own fp32 rounding).  Greedy ids equal the float64 ids up to a row's first step whose float64 top1-top2
 margin is below the guard: 2e-4 under logprob (the margin between two columns is sum_m w_m (x_m[a] - x_m[b]), every lse_m
-cancels: the suite's own bound), 4e-4 under prob (the lse terms do not cancel: two columns, each within 2e-4)."""
+cancels: the suite's own bound), 4e-4 under prob (the lse terms do not cancel: two columns, each within 2e-4).
+
+Section 1b takes the members' error out: the rule in float64 on the members' own DEVICE logits, the combined rows within
+1e-5 max(1, |ref|) of it -- the second term above, alone -- at every member count and every chunk count of the kernel."""
 import os
 
 import numpy as np
@@ -111,6 +114,63 @@ def test_combined_rows_teacher_forced(name, rule, T):
                 close(h.cpu().numpy(), rh.cpu().numpy(), 1e-5, f"ensemble {name} teacher-forced h")
                 close(c.cpu().numpy(), rc.cpu().numpy(), 1e-5, f"ensemble {name} teacher-forced c")
     record(f"ensemble {name} {rule} T={T}: combined rows vs float64 [abs]", worst)
+
+
+# ------------------------------------------------------------------------------------------------ 1b. the combine alone
+# ensemble_combine_kernel<M> holds 512 columns of every member a chunk: one exactly full chunk, two, three with one column in
+# the last, four (the limit), and V on and one past the lane stride.  Every M meets the two- and three-chunk walks with a
+# ragged last chunk, every V meets the smallest and the largest but one M.
+COMBINE_V = (64, 65, 512, 513, 1024, 1025, 2048)
+COMBINE_CASES = sorted({(M, V) for M in range(2, 9) for V in (513, 1025)} | {(M, V) for M in (2, 7) for V in COMBINE_V})
+
+
+def small(V):
+    return (V, 4, 64, 1, False)          # the smallest decoder the step-batched kernels accept
+
+
+def uneven(M):
+    """Unequal weights of sum 1 up to their rounding to fp32, which is done here: the entry takes floats."""
+    w = np.arange(1, M + 1, dtype=np.float64) ** 1.5
+    return [float(x) for x in (w / w.sum()).astype(np.float32)]
+
+
+@pytest.mark.parametrize("M,V", COMBINE_CASES)
+def test_combine_alone_vs_float64(M, V):
+    """The combine without its members' error.  Each member's own device logits come from running it as a one-member
+    EnsembleDecoder -- the single-model call bit for bit (test_one_member_is_the_single_model_call), the kernels the
+    ensemble launches for that member, unchanged -- along the same forced tokens from the same state on its own encoder
+    rows; ensemble_ref's rule applied to them in float64 is what the ensemble's combined rows are held to, within
+    1e-5 max(1, |ref|): the term the bound at the head of this file gives to the combine's own fp32 rounding, alone.
+    Columns [V, Vp) are never written and not looked at: logits_out has V columns."""
+    shape, T = small(V), 3
+    decs = [build(shape, seed=300 + m)[0].decoder for m in range(M)]
+    worst = {rule: 0.0 for rule in RULES}
+    for rows in (1, 5, 33):
+        encs = EncoderOutputs(torch.from_numpy(synth.uniform(9 + m, "enc", (rows, shape[1]), -1.5, 1.5)).to(DEV) for m in range(M))
+        forced = tokens(shape, rows, T).to(torch.int32).contiguous()
+        given = [(torch.from_numpy(synth.uniform(7 + m, "h0", (1, rows, 64), -0.9, 0.9)).to(DEV),
+                  torch.from_numpy(synth.uniform(7 + m, "c0", (1, rows, 64), -2.0, 2.0)).to(DEV)) for m in range(M)]
+        for hidden in (None, given):
+            kw = dict(forced=forced, want_ids=False, want_logits=True)
+            own = []
+            for m in range(M):
+                _, lg, _ = EnsembleDecoder([decs[m]], None, "logprob").run_steps(
+                    [encs[m]], T, forced[:, 0].contiguous(), hidden=None if hidden is None else [hidden[m]], **kw)
+                assert lg.shape == (rows, T, V) and bool(torch.isfinite(lg).all())
+                own.append(lg.cpu().double())
+            assert not torch.equal(own[0], own[1]), "vacuous: two members hold the same rows"
+            for rule in RULES:
+                for weights in (uneven(M), None):
+                    _, lg, _ = EnsembleDecoder(decs, weights, rule).run_steps(encs, T, forced[:, 0].contiguous(), hidden=hidden, **kw)
+                    got, want = lg.cpu().numpy().astype(np.float64), E.combine(own, weights, rule).numpy()
+                    assert got.shape == (rows, T, V) and np.isfinite(got).all()
+                    err = np.abs(got - want) / np.maximum(1.0, np.abs(want))
+                    worst[rule] = max(worst[rule], float(err.max()))
+                    at = np.unravel_index(int(err.argmax()), err.shape)
+                    assert err.max() <= 1e-5, (M, V, rule, weights is not None, rows, hidden is not None, float(err.max()), at)
+    for rule in RULES:
+        record(f"ensemble combine alone M={M} V={V} {rule}: combined rows vs float64 of the members' device logits "
+               "[rel to max(1,|ref|)]", worst[rule])
 
 
 # ------------------------------------------------------------------------------------------------ 2. greedy ids

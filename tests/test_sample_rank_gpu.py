@@ -8,7 +8,10 @@ The draws are judged by helpers.check_sampling's rule: the float64 distribution 
 device's distributions and runs without a stop rule; this entry returns ids under the sticky stop and no
 distributions, so its rule is applied to the oracle's distribution directly.  Scores: 1e-4 relative to max(1, |ref|),
 the bound test_beam_nbest_gpu.py holds beam scores to.  Integers -- len, finished, risk, dist, order -- are exact, and
-so is the key."""
+so is the key.
+
+Which test launches which sample_distance_kernel<W>: test_rank_on_crafted_ids W = 1, 2, 3 (steps 1, 7, 65, 130), the decode
+tests W = 1 (12 and 20 steps), test_distance_block_boundaries W = 1, 2, 3, 4, 8, 16 (steps 64 .. 1024)."""
 import numpy as np
 import pytest
 import torch
@@ -78,6 +81,63 @@ def test_rank_on_crafted_ids(samples, steps):
                 assert_ranked(got, ids, score, rank, norm, H.END, (names, samples, steps, rank, norm is not None))
 
 
+def rank_all_ways(ids, score, where):
+    """Both ranks, with and without a norm table; the consensus calls also return dist, held to be symmetric with a zero
+    diagonal (each d(i, j) and d(j, i) is a wave's own walk, with the two rows in exchanged roles)."""
+    steps = ids.shape[2]
+    for rank in (R.CONSENSUS, R.LOGPROB):
+        for norm in (None, H.norm_table(steps)):
+            got = device_rank(ids, score, rank, norm, want_dist=rank == R.CONSENSUS)
+            assert_ranked(got, ids, score, rank, norm, H.END, where + (rank, norm is not None))
+            if "dist" in got:
+                d = got["dist"]
+                assert np.array_equal(d, d.transpose(0, 2, 1)) and (np.diagonal(d, axis1=1, axis2=2) == 0).all(), where
+
+
+# rows of the first, second and third image for the calls of two samples: the pair equal but for its last token at
+# R = steps (bit (R - 1) & 63 of the last block), R = 128 beside a row without END, the empty row beside a shifted one
+PAIRS = ((10, 11), (8, 2), (12, 4))
+
+
+@pytest.mark.parametrize("steps", H.BOUNDARY_STEPS)
+def test_distance_block_boundaries(steps):
+    """sample_distance_kernel<W> at W = 1, 2, 3, 4, 4, 8, 8, 16, 16, 16 in a block of 16 waves, and at steps 256 and 1024
+    (W = 4, 16) in blocks of one and two: test_sample_rank_host.boundary_images -- cut lengths on and around every
+    64-token block boundary, identical, disjoint, shifted and last-token pairs, alphabets of 2, 5 and 400 tokens with
+    the padding's token 0 among them, random tokens and further ENDs behind the END -- exactly as the restatement, whose
+    numpy distance the host test holds to the plain table at these sizes."""
+    made = H.boundary_images(steps)
+    ids = np.stack([m[0] for m in made]).astype(np.int32)
+    score = H.boundary_scores(steps)
+    assert ids.shape == (3, 16, steps)
+    rank_all_ways(ids, score, ("boundaries", steps, 16))
+    if steps in (256, 1024):
+        one = np.stack([ids[k, [14]] for k in range(3)])
+        rank_all_ways(one, score[:, [14]], ("boundaries", steps, 1))
+        two = np.stack([ids[k, list(PAIRS[k])] for k in range(3)])
+        rank_all_ways(two, np.stack([score[k, list(PAIRS[k])] for k in range(3)]), ("boundaries", steps, 2))
+
+
+@pytest.mark.parametrize("what,samples,steps,code", [("steps 1025", 16, 1025, _lib.ERR_UNSUPPORTED),
+                                                     ("samples 17", 17, 64, _lib.ERR_UNSUPPORTED),
+                                                     ("samples 0", 0, 64, _lib.ERR_ARG)])
+def test_rank_refuses_without_a_launch(what, samples, steps, code):
+    """check_rank_dims' codes on live device buffers: nothing is launched, so the outputs keep what they held."""
+    S = max(samples, 1)
+    ids = torch.zeros((2, S, steps), dtype=torch.int32, device=DEV)
+    score = torch.zeros((2, S), dtype=torch.float64, device=DEV)
+    outs = [torch.full((2, S), -7, dtype=torch.int32, device=DEV) for _ in range(4)]
+    key = torch.full((2, S), -7.0, dtype=torch.float64, device=DEV)
+    dist = torch.full((2, S, S), -7, dtype=torch.int32, device=DEV)
+    for rank in (R.CONSENSUS, R.LOGPROB):
+        rc = _lib.lib().i2l_sample_rank(ids.data_ptr(), 2, samples, steps, H.END, score.data_ptr(), rank, None,
+                                        outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), key.data_ptr(),
+                                        outs[3].data_ptr(), dist.data_ptr(), _lib.stream_ptr())
+        assert rc == code, (what, rc)
+    torch.cuda.synchronize()
+    assert all(bool((o == -7).all()) for o in outs + [key, dist]), what
+
+
 # ------------------------------------------------------------------------------------------------ i2l_sample_decode_multi
 def model_of(shape):
     """test_sample_batched_gpu.loop_model's choice: "flat" weights above V = 3, weight seed 12 at V = 3."""
@@ -130,19 +190,17 @@ def judge_draws(logits, flat, seed, temperature, top_k, top_p, where):
     return judged, left_out
 
 
-@pytest.mark.parametrize("images,samples", [(7, 5), (3, 16)])
-@pytest.mark.parametrize("shape", [TINY, ODD, SHIPPED], ids=sid)
-def test_samples_vs_float64(shape, images, samples):
-    """35 rows (encoder row r / 5 crosses the 16-row tile edges) and 48 rows on encoder rows of 7 and 3 images."""
+def check_samples(shape, images, samples, seed, temperature=1.0):
+    """The draws by judge_draws' rule at ``temperature``; the scores against the float64 log-probabilities of the RAW logits
+    (no temperature, no truncation: sample_batched_kernel's documented score); both rankings exactly."""
     m, sd64, cfg = model_of(shape)
     enc = enc_for(shape, images, seed=43)
-    seed = 900 + samples
-    got = multi(m, enc, samples, seed=seed)
+    got = multi(m, enc, samples, seed=seed, temperature=temperature)
     ids, flat = got["ids"], got["ids"].reshape(images * samples, STEPS)
     assert ids.shape == (images, samples, STEPS) and flat.max() < shape[0]
     logits = replay64(sd64, cfg, enc, ids, samples)
-    tag = f"sample_decode_multi {sid(shape)} {images}x{samples}"
-    judged, left_out = judge_draws(logits, flat, seed, 1.0, TOP_K, TOP_P, tag)
+    tag = f"sample_decode_multi {sid(shape)} {images}x{samples}" + (f" T={temperature}" if temperature != 1.0 else "")
+    judged, left_out = judge_draws(logits, flat, seed, temperature, TOP_K, TOP_P, tag)
     record(f"{tag}: draws judged", judged)
     record(f"{tag}: draws left out within 1e-5 of a float64 boundary", left_out)
     assert left_out <= 0.02 * judged, (judged, left_out)
@@ -153,9 +211,32 @@ def test_samples_vs_float64(shape, images, samples):
     assert err.max() <= 1e-4, (tag, float(err.max()))
     assert_ranked(got, ids, got["score"], R.CONSENSUS, None, END, tag)
     norm = H.norm_table(STEPS)
-    again = multi(m, enc, samples, seed=seed, rank="logprob", length_norm=norm)
+    again = multi(m, enc, samples, seed=seed, temperature=temperature, rank="logprob", length_norm=norm)
     assert np.array_equal(again["ids"], ids) and again["score"].tobytes() == got["score"].tobytes()
     assert_ranked(again, ids, again["score"], R.LOGPROB, norm, END, tag + " logprob")
+
+
+@pytest.mark.parametrize("images,samples", [(7, 5), (3, 16)])
+@pytest.mark.parametrize("shape", [TINY, ODD, SHIPPED], ids=sid)
+def test_samples_vs_float64(shape, images, samples):
+    """35 rows (encoder row r / 5 crosses the 16-row tile edges) and 48 rows on encoder rows of 7 and 3 images."""
+    check_samples(shape, images, samples, 900 + samples)
+
+
+# The seed was picked on the float64 oracle alone (CPU): the 7 x 5 rows sampled along the oracle's own logits with rule64 /
+# draw64 under the sticky stop, a draw counted when its mask margin or its distance to a CDF step is below GUARD.  Seed 905
+# leaves 0 of 334 (TINY, 0.7), 0 of 311 (TINY, 1.3), 0 of 420 (ODD, 0.7) and 0 of 420 (ODD, 1.3) draws there -- at most 1 % was
+# asked for, half of the 2 % cap, the other half being the device's own path's; 906 and 908 leave 1 of 420 at ODD.  In all
+# four cases some image's five samples are five different sequences.
+TEMPERED_SEED = 905
+
+
+@pytest.mark.parametrize("temperature", [0.7, 1.3])
+@pytest.mark.parametrize("shape", [TINY, ODD], ids=sid)
+def test_samples_vs_float64_tempered(shape, temperature):
+    """Away from temperature 1 the softmax's maximum and sum are those of the scaled logits, and the score's second pass
+    takes its own from the raw ones (sample_batched_kernel<Rule, true>, unconstrained: NoRule)."""
+    check_samples(shape, 7, 5, TEMPERED_SEED, temperature)
 
 
 def test_reproducible_and_seeded():

@@ -5,6 +5,8 @@ stand-alone program (csrc/sample_rank_host_main.cpp), a process of its own under
 Python restatement (sample_rank_ref.py): ``order``, ``risk``, ``len``, ``finished`` and ``dist`` exactly, ``key`` bit for
 bit.  Exhaustively over every image of up to 3 samples of up to 3 tokens over {a, b, END}, and on random and crafted
 images up to 16 samples of 130 tokens (``image_kinds``: the GPU test feeds the same ones to i2l_sample_rank).
+``boundary_images`` are the GPU test's images on the 64-token block boundaries up to 1024 steps; here their pairings are
+checked and the restatement's numpy distance is held to the plain table at those sizes.
 
 Also here: the header / library / ``_lib`` agreement on the three entries, the scratch-size query, the refusals of
 i2l_sample_decode_multi and i2l_sample_rank (they answer before the first HIP call), and the Python and CLI refusals."""
@@ -74,6 +76,108 @@ def image_kinds(rng, S, T):
 
 def norm_table(T):
     return [1.0] + [float(n) ** 0.7 for n in range(1, T + 1)]
+
+
+# ------------------------------------------------------------------------------------------------ the block boundaries
+BOUNDARY_STEPS = [64, 128, 192, 193, 256, 257, 512, 513, 1023, 1024]    # sample_distance_kernel<W>: W = 1 2 3 4 4 8 8 16 16 16
+ALPHABETS = (2, 5, 400)                                                 # dense .. sparse match masks
+SAMPLES = 16
+
+
+def alphabet(alpha):
+    """The first ``alpha`` token ids that are not END; 0 is among them, so the kernel's zero padding is a real token."""
+    return np.array([t for t in range(alpha + 1) if t != END], dtype=np.int32)
+
+
+def boundary_lengths(T, image):
+    """The cut length (the place of the first END; >= T: the row has none) of each of the 16 rows of image ``image``
+    (0, 1 or 2).  Rows in pairs: 0-1 identical, 2-3 no token in common and no END, 4-5 one the other shifted by half its
+    length, 6-7 / 8-9 / 10-11 equal but for their last token at R = 64, 128, T; rows 12-15 are random rows.  Over the
+    three images the lengths are {0, 1, 63, 64, 65, 127, 128, 129, T / 2, T - 1, T, no END}, each clipped to T."""
+    same, shifted, free = [(T - 1, T, (0, 1, 63, 65)), (T // 2, 127, (0, 1, 127, 129)), (129, T - 1, (0, 65, T // 2, T - 1))][image]
+    return [same, same, T, T, shifted, shifted, 64, 64, 128, 128, T, T] + list(free)
+
+
+def boundary_image(rng, T, alpha, image):
+    """ids (16, T) int32 and the rows' cut lengths, each clipped to T.  Behind its END a row holds random tokens, further
+    ENDs and zeros among them: the cut ignores them."""
+    abc = alphabet(alpha)
+    low, high = abc[:alpha // 2], abc[alpha // 2:]
+    cut = [min(n, T) for n in boundary_lengths(T, image)]
+    ids = rng.choice(abc, size=(SAMPLES, T)).astype(np.int32)
+    ids[rng.random(ids.shape) < 0.1] = 0                 # the sparse alphabet too meets the padding's token
+    ids[1] = ids[0]
+    ids[2], ids[3] = rng.choice(low, size=T), rng.choice(high, size=T)
+    n = cut[4]
+    ids[5, :n // 2] = ids[4, n - n // 2:n]
+    for s in (6, 8, 10):
+        ids[s + 1] = ids[s]
+        if cut[s]:
+            ids[s + 1, cut[s] - 1] = abc[(list(abc).index(ids[s, cut[s] - 1]) + 1) % alpha]
+    behind = np.concatenate([abc, [END, END, 0, 0]]).astype(np.int32)
+    for s in range(SAMPLES):
+        if cut[s] < T:
+            ids[s, cut[s]] = END
+            ids[s, cut[s] + 1:] = rng.choice(behind, size=T - cut[s] - 1)
+    return ids, cut
+
+
+def boundary_images(T, images=3):
+    """[(ids, cut)] of ``images`` images of ``T`` steps; image k draws from alphabet k, the steps taking turns in which
+    image comes first, so that a call of two images still meets every alphabet at every kernel width."""
+    rng = np.random.default_rng(7000 + T)
+    turn = BOUNDARY_STEPS.index(T) if T in BOUNDARY_STEPS else 0
+    return [boundary_image(rng, T, ALPHABETS[(k + turn) % 3], (k + turn) % 3) for k in range(images)]
+
+
+def boundary_scores(T, images=3):
+    rng = np.random.default_rng(7100 + T)
+    return np.stack([_scores(rng, SAMPLES) for _ in range(images)])
+
+
+@pytest.mark.parametrize("T", BOUNDARY_STEPS)
+def test_boundary_images_hold_the_pairings(T):
+    """What test_sample_rank_gpu.test_distance_block_boundaries relies on, of every image: the restatement's cut is the
+    intended one; two lengths that are multiples of 64; a row in block 0 beside one in the last block; an empty row
+    beside a non-empty one; two rows without END; the crafted pairs are at distance 0, their length, and 1."""
+    seen = set()
+    for ids, cut in boundary_images(T):
+        got = [R.cut(row, END) for row in ids]
+        assert [len(g[0]) for g in got] == cut and [g[2] for g in got] == [int(n < T) for n in cut]
+        seen |= set(cut)
+        assert sum(n > 0 and n % 64 == 0 for n in cut) >= 2
+        assert any(1 <= n <= 64 for n in cut) and any((n - 1) >> 6 == (T - 1) >> 6 for n in cut if n)
+        assert 0 in cut and sum(n == T and END not in row for n, row in zip(cut, ids.tolist())) >= 2
+        seq = [g[0] for g in got]
+        assert sum(0 in q for q in seq) >= 4                                 # token 0 is in play
+        assert seq[0] == seq[1] and not set(seq[2]) & set(seq[3]) and R.distance(seq[2], seq[3]) == T
+        assert seq[5][:cut[4] // 2] == seq[4][cut[4] - cut[4] // 2:]
+        for s in (6, 8, 10):
+            assert cut[s] == cut[s + 1] and seq[s][:-1] == seq[s + 1][:-1] and seq[s][-1] != seq[s + 1][-1]
+            assert (cut[s] - 1) & 63 == 63 or cut[s] == T
+        for s in range(SAMPLES):                                             # something lies behind every END
+            assert T - cut[s] <= 8 or len(set(ids[s, cut[s] + 1:].tolist())) > 1
+    assert seen == {min(n, T) for n in (0, 1, 63, 64, 65, 127, 128, 129, T // 2, T - 1, T)}
+
+
+def test_the_numpy_distance_at_the_block_boundaries():
+    """sample_rank_ref.distance (a table row per numpy operation: the device tests' reference) against the plain table
+    ``levenshtein`` at lengths on and around the 64-token block boundaries, each against each (the alphabets -- dense and
+    sparse matches -- take turns over the pairs), a pair equal but for its last token, a pair one the other's shift, and
+    one 1024 x 1023 pair."""
+    rng = np.random.default_rng(64)
+    lens = (63, 64, 65, 127, 128, 129, 255, 256, 257)
+    for i, na in enumerate(lens):
+        for j, nb in enumerate(lens):
+            abc = alphabet(ALPHABETS[(i + j) % 3])
+            a, b = rng.choice(abc, size=na).tolist(), rng.choice(abc, size=nb).tolist()
+            want = R.levenshtein(a, b)
+            assert 0 < want and R.distance(a, b) == want == R.distance(b, a), (na, nb)
+    a = rng.choice(alphabet(5), size=257).tolist()
+    assert R.distance(a, a[:256] + [a[256] + 7]) == 1 == R.levenshtein(a, a[:256] + [a[256] + 7])
+    assert R.distance(a, a[128:] + a[:128]) == R.levenshtein(a, a[128:] + a[:128]) > 0
+    a, b = rng.choice(alphabet(5), size=1024).tolist(), rng.choice(alphabet(5), size=1023).tolist()
+    assert R.distance(a, b) == R.levenshtein(a, b) > 0
 
 
 def make_cases():
