@@ -149,6 +149,11 @@ def test_linear_kernel_odd_shapes():
                                        ws.data_ptr(), nbytes, 0, _lib.stream_ptr())
         assert rc == 0
         close(y.cpu().numpy(), want.numpy(), 1e-5)
+        # and element by element against float64 (every plan and path: tests/test_linear_fwd_vs_float64.py)
+        t64 = x.double() @ w.double().t() + b.double()
+        t64 = t64.relu() if relu else t64
+        mag = x.double().abs() @ w.double().abs().t() + b.double().abs()
+        assert float(((y.cpu().double() - t64).abs() / mag).max()) <= 2.0 ** -20, (M, K, N)
 
 
 def test_conv_kernel_odd_shapes():

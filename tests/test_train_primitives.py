@@ -637,3 +637,43 @@ def test_linear_bwd_odd_shapes_vs_float64():
                         assert r <= 2.0 ** -20, (M, K, N, relu, flags, want_dx, want_db, name, r)
     for (name, flags), v in worst.items():
         record(f"train prims linear_bwd {name} flags={flags} [err / float64 magnitude]", v)
+    # The magnitude bound above does not see a lost product of the six-product split scheme (zero-mean operands: 0.05 to
+    # 0.4 of the bound, tests/test_linear_fwd_vs_float64.py).  Selection operands do: every dx and dw element is ONE
+    # product, exact in fp32, so both kernels must return the float64 value bit for bit.  dx sums over n and dw over m,
+    # so the one-hot operand holds one value per COLUMN k (w and x), or per row and column (dy).  A: dy dense randn
+    # (a lost a1 b0 / a2 b0 shows), w and x one-hot +-2^e.  B: dy one-hot, w and x dense (a0 b1 / a0 b2).  C: every value
+    # +-2^e (1 + 2^-9), w and x one-hot: the product's 2^-18 bit is the a1 b1 term.  M = 70: dw's reduction runs on the
+    # split kernel's M/N-contiguous instantiation; M = 5: on the fp32 kernel.  dx (reduction N = 72) is split in both.
+    def pow2(*shape):
+        e = torch.randint(-6, 7, shape, generator=g).double()
+        return ((torch.randint(0, 2, shape, generator=g).double() * 2 - 1) * 2.0 ** e).float()
+
+    def one_per_column(rows, K, val):
+        m = torch.zeros(rows, K)
+        m[(7 * torch.arange(K)) % rows, torch.arange(K)] = val
+        return m
+
+    for (M, K, N) in [(70, 130, 72), (5, 33, 72)]:
+        assert M <= N and math.gcd(7, N) == 1            # dy's one-hot rows sit in distinct columns
+        nb = L.i2l_linear_bwd_workspace_bytes(M, K, N)
+        for fam in "ABC":
+            if fam == "A":
+                dy, w, x = torch.randn(M, N, generator=g), one_per_column(N, K, pow2(K)), one_per_column(M, K, pow2(K))
+            elif fam == "B":
+                dy = torch.zeros(M, N)
+                dy[torch.arange(M), (7 * torch.arange(M)) % N] = pow2(M)
+                w, x = torch.randn(N, K, generator=g), torch.randn(M, K, generator=g)
+            else:
+                c = 1 + 2.0 ** -9
+                dy = (pow2(M, N).double() * c).float()
+                w, x = one_per_column(N, K, (pow2(K).double() * c).float()), one_per_column(M, K, (pow2(K).double() * c).float())
+            dx64, dw64 = dy.double() @ w.double(), dy.double().t() @ x.double()
+            assert torch.equal(dx64.float().double(), dx64) and torch.equal(dw64.float().double(), dw64)
+            assert float(dx64.abs().max()) > 0 and float(dw64.abs().max()) > 0
+            x_dev, w_dev, dy_dev = _dev(x), _dev(w), _dev(dy)
+            for flags in (0, _lib.FLAG_EXACT_FP32):
+                dx, dw, ws = Out((M, K)), Out((N, K)), _ws(nb)
+                assert L.i2l_linear_bias_act_bwd(x_dev.data_ptr(), w_dev.data_ptr(), None, dy_dev.data_ptr(), dx.ptr(),
+                                                 dw.ptr(), None, M, K, N, 0, ws.data_ptr(), nb, flags, None, st) == 0
+                assert torch.equal(dx.get(), dx64.float()), ("selection", fam, M, K, N, flags, "dx")
+                assert torch.equal(dw.get(), dw64.float()), ("selection", fam, M, K, N, flags, "dw")
