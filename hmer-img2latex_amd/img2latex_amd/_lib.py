@@ -26,7 +26,7 @@ ENSEMBLE_LOGPROB, ENSEMBLE_PROB = 0, 1            # I2L_ENSEMBLE_*: the combinat
 CONSTRAIN_NONE, CONSTRAIN_BRACKETS, CONSTRAIN_ARGUMENTS = 0, 1, 2   # I2L_CONSTRAIN_*: the kind of its class table
 RANK_CONSENSUS, RANK_LOGPROB = 0, 1               # I2L_RANK_*: the order of i2l_sample_decode_multi / i2l_sample_rank
 MAX_RANK_STEPS = 1024                             # I2L_MAX_RANK_STEPS
-ABI_VERSION = 115                                 # the i2l_version() this binding was written against (csrc/api.hip)
+ABI_VERSION = 116                                # the i2l_version() this binding was written against (csrc/api.hip)
 # kernel-selection flags (include/img2latex_hip.h I2L_FLAG_*): explicit arguments, the library reads no environment
 FLAG_EXACT_FP32, FLAG_NO_GROUP, FLAG_RESNET_NO_RING, FLAG_RESNET_IM2COL_STEM = 0x1, 0x2, 0x4, 0x8
 FLAG_WEIGHTS_PACKED = 0x10          # conv forward: the workspace still holds the packed filters of these weights
@@ -197,6 +197,13 @@ _SIGNATURES.update({
     "i2l_sequence_metrics": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "i2l_compact_ids": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "i2l_edit_alignment_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "i2l_edit_alignment": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "i2l_confusion_margins": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "i2l_confusion_top_scratch_bytes": (c_size_t, [c_int]),
+    "i2l_confusion_top": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "i2l_detokenize_workspace_bytes": (c_size_t, [c_int]),
     "i2l_detokenize": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -13,7 +13,7 @@
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
                                   [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
                                   [--augment] [--data {auto,native,reference}] [--decode {host,device}]
-    python -m img2latex_amd evaluate CHECKPOINT DATA_DIR [--split test] [--batch-size 32] [--num-samples N]
+    python -m img2latex_amd evaluate CHECKPOINT DATA_DIR [--split test] [--batch-size 32] [--num-samples N] [--errors]
                                                          [--beam-size 0] [--device cuda] [--output-dir outputs]
                                                          [--decode {host,device}]
                                                          [--ensemble CHECKPOINT ... --ensemble-weights a,b,...
@@ -361,7 +361,8 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
 def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_size: int = 32,
              num_samples: Optional[int] = None, beam_size: int = 0, device: Optional[str] = None,
              output_dir: str = "outputs", decode: Optional[str] = None, decode_kernel: str = "auto",
-             well_formed: bool = False, ensemble=(), ensemble_weights=None, ensemble_rule: str = "logprob") -> Dict:
+             well_formed: bool = False, ensemble=(), ensemble_weights=None, ensemble_rule: str = "logprob",
+             errors: bool = False, errors_top: int = 20) -> Dict:
     """cli.py:315-518 on the device: returns {"bleu", "levenshtein", "batch_size"} over the whole split -- the means over
     all pairs, as ``calculate_metrics`` on the reference's two lists computes them -- after printing the three result
     lines and writing ``predictions.json``.
@@ -373,7 +374,11 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
     repeated: the loaders are built at the model's own input size, and the reference's encoder cannot run any other.
     ``decode``: "host" or "device", where the page files are decoded (``data.PageStore``); None: the checkpoint's
     config key ``data.decode``, "host" when absent.  ``well_formed``: as in ``predict``.  ``ensemble``: as in ``predict``;
-    the split is then walked with ``evaluate_batch``, one batch at a time (the look-ahead pipeline is single-model)."""
+    the split is then walked with ``evaluate_batch``, one batch at a time (the look-ahead pipeline is single-model).
+    ``errors``: also write ``error_analysis.json`` and ``error_analysis_report.md`` beside ``predictions.json``: the token
+    confusion matrix of the split, accumulated on the device behind every batch's statistics (``metrics.ErrorAnalysis``;
+    token-level, where the reference's offline analysis/errors.py is character-level); ``errors_top``: the length of
+    its lists.  The returned dict then carries the report under "error_analysis"."""
     import json
     import warnings
     from pathlib import Path
@@ -411,12 +416,13 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
             yield x, batch["formulas"]
 
     stats, predictions = [], []
+    analysis = M.ErrorAnalysis(predictor.tokenizer.vocab_size, dev) if errors else None
     if ensemble:
         results = (predictor.evaluate_batch(x, formulas, predictor.tokenizer.max_sequence_length, return_strings=True,
-                                            return_statistics=True) for x, formulas in batches())
+                                            return_statistics=True, errors=analysis) for x, formulas in batches())
     else:
         results = predictor.evaluate_stream(batches(), max_length=predictor.tokenizer.max_sequence_length,
-                                            return_strings=True, return_statistics=True)
+                                            return_strings=True, return_statistics=True, errors=analysis)
     for out in results:
         stats.append(out["statistics"])
         predictions.extend(out["pred_text"])
@@ -434,6 +440,16 @@ def evaluate(checkpoint_path: str, data_dir: str, split: str = "test", batch_siz
         with open(save_path, "w") as f:
             json.dump([{"prediction": p, "reference": r} for p, r in zip(predictions, raw)], f, indent=2)
         print(f"Predictions saved to: {save_path}")
+    if analysis is not None:
+        report = analysis.report(predictor.tokenizer, top=errors_top, ranges=M.ErrorAnalysis.ranges_from_config(config))
+        metrics = dict(metrics, error_analysis=report)
+        if experiment_name:
+            json_path = os.path.join(predictions_dir, "error_analysis.json")
+            with open(json_path, "w") as f:
+                json.dump(report, f, indent=2)
+            with open(os.path.join(predictions_dir, "error_analysis_report.md"), "w") as f:
+                f.write(M.report_markdown(report))
+            print(f"Error analysis saved to: {json_path}")
     return metrics
 
 
@@ -530,6 +546,13 @@ def main(argv: Optional[List[str]] = None) -> int:
     e.add_argument("--complete-arguments", action="store_true",
                    help="(this package) implies --well-formed, and every command gets the arguments it demands: \\frac its "
                         "two groups, ^ and _ an operand")
+    e.add_argument("--errors", action="store_true",
+                   help="(this package) also write error_analysis.json and error_analysis_report.md beside predictions.json: "
+                        "edit-distance buckets, operation totals, the top substituted / deleted / inserted tokens and per-token "
+                        "recall and precision, from edit alignments computed on the device.  Distances and operations are "
+                        "counted in TOKENS (the reference's offline error report counts characters)")
+    e.add_argument("--errors-top", type=int, default=20, metavar="N",
+                   help="(this package) with --errors: the length of the top lists (1 .. 1024, default 20)")
     for q in (p, e):
         q.add_argument("--ensemble", action="append", default=[], metavar="CHECKPOINT",
                        help="(this package) a further checkpoint of the same vocabulary; repeatable.  The checkpoints choose "
@@ -556,6 +579,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             ensemble_weights = _ensemble_weights(args.ensemble_weights, 1 + len(args.ensemble))
         except ValueError as exc:
             ap.error(str(exc))
+    if args.command == "evaluate" and not 1 <= args.errors_top <= 1024:
+        ap.error("--errors-top must be 1 .. 1024")
     if args.command == "predict" and args.complete_arguments and args.beam_size > 0:
         ap.error("--complete-arguments with --beam-size: the argument rules exist for the greedy and sampling decode only "
                  "(--well-formed --nbest N is the constrained beam search)")
@@ -602,7 +627,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.command == "evaluate":
         evaluate(args.checkpoint_path, args.data_dir, args.split, args.batch_size, args.num_samples, args.beam_size,
                  args.device, args.output_dir, args.decode, args.decode_kernel, args.well_formed, args.ensemble,
-                 ensemble_weights, args.ensemble_rule)
+                 ensemble_weights, args.ensemble_rule, **(dict(errors=True, errors_top=args.errors_top) if args.errors else {}))
         return 0
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,

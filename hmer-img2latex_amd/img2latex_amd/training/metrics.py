@@ -192,3 +192,263 @@ def masked_accuracy(logits: torch.Tensor, targets: torch.Tensor, pad_token_id: i
                                               out.data_ptr(), _lib.stream_ptr()), "masked_accuracy")
     c, t = out.cpu().tolist()
     return int(c), int(t)
+
+
+# ------------------------------------------------------------------------------------------------ error analysis
+# Which tokens the model gets wrong: the edit script of every (target, prediction) pair and the token confusion matrix of
+# a split, on the device (csrc/edit_align_rules.inc.h states the rules; i2l_edit_alignment / i2l_confusion_margins /
+# i2l_confusion_top).  The reference answers the question offline, per character string (analysis/errors.py).
+OP_MATCH, OP_SUBSTITUTION, OP_DELETION, OP_INSERTION = 0, 1, 2, 3
+KIND_SUBSTITUTIONS, KIND_DELETIONS, KIND_INSERTIONS, KIND_MATCHES = 1, 2, 4, 8     # I2L_CONFUSION_*
+MAX_ALIGN_WIDTH, MAX_ALIGN_VOCAB, MAX_TOP = 1024, 2048, 1024
+DEFAULT_DISTANCE_RANGES = [[0, 0], [1, 1], [2, 3], [4, "inf"]]                     # analysis/errors.py's defaults
+
+
+def device_edit_alignment(p_ids: torch.Tensor, p_len: torch.Tensor, t_ids: torch.Tensor, t_len: torch.Tensor,
+                          vocab_size: int, confusion: torch.Tensor = None, want_ops: bool = True,
+                          want_script: bool = False) -> Dict[str, torch.Tensor]:
+    """ONE launch over id matrices that live on the device ((P, W) int32 + lengths (P) int32, as
+    ``device_sequence_statistics`` takes them); nothing is copied to the host.  Returns device tensors: "ops" (P, 4) int32
+    = matches, substitutions, deletions, insertions (``want_ops``); "script" (P, Wp + Wt) uint8 and "script_len" (P) int32
+    (``want_script``: 0 match, 1 substitution, 2 deletion, 3 insertion, forward order, the bytes behind script_len
+    unwritten).  ``confusion``: a (V + 1, V + 1) int32 device tensor that the pairs' operations are ADDED to."""
+    for name, t in (("pred ids", p_ids), ("pred lengths", p_len), ("target ids", t_ids), ("target lengths", t_len)):
+        _lib.require_gpu(t, name, torch.int32)
+    V = int(vocab_size)
+    if p_ids.dim() != 2 or t_ids.dim() != 2 or p_ids.shape[0] != t_ids.shape[0] or p_len.numel() != p_ids.shape[0] or \
+            t_len.numel() != t_ids.shape[0]:
+        raise RuntimeError("id matrices must be (P, W) with P lengths each")
+    if p_ids.stride(1) != 1 or t_ids.stride(1) != 1 or not p_len.is_contiguous() or not t_len.is_contiguous():
+        raise RuntimeError("id rows and lengths must be contiguous")
+    if confusion is not None:
+        _lib.require_gpu(confusion, "confusion", torch.int32)
+        if tuple(confusion.shape) != (V + 1, V + 1) or not confusion.is_contiguous():
+            raise RuntimeError(f"confusion must be a contiguous ({V + 1}, {V + 1}) int32 tensor")
+    if not (want_ops or want_script or confusion is not None):
+        raise ValueError("nothing asked for: want_ops, want_script or a confusion matrix")
+    pairs, dev = p_ids.shape[0], p_ids.device
+    out: Dict[str, torch.Tensor] = {}
+    if pairs == 0:
+        if want_ops:
+            out["ops"] = torch.zeros((0, 4), dtype=torch.int32, device=dev)
+        if want_script:
+            out["script"] = torch.zeros((0, p_ids.shape[1] + t_ids.shape[1]), dtype=torch.uint8, device=dev)
+            out["script_len"] = torch.zeros((0,), dtype=torch.int32, device=dev)
+        return out
+    # a zero-width matrix holds nothing to read: one column of filler keeps the strides positive
+    if p_ids.shape[1] == 0:
+        p_ids = torch.zeros((pairs, 1), dtype=torch.int32, device=dev)
+    if t_ids.shape[1] == 0:
+        t_ids = torch.zeros((pairs, 1), dtype=torch.int32, device=dev)
+    wp, wt = p_ids.shape[1], t_ids.shape[1]
+    if p_ids.stride(0) != wp:
+        p_ids = p_ids.contiguous()
+    if t_ids.stride(0) != wt:
+        t_ids = t_ids.contiguous()
+    L = _lib.lib()
+    need = L.i2l_edit_alignment_scratch_bytes(pairs, wp, wt)
+    scratch = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+    if want_ops:
+        out["ops"] = torch.empty((pairs, 4), dtype=torch.int32, device=dev)
+    if want_script:
+        out["script"] = torch.empty((pairs, wp + wt), dtype=torch.uint8, device=dev)
+        out["script_len"] = torch.empty((pairs,), dtype=torch.int32, device=dev)
+    _lib.check(L.i2l_edit_alignment(p_ids.data_ptr(), p_len.data_ptr(), wp, t_ids.data_ptr(), t_len.data_ptr(), wt, pairs, V,
+                                    _lib.ptr(scratch), need, _lib.ptr(out.get("ops")), _lib.ptr(out.get("script")),
+                                    _lib.ptr(out.get("script_len")), _lib.ptr(confusion), _lib.stream_ptr()),
+               "edit_alignment")
+    return out
+
+
+def edit_alignment(predictions: Sequence[Sequence[int]], targets: Sequence[Sequence[int]], vocab_size: int,
+                   confusion: torch.Tensor = None, want_ops: bool = True, want_script: bool = False):
+    """``device_edit_alignment`` for ragged id lists (uploaded, as ``sequence_statistics`` uploads them).  Returns host
+    values: "ops" (P, 4) int32 tensor; "script": a list of P lists of operation codes; "confusion": the device tensor the
+    operations were added to (a fresh zeroed one when none was given)."""
+    assert len(predictions) == len(targets), "Predictions and targets must have the same length"
+    dev = _device()
+    V = int(vocab_size)
+    if confusion is None:
+        confusion = torch.zeros((V + 1, V + 1), dtype=torch.int32, device=dev)
+    out = {"confusion": confusion}
+    if len(predictions) == 0:
+        if want_ops:
+            out["ops"] = torch.zeros((0, 4), dtype=torch.int32)
+        if want_script:
+            out["script"] = []
+        return out
+    width = max([len(s) for s in predictions] + [len(s) for s in targets] + [1])
+    p_ids, p_len = _pack(predictions, dev, width)
+    t_ids, t_len = _pack(targets, dev, width)
+    if int(p_len.max()) > p_ids.shape[1] or int(t_len.max()) > t_ids.shape[1]:
+        raise RuntimeError("sequence length exceeds the id matrix width")
+    res = device_edit_alignment(p_ids, p_len, t_ids, t_len, V, confusion, want_ops, want_script)
+    if want_ops:
+        out["ops"] = res["ops"].cpu()
+    if want_script:
+        rows, lens = res["script"].cpu(), res["script_len"].cpu().tolist()
+        out["script"] = [rows[i, :n].tolist() for i, n in enumerate(lens)]
+    return out
+
+
+def confusion_margins(confusion: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(row_total (V + 1), col_total (V + 1), diag (V)) int32 device tensors of a (V + 1, V + 1) confusion matrix."""
+    _lib.require_gpu(confusion, "confusion", torch.int32)
+    V = confusion.shape[0] - 1
+    if confusion.dim() != 2 or confusion.shape[1] != V + 1 or V < 1 or not confusion.is_contiguous():
+        raise RuntimeError("confusion must be a contiguous (V + 1, V + 1) int32 tensor")
+    dev = confusion.device
+    row, col = (torch.empty((V + 1,), dtype=torch.int32, device=dev) for _ in range(2))
+    diag = torch.empty((V,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().i2l_confusion_margins(confusion.data_ptr(), V, row.data_ptr(), col.data_ptr(), diag.data_ptr(),
+                                                _lib.stream_ptr()), "confusion_margins")
+    return row, col, diag
+
+
+def confusion_top(confusion: torch.Tensor, kinds: int, n: int) -> List[Tuple[int, int, int]]:
+    """The up to ``n`` largest non-zero cells of the selected kinds (an OR of KIND_*) as host (row, col, count) tuples:
+    count descending, then row, then column ascending.  One small copy of the listed cells."""
+    _lib.require_gpu(confusion, "confusion", torch.int32)
+    V = confusion.shape[0] - 1
+    if confusion.dim() != 2 or confusion.shape[1] != V + 1 or V < 1 or not confusion.is_contiguous():
+        raise RuntimeError("confusion must be a contiguous (V + 1, V + 1) int32 tensor")
+    L, dev, n = _lib.lib(), confusion.device, int(n)
+    need = L.i2l_confusion_top_scratch_bytes(V)
+    scratch = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    out = torch.empty((3 * max(n, 1) + 1,), dtype=torch.int32, device=dev)       # rows | cols | counts | listed
+    m = max(n, 1)
+    _lib.check(L.i2l_confusion_top(confusion.data_ptr(), V, int(kinds), n, scratch.data_ptr(), need, out[:m].data_ptr(),
+                                   out[m:2 * m].data_ptr(), out[2 * m:3 * m].data_ptr(), out[3 * m:].data_ptr(),
+                                   _lib.stream_ptr()), "confusion_top")
+    host = out.cpu()
+    listed = int(host[3 * m])
+    counts = host[2 * m:2 * m + listed].to(torch.int64) & 0xFFFFFFFF
+    return list(zip(host[:listed].tolist(), host[m:m + listed].tolist(), counts.tolist()))
+
+
+def distance_buckets(distances: Sequence[int], ranges=None) -> List[Dict]:
+    """Counts of the pairs' edit distances per closed range [lo, hi] ("inf": no upper edge), analysis/errors.py's buckets
+    on TOKEN distances."""
+    ranges = DEFAULT_DISTANCE_RANGES if ranges is None else ranges
+    total = len(distances)
+    out = []
+    for lo, hi in ranges:
+        unbounded = isinstance(hi, str) or hi == float("inf")
+        count = sum(1 for d in distances if d >= lo and (unbounded or d <= hi))
+        out.append({"range": [int(lo), "inf" if unbounded else int(hi)], "count": count,
+                    "fraction": count / total if total else 0.0})
+    return out
+
+
+class ErrorAnalysis:
+    """The confusion matrix of a split and the report on it.
+
+    ``update`` only enqueues i2l_edit_alignment on the current stream (``Predictor.evaluate_batch / evaluate_stream`` call it
+    behind i2l_sequence_metrics when given ``errors=``); ``add_distances`` takes the per-pair edit distances that the packed
+    statistics bring to the host anyway; ``report`` runs i2l_confusion_margins and i2l_confusion_top and copies their
+    results -- the only device-to-host copies of the analysis.  Everything counted comes from those three entries: the
+    host divides and packs."""
+
+    def __init__(self, vocab_size: int, device=None):
+        self.vocab_size = int(vocab_size)
+        if not 1 <= self.vocab_size <= MAX_ALIGN_VOCAB:
+            raise NotImplementedError(f"img2latex_amd: the error analysis is built for vocabularies of 1 .. {MAX_ALIGN_VOCAB} tokens")
+        dev = _device() if device is None else torch.device(device)
+        self.confusion = torch.zeros((self.vocab_size + 1, self.vocab_size + 1), dtype=torch.int32, device=dev)
+        self.distances: List[int] = []
+
+    def update(self, p_ids: torch.Tensor, p_len: torch.Tensor, t_ids: torch.Tensor, t_len: torch.Tensor) -> None:
+        device_edit_alignment(p_ids, p_len, t_ids, t_len, self.vocab_size, self.confusion, want_ops=False)
+
+    def retract(self, p_ids: torch.Tensor, p_len: torch.Tensor, t_ids: torch.Tensor, t_len: torch.Tensor) -> None:
+        """Takes a batch out again that ``update`` had added (the evaluate chain's rare second run of a batch).  The
+        subtraction is no atomic, so it waits for the updates in flight on other streams, and they for it."""
+        once = torch.zeros_like(self.confusion)
+        device_edit_alignment(p_ids, p_len, t_ids, t_len, self.vocab_size, once, want_ops=False)
+        torch.cuda.synchronize(self.confusion.device)
+        self.confusion -= once
+        torch.cuda.synchronize(self.confusion.device)
+
+    def add_distances(self, lev) -> None:
+        self.distances.extend(int(d) for d in (lev.tolist() if hasattr(lev, "tolist") else lev))
+
+    @staticmethod
+    def ranges_from_config(config) -> Union[List, None]:
+        """A checkpoint config's ``analysis.error_distance_ranges``, or None."""
+        got = ((config or {}).get("analysis") or {}).get("error_distance_ranges")
+        return [list(r) for r in got] if got else None
+
+    def report(self, tokenizer=None, top: int = 20, ranges=None) -> Dict:
+        V = self.vocab_size
+        top = max(1, min(int(top), MAX_TOP))
+        row_d, col_d, diag_d = confusion_margins(self.confusion)
+        subs = confusion_top(self.confusion, KIND_SUBSTITUTIONS, top)
+        dels = confusion_top(self.confusion, KIND_DELETIONS, top)
+        ins = confusion_top(self.confusion, KIND_INSERTIONS, top)
+        unsigned = lambda t: (t.cpu().to(torch.int64) & 0xFFFFFFFF).tolist()
+        row, col, diag = unsigned(row_d), unsigned(col_d), unsigned(diag_d)
+        return build_report(V, row, col, diag, subs, dels, ins, self.distances, tokenizer, ranges)
+
+
+def build_report(V: int, row: Sequence[int], col: Sequence[int], diag: Sequence[int], subs, dels, ins, distances,
+                 tokenizer=None, ranges=None) -> Dict:
+    """The report dict from the device entries' results on the host: margins (row (V + 1), col (V + 1), diag (V)) and the
+    three top lists of (row, col, count).  Sums of the margins, divisions, packing."""
+    id_to_token = getattr(tokenizer, "id_to_token", None) if tokenizer is not None else None
+
+    def name(i):
+        if id_to_token is None:
+            return int(i)
+        return id_to_token.get(int(i), str(int(i))) if hasattr(id_to_token, "get") else id_to_token[int(i)]
+
+    matches, deletions, insertions = sum(diag), col[V], row[V]
+    substitutions = sum(row[:V]) - matches - deletions
+    per_token = []
+    for v in range(V):
+        if row[v] or col[v]:
+            per_token.append({"token": name(v), "id": v, "target_count": row[v], "predicted_count": col[v], "matches": diag[v],
+                              "recall": diag[v] / row[v] if row[v] else None,
+                              "precision": diag[v] / col[v] if col[v] else None})
+    return {
+        "level": "token",
+        "vocab_size": V,
+        "pairs": len(distances),
+        "edit_distance_total": sum(distances),
+        "distance_buckets": distance_buckets(distances, ranges),
+        "operations": {"match": matches, "substitution": substitutions, "deletion": deletions, "insertion": insertions},
+        "top_substitutions": [{"target": name(a), "predicted": name(b), "count": c} for a, b, c in subs],
+        "top_deletions": [{"target": name(a), "count": c} for a, _, c in dels],
+        "top_insertions": [{"predicted": name(b), "count": c} for _, b, c in ins],
+        "per_token": per_token,
+    }
+
+
+def report_markdown(report: Dict) -> str:
+    """error_analysis_report.md: the report dict as the sections of the reference's error report (analysis/errors.py),
+    with TOKEN-level distances where the reference's are character-level."""
+    lines = ["# Error analysis", "",
+             f"{report['pairs']} (target, prediction) pairs, vocabulary of {report['vocab_size']} tokens.  Edit distances and "
+             "operations are counted in tokens (the reference's offline report counts characters).  The `evaluate` command "
+             "aligns the pairs its BLEU and Levenshtein figures are computed on, built as the reference builds them: the "
+             "prediction without special tokens, the target without padding but with its START and END tokens, which "
+             "therefore show up as two deletions per pair.", "",
+             "## Edit-distance buckets", "", "| token edit distance | pairs | fraction |", "|---|---|---|"]
+    for b in report["distance_buckets"]:
+        lo, hi = b["range"]
+        label = f"{lo}" if lo == hi else (f"{lo}+" if hi == "inf" else f"{lo}-{hi}")
+        lines.append(f"| {label} | {b['count']} | {b['fraction']:.4f} |")
+    lines += ["", "## Operation totals", "", "| operation | count |", "|---|---|"]
+    lines += [f"| {k} | {v} |" for k, v in report["operations"].items()]
+    cell = lambda t: "`" + str(t).replace("|", "\\|") + "`"
+    lines += ["", "## Top substitutions", "", "| target | predicted | count |", "|---|---|---|"]
+    lines += [f"| {cell(e['target'])} | {cell(e['predicted'])} | {e['count']} |" for e in report["top_substitutions"]]
+    lines += ["", "## Top deleted tokens", "", "| target | count |", "|---|---|"]
+    lines += [f"| {cell(e['target'])} | {e['count']} |" for e in report["top_deletions"]]
+    lines += ["", "## Top inserted tokens", "", "| predicted | count |", "|---|---|"]
+    lines += [f"| {cell(e['predicted'])} | {e['count']} |" for e in report["top_insertions"]]
+    worst = sorted((t for t in report["per_token"] if t["recall"] is not None), key=lambda t: (t["recall"], -t["target_count"]))
+    lines += ["", "## Lowest per-token recall", "", "| token | in targets | matches | recall | precision |", "|---|---|---|---|---|"]
+    for t in worst[:len(report["top_substitutions"]) or 20]:
+        prec = "-" if t["precision"] is None else f"{t['precision']:.4f}"
+        lines.append(f"| {cell(t['token'])} | {t['target_count']} | {t['matches']} | {t['recall']:.4f} | {prec} |")
+    return "\n".join(lines) + "\n"

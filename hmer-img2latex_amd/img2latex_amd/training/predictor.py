@@ -511,7 +511,8 @@ class Predictor:
             pipe.close()                                     # gives its decoder workspaces back
 
     def evaluate_batch(self, images, targets: Union[torch.Tensor, Sequence[str]], max_length: Optional[int] = None,
-                       return_strings: bool = False, well_formed=None, return_statistics: bool = False) -> Dict:
+                       return_strings: bool = False, well_formed=None, return_statistics: bool = False,
+                       errors=None) -> Dict:
         """One batch of the reference's ``evaluate`` command (cli.py:449-495) with every stage on the device and
         the token ids never leaving HBM between them:
 
@@ -530,14 +531,17 @@ class Predictor:
         ``tokenizer.decode`` of every row of "pred_ids", built by i2l_detokenize in the same chain (from the decode's ids
         under the compaction's own cut and drop rule: the compacted rows are zero-padded and the kernel takes no
         lengths) and copied beside the statistics; a tokenizer without a device image decodes "pred_ids" on the host.
-        ``return_statistics``: also "statistics", as in ``evaluate_stream``."""
+        ``return_statistics``: also "statistics", as in ``evaluate_stream``.  ``errors``: a ``metrics.ErrorAnalysis``; its
+        i2l_edit_alignment launch then follows i2l_sequence_metrics on the same stream over the same compacted ids and adds
+        the batch to its confusion matrix, and the batch's edit distances -- already on the host with the statistics -- go
+        into its buckets.  None (the default): not one launch or copy more."""
         launched = self._evaluate_launch(images, targets, max_length, return_strings=return_strings,
-                                         constraint=self._constraint(well_formed))
+                                         constraint=self._constraint(well_formed), errors=errors)
         launched["return_statistics"] = return_statistics
         return self._evaluate_finish(launched)
 
     def evaluate_stream(self, batches, max_length: Optional[int] = None, lookahead: int = 2, return_strings: bool = False,
-                        return_statistics: bool = False, well_formed=None):
+                        return_statistics: bool = False, well_formed=None, errors=None):
         """``evaluate_batch`` over an iterable of (images, targets), one result per batch in order, software-pipelined:
         the host work of batch i+1 (shape pass, packing the ragged pages into pinned memory, their upload on a side
         stream) runs while the device is still busy with batch i, and the host only waits for batch i's statistics
@@ -561,18 +565,19 @@ class Predictor:
         ``return_strings``: as in ``evaluate_batch`` ("pred_text").  ``return_statistics``: every result also carries
         "statistics", a host copy of its (B, 9) int32 statistics rows; ``metrics.metrics_from_packed`` of the rows of all
         batches, concatenated, gives the means over all pairs of a split (not means of batch means).  ``well_formed``: the
-        bracket-constrained decode (step-batched kernels) in the place of the grouped one, the schedule otherwise the same."""
+        bracket-constrained decode (step-batched kernels) in the place of the grouped one, the schedule otherwise the same.
+        ``errors``: as in ``evaluate_batch``; the alignment launch sits behind the statistics on the decode's stream."""
         self._single_model("evaluate_stream")
-        return self._evaluate_stream(batches, max_length, lookahead, return_strings, return_statistics, well_formed)
+        return self._evaluate_stream(batches, max_length, lookahead, return_strings, return_statistics, well_formed, errors)
 
-    def _evaluate_stream(self, batches, max_length, lookahead, return_strings, return_statistics, well_formed):
+    def _evaluate_stream(self, batches, max_length, lookahead, return_strings, return_statistics, well_formed, errors=None):
         from collections import deque
         pending = deque()
         constraint = self._constraint(well_formed)
         lookahead = max(1, min(int(lookahead), 2))           # the landing buffers / decoder slots rotate over 4 / 3
         for images, targets in batches:
             pending.append(self._evaluate_launch(images, targets, max_length, side_upload=True, coresident=True,
-                                                 return_strings=return_strings, constraint=constraint))
+                                                 return_strings=return_strings, constraint=constraint, errors=errors))
             pending[-1]["return_statistics"] = return_statistics
             if len(pending) > lookahead:
                 yield self._evaluate_finish(pending.popleft())
@@ -581,7 +586,7 @@ class Predictor:
 
     def _evaluate_launch(self, images, targets, max_length: Optional[int], side_upload: bool = False,
                          rows_per_workgroup: int = 0, coresident: bool = False, return_strings: bool = False,
-                         constraint=None):
+                         constraint=None, errors=None):
         """Enqueues the whole chain of one batch and the copy of its statistics to pinned memory; no host wait.
         ``coresident``: two streams -- everything up to the decoder's prepare on the first, the decode and what follows on the
         second (see evaluate_stream); otherwise the whole chain on the current stream."""
@@ -693,6 +698,8 @@ class Predictor:
                                              self._drop.data_ptr(), len(drop), p_ids.data_ptr(), W, p_len.data_ptr(),
                                              _lib.stream_ptr()), "compact_ids")
                 packed = M.device_sequence_statistics(p_ids, p_len, t_ids, t_len, 4, tk.pad_token_id, _max_len=W, defer=True)
+                if errors is not None:
+                    errors.update(p_ids, p_len, t_ids, t_len)
             # statistics + the first id of every row (-3 = the grouped decode timed out) in ONE device->host copy
             packed = torch.cat([packed, ids[:, :1]] + ([] if tok_status is None else [tok_status.expand(B)[:, None]]), dim=1)
             # pinned landing buffers are reused (registering pinned memory costs ~1 ms): a ring of 4, more than the
@@ -718,7 +725,8 @@ class Predictor:
             done = torch.cuda.Event()
             done.record()
         return dict(host=host, done=done, keep=(packed, x, tgt), p_ids=p_ids, p_len=p_len, raw=(raw, targets, max_length),
-                    rows_per_workgroup=rows_per_workgroup, return_strings=return_strings, text=text, constraint=constraint)
+                    rows_per_workgroup=rows_per_workgroup, return_strings=return_strings, text=text, constraint=constraint,
+                    errors=errors, aligned=(p_ids, p_len, t_ids, t_len))
 
     def _evaluate_finish(self, h) -> Dict:
         from . import metrics as M
@@ -727,19 +735,25 @@ class Predictor:
         if _lib.ids_timed_out(host[:, 9:10]) and h["rows_per_workgroup"] == 0:
             # the timeout fallback of Seq2SeqModel.greedy_ids_host: the row-per-workgroup kernel needs no partner
             raw, targets, max_length = h["raw"]
+            if h["errors"] is not None:
+                h["errors"].retract(*h["aligned"])           # this run's rows are not the batch's
             again = self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=1, return_strings=h["return_strings"],
-                                          constraint=h["constraint"])
+                                          constraint=h["constraint"], errors=h["errors"])
             again["return_statistics"] = h.get("return_statistics", False)
             return self._evaluate_finish(again)
         _lib.check_ids(host[:, 9:10])
         if host.shape[1] > 10 and int(host[0, 10]) != 0:
             # string targets at the stream's fixed width and a row was cut: once more with collate's width
             raw, targets, max_length = h["raw"]
+            if h["errors"] is not None:
+                h["errors"].retract(*h["aligned"])
             again = self._evaluate_launch(raw, targets, max_length, rows_per_workgroup=h["rows_per_workgroup"],
-                                          return_strings=h["return_strings"], constraint=h["constraint"])
+                                          return_strings=h["return_strings"], constraint=h["constraint"], errors=h["errors"])
             again["return_statistics"] = h.get("return_statistics", False)
             return self._evaluate_finish(again)
         out = M.metrics_from_packed(host)
+        if h["errors"] is not None:
+            h["errors"].add_distances(host[:, 0])
         out["pred_ids"], out["pred_len"] = h["p_ids"], h["p_len"]
         if h.get("return_statistics"):
             out["statistics"] = host[:, :9].clone()                  # the landing buffer is reused

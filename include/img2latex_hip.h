@@ -820,6 +820,51 @@ int i2l_sequence_metrics(const int32_t* pred, const int32_t* pred_len, int pred_
 int i2l_scores_from_statistics(const int32_t* stats, int pairs, int stride, int n, double* bleu_mean_out,
                                double* lev_mean_out);
 
+/* Error analysis: the edit script of every (target, prediction) pair and the token confusion matrix of a split.  The
+ * rules are csrc/edit_align_rules.inc.h's.  For a target r[0, m) and a prediction p[0, n), D[i][j] is the Levenshtein table
+ * of r[0, i) against p[0, j) (the recurrence of i2l_sequence_metrics' lev_out, so D[m][n] is that integer).  THE script is
+ * the backtrace from (m, n) to (0, 0) that takes at (i, j) the first of: a match (i, j > 0, r[i-1] == p[j-1], D[i][j] ==
+ * D[i-1][j-1]); a substitution of r[i-1] by p[j-1] (i, j > 0, D[i][j] == D[i-1][j-1] + 1); a deletion of r[i-1] (i > 0,
+ * D[i][j] == D[i-1][j] + 1); an insertion of p[j-1].  It is reported in forward order, one byte per operation: 0 match,
+ * 1 substitution, 2 deletion, 3 insertion.
+ *   pred (pairs, pred_stride) / target (pairs, target_stride) int32 rows; lengths clamped to [0, stride] on the device
+ *   ops_out         [pairs][4] int32: matches, substitutions, deletions, insertions (the last three sum to lev_out); may be NULL
+ *   script_out      [pairs][pred_stride + target_stride] uint8, the first script_len_out[pair] bytes written; NULL together
+ *   confusion       (vocab + 1) x (vocab + 1) uint32, ACCUMULATED into by integer atomics (the caller zeroes it once): row =
+ *                   target id or `vocab` for "nothing", column = predicted id or `vocab`.  A match or substitution of a by
+ *                   b adds 1 to [a][b], a deletion of a to [a][vocab], an insertion of b to [vocab][b]; an operation with
+ *                   an id outside [0, vocab) is in the script and in ops_out and adds nothing.  May be NULL.
+ * One launch, one wave per pair: Myers' bit-vector column pass with two vectors kept per column, in LDS while they fit
+ * (pairs of up to 256 x 256 tokens), else in `scratch` (i2l_edit_alignment_scratch_bytes, 0 when none is needed; the call
+ * returns I2L_ERR_WORKSPACE when scratch_bytes is smaller).  I2L_ERR_ARG: a NULL input, non-positive pairs / strides /
+ * vocab, all three outputs NULL, one of script_out / script_len_out NULL.  I2L_ERR_UNSUPPORTED: a stride above 1024 (the
+ * decode's step limit) or vocab > 2048.  Every refusal is decided before the first HIP call.  The library keeps no state. */
+size_t i2l_edit_alignment_scratch_bytes(int pairs, int pred_stride, int target_stride);
+int i2l_edit_alignment(const int32_t* pred, const int32_t* pred_len, int pred_stride, const int32_t* target,
+                       const int32_t* target_len, int target_stride, int pairs, int vocab, void* scratch,
+                       size_t scratch_bytes, int32_t* ops_out, uint8_t* script_out, int32_t* script_len_out,
+                       uint32_t* confusion, i2l_stream_t stream);
+
+/* Margins of a confusion matrix: row_total[vocab + 1] (occurrences of each target token, its deletions included; [vocab]:
+ * all insertions), col_total[vocab + 1] (occurrences of each predicted token, its insertions included; [vocab]: all
+ * deletions), diag[vocab] (matches of each token).  Each may be NULL, not all.  Deterministic: no atomics. */
+int i2l_confusion_margins(const uint32_t* confusion, int vocab, uint32_t* row_total, uint32_t* col_total, uint32_t* diag,
+                          i2l_stream_t stream);
+
+/* The n <= 1024 largest non-zero cells of a confusion matrix among the kinds selected by `kinds` (an OR of the bits
+ * below), in the order count descending, then row ascending, then column ascending: row_out / col_out / count_out [n],
+ * *listed_out = the number listed (fewer than n when fewer cells qualify; the entries behind it are -1, -1, 0).  Two
+ * launches; scratch (i2l_confusion_top_scratch_bytes) is the caller's.  I2L_ERR_ARG: NULL pointers, n <= 0, kinds without a
+ * known bit or with an unknown one; I2L_ERR_UNSUPPORTED: n > 1024, vocab > 2048; I2L_ERR_WORKSPACE. */
+#define I2L_CONFUSION_SUBSTITUTIONS 1   /* off the diagonal, both indices < vocab */
+#define I2L_CONFUSION_DELETIONS 2       /* column `vocab`                         */
+#define I2L_CONFUSION_INSERTIONS 4      /* row `vocab`                            */
+#define I2L_CONFUSION_MATCHES 8         /* the diagonal                           */
+#define I2L_CONFUSION_ALL 15
+size_t i2l_confusion_top_scratch_bytes(int vocab);
+int i2l_confusion_top(const uint32_t* confusion, int vocab, int kinds, int n, void* scratch, size_t scratch_bytes,
+                      int32_t* row_out, int32_t* col_out, uint32_t* count_out, int32_t* listed_out, i2l_stream_t stream);
+
 /* The id post-processing between the decode loop and the metrics, on the device (cli.py:466-481 with
  * predictor.py:350-358,384-391 and tokenizer.py:166-192): per row keep, in order, the ids BEFORE the first stop
  * position -- id == end_id, or id < 0 (the sticky stop rule's filler) -- that are not one of drop_ids[0..n_drop)
