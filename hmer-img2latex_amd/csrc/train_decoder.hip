@@ -423,6 +423,8 @@ __global__ __launch_bounds__(256) void ordered_sum2_kernel(const float* __restri
     if (threadIdx.x == 0) { out[0] = (float)ra[0]; out[1] = (float)rb[0]; }
 }
 
+#include "train_distill.inc.h"
+
 // out[n] = sum_m A[m][n]   (bias gradients): one thread per column chunk, rows in order (deterministic).
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ A, size_t M, int N, int rows_per_block,
                                                      float* __restrict__ partial) {
@@ -807,6 +809,43 @@ extern "C" int i2l_ce_label_smooth_fwd_bwd(const float* logits, const int32_t* t
 
 extern "C" size_t i2l_ce_workspace_bytes(int rows) {
     return rows > 0 ? 2 * i2l_align((size_t)rows * sizeof(float)) : 0;
+}
+
+extern "C" size_t i2l_ce_distill_workspace_bytes(int rows) {
+    return rows > 0 ? 3 * i2l_align((size_t)rows * sizeof(float)) : 0;
+}
+
+// Every refusal is host code in front of the first HIP call: a refused call leaves every output untouched.
+extern "C" int i2l_ce_distill_fwd_bwd(const float* logits, const int32_t* targets, int rows, int vocab, int pad_id,
+                                       float label_smoothing, const i2l_distill_teacher* teachers, int n, int combine,
+                                       float temperature, float alpha, void* workspace, size_t workspace_bytes,
+                                       float* dlogits_out, float* loss_sum_and_count_out, float* parts_out,
+                                       i2l_stream_t stream) {
+    if (!logits || !targets || !loss_sum_and_count_out || !teachers || rows <= 0 || vocab <= 0) return I2L_ERR_ARG;
+    if (!dr_args_ok(n, combine, temperature, alpha)) return I2L_ERR_ARG;
+    float weight[ENS_MAX];
+    for (int m = 0; m < n; ++m) {
+        if (!teachers[m].logits || teachers[m].ld < vocab || !ens_weight_ok(teachers[m].weight)) return I2L_ERR_ARG;
+        weight[m] = teachers[m].weight;
+    }
+    const size_t part = i2l_align((size_t)rows * sizeof(float));
+    if (!workspace || workspace_bytes < 3 * part) return I2L_ERR_WORKSPACE;
+    DistillArgs e{};
+    e.x = logits; e.tgt = targets; e.d = dlogits_out;
+    e.row_hard = static_cast<float*>(workspace);
+    e.row_soft = reinterpret_cast<float*>(static_cast<char*>(workspace) + part);
+    e.row_keep = reinterpret_cast<float*>(static_cast<char*>(workspace) + 2 * part);
+    e.rows = rows; e.V = vocab; e.pad = pad_id; e.rule = combine;
+    e.k = dr_coef(temperature, alpha, label_smoothing, vocab);
+    for (int m = 0; m < n; ++m) { e.z[m] = teachers[m].logits; e.ld[m] = teachers[m].ld; }
+    ens_normalise(weight, n, e.w, e.logw);
+    hipStream_t s = i2l_s(stream);
+    launch_distill<1>(n, e, s);
+    I2L_CHECK_LAUNCH();
+    hipLaunchKernelGGL(distill_sum3_kernel, dim3(1), dim3(256), 0, s, (const float*)e.row_hard, (const float*)e.row_soft,
+                       (const float*)e.row_keep, (size_t)rows, alpha, loss_sum_and_count_out, parts_out);
+    I2L_CHECK_LAUNCH();
+    return I2L_OK;
 }
 
 extern "C" int i2l_decoder_train_bwd(const i2l_decoder_weights* w, const int32_t* tokens, int B, int T, float dropout_p,

@@ -13,6 +13,8 @@
     python -m img2latex_amd train [--config-path F] [--experiment-name S] [--checkpoint-path F] [--data-dir D]
                                   [--device cuda] [--seed N] [--synthetic-steps N [--synthetic-val-steps N]]
                                   [--augment] [--data {auto,native,reference}] [--decode {host,device}]
+                                  [--teacher CHECKPOINT ... --teacher-weights a,b,... --teacher-rule {logprob,prob}
+                                   --distill-alpha A --distill-temperature T]  (this package: distillation)
     python -m img2latex_amd evaluate CHECKPOINT DATA_DIR [--split test] [--batch-size 32] [--num-samples N] [--errors]
                                                          [--beam-size 0] [--device cuda] [--output-dir outputs]
                                                          [--decode {host,device}]
@@ -114,19 +116,36 @@ def _predictor(checkpoint_path: str, device, decode_kernel: str, well_formed, en
                                       well_formed=_well_formed(well_formed))
 
 
-def _ensemble_weights(text: Optional[str], n: int):
-    """--ensemble-weights "a,b,..." -> n floats (None when absent); ValueError with the reason otherwise."""
+def _ensemble_weights(text: Optional[str], n: int, option: str = "--ensemble-weights", order: str = " (the positional one first)"):
+    """--ensemble-weights "a,b,..." (or ``option``) -> n floats (None when absent); ValueError with the reason otherwise."""
     if text is None:
         return None
     try:
         weights = [float(t) for t in text.split(",")]
     except ValueError:
-        raise ValueError(f"--ensemble-weights {text}: expected comma-separated numbers")
+        raise ValueError(f"{option} {text}: expected comma-separated numbers")
     if len(weights) != n:
-        raise ValueError(f"--ensemble-weights has {len(weights)} values for {n} checkpoints (the positional one first)")
+        raise ValueError(f"{option} has {len(weights)} values for {n} checkpoints{order}")
     if not all(w > 0 and w != float("inf") for w in weights):
-        raise ValueError(f"--ensemble-weights {text}: every weight must be finite and above 0")
+        raise ValueError(f"{option} {text}: every weight must be finite and above 0")
     return weights
+
+
+def _check_teacher_tokens(paths, tables, tokenizer) -> None:
+    """SystemExit naming the first differing token when a teacher checkpoint's ``token_to_id`` is not the student's: the
+    distillation loss compares the two distributions column by column, so column v must be the same token in both."""
+    mine = dict(tokenizer.token_to_id)
+    for path, table in zip(paths, tables):
+        theirs = dict(table.token_to_id)
+        if theirs == mine:
+            continue
+        for tok, i in sorted(mine.items(), key=lambda kv: kv[1]):
+            if theirs.get(tok) != i:
+                raise SystemExit(f"img2latex_amd train: --teacher {path}: its token_to_id differs from the student's "
+                                 f"tokenizer at token {tok!r} (student id {i}, teacher id {theirs.get(tok)})")
+        tok, i = min(((t, i) for t, i in theirs.items() if t not in mine), key=lambda kv: kv[1])
+        raise SystemExit(f"img2latex_amd train: --teacher {path}: its token_to_id differs from the student's tokenizer "
+                         f"at token {tok!r} (teacher id {i}, not in the student's vocabulary)")
 
 
 def predict(checkpoint_path: str, image_path: str, beam_size: int = 0, max_length: int = 141, temperature: float = 1.0,
@@ -211,7 +230,8 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
           checkpoint_path: Optional[str] = None, data_dir: Optional[str] = None, device: Optional[str] = None,
           seed: int = 42, synthetic_steps: int = 0, synthetic_vocab: int = 512, output_dir: str = "outputs",
           synthetic_val_steps: int = 0, augment: bool = False, data: str = "auto", decode: Optional[str] = None,
-          train_kernel: str = "auto") -> Dict:
+          train_kernel: str = "auto", teacher=(), teacher_weights=None, teacher_rule: str = "logprob",
+          distill_alpha: float = 0.5, distill_temperature: float = 2.0) -> Dict:
     """cli.py:104-250 reduced to the hot path: model from the config, optional resume, TrainStep over the batches, a
     checkpoint in the reference's layout (trainer.py:209-224) per epoch, and -- with validation batches -- the epoch-end
     validation / LR schedule / best checkpoint / early stop of trainer.py:713-766.  Returns {"loss", "steps",
@@ -220,7 +240,11 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
     native loaders warp the raw pages with the same keys instead.  ``data``: "auto", "native" or "reference" (see the
     module docstring).  ``decode``: where the native loaders decode the page files, "host" (PIL) or "device"
     (i2l_png_decode); None leaves it to the config key ``data.decode`` (default "host").  ``train_kernel``: see
-    ``_train_flags`` (training and the epoch-end validation follow it)."""
+    ``_train_flags`` (training and the epoch-end validation follow it).  ``teacher``: checkpoint paths of one teacher or
+    of an ensemble (``teacher_weights`` one per path, ``teacher_rule`` "logprob" / "prob"); the student then trains on
+    ``distill_alpha`` x the cross entropy + (1 - ``distill_alpha``) x the divergence from the teacher's token distribution
+    at ``distill_temperature`` (training/distill.py).  Every teacher checkpoint's ``token_to_id`` must be the student's
+    tokenizer's (SystemExit naming the first differing token).  Validation is untouched: ``val_loss`` stays the hard loss."""
     import random
     from . import data as D
     from .training import EarlyStopping, PlateauSchedule, TokenTable, TrainStep, save_checkpoint, validate
@@ -272,6 +296,15 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
             if not loaders:
                 raise SystemExit(f"img2latex_amd train: no samples under {config['data']['data_dir']}")
         max_epochs = int(tcfg.get("epochs", 50))                            # trainer.py:118
+    teacher = list(teacher or ())
+    distill = None
+    if teacher:
+        from .training import Teacher
+        try:
+            distill, tables = Teacher.from_checkpoints(teacher, weights=teacher_weights, combine=teacher_rule, device=dev)
+        except ValueError as exc:
+            raise SystemExit(f"img2latex_amd train: --teacher: {exc}")
+        _check_teacher_tokens(teacher, tables, tokenizer)
     model = build_model(config, tokenizer.vocab_size)
     if resume is not None:
         model.load_state_dict(resume["model_state_dict"])                   # trainer.py:253
@@ -279,7 +312,9 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
     model.decoder.kernel_flags |= _train_flags(train_kernel)
     ts = TrainStep(model, lr=float(tcfg.get("learning_rate", 1e-3)), weight_decay=float(tcfg.get("weight_decay", 1e-4)),
                    clip_grad_norm=float(tcfg.get("clip_grad_norm", 5.0)), pad_token_id=tokenizer.pad_token_id,
-                   label_smoothing=0.1, seed=seed)                          # trainer.py:91-93,111-115
+                   label_smoothing=0.1, seed=seed,                          # trainer.py:91-93,111-115
+                   **(dict(teacher=distill, distill_alpha=distill_alpha, distill_temperature=distill_temperature)
+                      if distill is not None else {}))
     if resume is not None and resume.get("optimizer_state_dict"):
         ts.load_optimizer_state_dict(resume["optimizer_state_dict"])        # trainer.py:255
     # trainer.py:257-258,697: a checkpoint's "epoch" is the number of COMPLETED epochs and "step" the global step; a resumed
@@ -325,11 +360,14 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
             step += 1                                                       # the reference's global_step counts batches (:399)
             batch, batch_idx = nxt, batch_idx + 1
         loss = float(last["loss"]) if last is not None else float("nan")
+        parts = ""
+        if last is not None and "hard_loss" in last:                       # distillation: the last batch's two parts
+            parts = f" (hard {float(last['hard_loss']):.4f}, soft {float(last['soft_loss']):.4f})"
         if val_batches is None:
             path = os.path.join(ck_dir, f"checkpoint_epoch_{epoch}_step_{step}.pt")
             save_checkpoint(path, model, tokenizer, config, epoch=epoch, step=step, metrics={"loss": loss},
                             optimizer_state_dict=ts.optimizer_state_dict())
-            print(f"epoch {epoch}: {step} steps, loss {loss:.4f}, checkpoint {path}")
+            print(f"epoch {epoch}: {step} steps, loss {loss:.4f}{parts}, checkpoint {path}")
             continue
         # trainer.py:716-766: validate, step the LR schedule on val_loss, best or plain checkpoint, early stop
         val_metrics = validate(model, val_batches, tokenizer.pad_token_id, int(ecfg.get("bleu_batches", 10)),
@@ -346,13 +384,15 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
         if ecfg.get("save_basic_metrics", False):                           # trainer.py:645-661
             _save_basic_metrics(os.path.join(output_dir, experiment_name, "metrics"), epoch, val_metrics)
         extra = "".join(f", {k} {val_metrics[k]:.4f}" for k in ("bleu", "levenshtein") if k in val_metrics)
-        print(f"epoch {epoch}: {step} steps, loss {loss:.4f}, val_loss {val_metrics['val_loss']:.4f}, "
+        print(f"epoch {epoch}: {step} steps, loss {loss:.4f}{parts}, val_loss {val_metrics['val_loss']:.4f}, "
               f"val_acc {val_metrics['val_acc']:.4f}{extra}, lr {ts.lr:g}, checkpoint {path}")
         if stop:
             print(f"early stopping after {epoch} epochs ({stopper.patience_counter} epochs without improvement)")
             break
     out = {"loss": float(last["loss"]) if last is not None else None, "steps": step - step0, "global_step": step,
            "checkpoint": path}
+    if last is not None and "hard_loss" in last:
+        out.update(hard_loss=float(last["hard_loss"]), soft_loss=float(last["soft_loss"]))
     if val_metrics is not None:
         out.update(best_val_loss=stopper.best_val_loss, val_metrics=val_metrics)
     return out
@@ -527,6 +567,17 @@ def main(argv: Optional[List[str]] = None) -> int:
                         "the device; default: the config key data.decode, else host")
     t.add_argument("--train-kernel", choices=("auto", "batched"), default="auto",
                    help="(this package) decoder recurrences of a training step: auto, or the step-batched matrix-core ones")
+    t.add_argument("--teacher", action="append", default=[], metavar="CHECKPOINT",
+                   help="(this package) distil: train against the token distribution of this checkpoint; repeat the "
+                        "option for an ensemble of teachers (all of the student's vocabulary)")
+    t.add_argument("--teacher-weights", default=None, metavar="A,B,...",
+                   help="(this package) with --teacher: one weight per teacher checkpoint, in order (default: equal)")
+    t.add_argument("--teacher-rule", choices=("logprob", "prob"), default=None,
+                   help="(this package) with --teacher: how the teachers' distributions combine (default logprob)")
+    t.add_argument("--distill-alpha", type=float, default=None, metavar="A",
+                   help="(this package) with --teacher: weight of the data set's tokens in the loss, 0 .. 1 (default 0.5)")
+    t.add_argument("--distill-temperature", type=float, default=None, metavar="T",
+                   help="(this package) with --teacher: temperature of both distributions in the soft term (default 2.0)")
     e = sub.add_parser("evaluate", help="Evaluate the model on a dataset.")
     e.add_argument("checkpoint_path", help="Path to trained model checkpoint")
     e.add_argument("data_dir", help="Path to data directory")
@@ -579,6 +630,22 @@ def main(argv: Optional[List[str]] = None) -> int:
             ensemble_weights = _ensemble_weights(args.ensemble_weights, 1 + len(args.ensemble))
         except ValueError as exc:
             ap.error(str(exc))
+    distill_kw = {}
+    if args.command == "train":
+        if not args.teacher:
+            for name in ("teacher_weights", "teacher_rule", "distill_alpha", "distill_temperature"):
+                if getattr(args, name) is not None:
+                    ap.error(f"--{name.replace('_', '-')} needs --teacher")
+        else:
+            from .training.distill import check_distill_arguments
+            try:
+                weights = _ensemble_weights(args.teacher_weights, len(args.teacher), "--teacher-weights", "")
+                alpha, temperature = check_distill_arguments(0.5 if args.distill_alpha is None else args.distill_alpha,
+                                                             2.0 if args.distill_temperature is None else args.distill_temperature)
+            except ValueError as exc:
+                ap.error(str(exc))
+            distill_kw = dict(teacher=args.teacher, teacher_weights=weights, teacher_rule=args.teacher_rule or "logprob",
+                              distill_alpha=alpha, distill_temperature=temperature)
     if args.command == "evaluate" and not 1 <= args.errors_top <= 1024:
         ap.error("--errors-top must be 1 .. 1024")
     if args.command == "predict" and args.complete_arguments and args.beam_size > 0:
@@ -632,7 +699,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     try:
         train(args.config_path, args.experiment_name, args.checkpoint_path, args.data_dir, args.device, args.seed,
               args.synthetic_steps, args.synthetic_vocab, args.output_dir, args.synthetic_val_steps, args.augment,
-              args.data, args.decode, args.train_kernel)
+              args.data, args.decode, args.train_kernel, **distill_kw)
     except SystemExit:
         raise
     except Exception as exc:                                                # cli.py:247-250: failure -> exit code 1

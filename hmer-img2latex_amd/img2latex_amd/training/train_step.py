@@ -5,6 +5,8 @@
     loss = CrossEntropyLoss(ignore_index=PAD, label_smoothing=0.1)   :111-115,335-336
     loss.backward(); clip_grad_norm_(5.0); Adam(lr, weight_decay).step(); zero_grad   :337-343
 
+(with ``teacher=``: the distillation loss of training/distill.py in place of the plain cross entropy)
+
 run entirely with the HIP kernels: training forward of encoder and decoder, fused CE, BPTT,
 conv/linear backward writing straight into ONE flat gradient buffer, one all-reduce of that
 buffer when data-parallel, then a fused clip + Adam over the flat parameter buffer.  No host
@@ -32,7 +34,19 @@ def step_seed(seed: int, step: int, rank: int, micro: int) -> int:
 class TrainStep:
     def __init__(self, model, lr: float = 1e-3, weight_decay: float = 1e-4, clip_grad_norm: float = 5.0,
                  pad_token_id: int = 0, label_smoothing: float = 0.1, betas=(0.9, 0.999), eps: float = 1e-8,
-                 process_group=None, seed: int = 0, overlap_all_reduce: bool = True, side_wgrad: bool = True):
+                 process_group=None, seed: int = 0, overlap_all_reduce: bool = True, side_wgrad: bool = True,
+                 teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 2.0):
+        # teacher (training/distill.py: Teacher, or None): the loss becomes distill_alpha x today's cross entropy +
+        # (1 - distill_alpha) x temperature^2 KL(teacher || student) at distill_temperature (i2l_ce_distill_fwd_bwd).  With
+        # None nothing changes: the same entry is called with the same arguments.  Refused before anything else is looked at
+        self.teacher = teacher
+        if teacher is not None:
+            from .distill import Teacher, check_distill_arguments
+            if not isinstance(teacher, Teacher):
+                raise TypeError("img2latex_amd: TrainStep(teacher=...) takes a training.distill.Teacher "
+                                f"(wrap the model: Teacher(model)), got {type(teacher).__name__}")
+            self.distill_alpha, self.distill_temperature = check_distill_arguments(distill_alpha, distill_temperature)
+            teacher.check_vocab(model.vocab_size)
         self.model = model
         self.lr, self.weight_decay, self.clip = lr, weight_decay, clip_grad_norm
         self.pad, self.smoothing, self.betas, self.eps = pad_token_id, label_smoothing, betas, eps
@@ -68,6 +82,10 @@ class TrainStep:
         self.exp_avg = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self.stats = torch.zeros(4, dtype=torch.float32, device=dev)
+        # distillation only: [sum of hard, sum of soft] of the last forward_backward, unweighted, and its non-PAD count;
+        # this rank's own rows (never all-reduced)
+        self.loss_parts = torch.zeros(2, dtype=torch.float32, device=dev) if teacher is not None else None
+        self._parts_count = None
         self.grad_views: Dict[str, torch.Tensor] = {}
         with torch.no_grad():
             for name, p in named:
@@ -98,7 +116,8 @@ class TrainStep:
     # ------------------------------------------------------------------
     def forward_backward(self, images: torch.Tensor, formulas: torch.Tensor) -> torch.Tensor:
         """Training forward + backward for this rank's shard; fills flat_grads (gradient of the SUM of the
-        per-token losses), flat_grads[n] = loss sum, flat_grads[n+1] = non-PAD count.  Returns logits."""
+        per-token losses), flat_grads[n] = loss sum, flat_grads[n+1] = non-PAD count.  Returns logits.  With a teacher
+        the loss is the distillation loss and ``loss_parts`` holds its two unweighted sums."""
         model = self.model
         L = _lib.lib()
         formulas = formulas.to(torch.int32) if formulas.dtype != torch.int32 else formulas
@@ -110,12 +129,15 @@ class TrainStep:
         logits, dec_state = decoder_train_forward(model.decoder, enc, tokens_in, self.step_seed)
         V = logits.shape[-1]
         dlogits = torch.empty_like(logits)
-        nbytes = L.i2l_ce_workspace_bytes(B * T)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
-        _lib.check(L.i2l_ce_label_smooth_fwd_bwd(logits.data_ptr(), targets.data_ptr(), B * T, V, self.pad,
-                                                 self.smoothing, ws.data_ptr(), nbytes, dlogits.data_ptr(),
-                                                 self.flat_grads.data_ptr() + 4 * self.n, _lib.stream_ptr()),
-                   "ce_label_smooth_fwd_bwd")
+        if self.teacher is None:
+            nbytes = L.i2l_ce_workspace_bytes(B * T)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+            _lib.check(L.i2l_ce_label_smooth_fwd_bwd(logits.data_ptr(), targets.data_ptr(), B * T, V, self.pad,
+                                                     self.smoothing, ws.data_ptr(), nbytes, dlogits.data_ptr(),
+                                                     self.flat_grads.data_ptr() + 4 * self.n, _lib.stream_ptr()),
+                       "ce_label_smooth_fwd_bwd")
+        else:
+            self._distill_loss(images, formulas, logits, targets, dlogits)
         dgr = {n[len("decoder."):]: g for n, g in self.grad_views.items() if n.startswith("decoder.")}
         # weight gradients feed nothing in the backward chain: they go to this object's side lanes and fill the launch
         # gaps and tile tails of the data-gradient chain; the join at the end of this method orders them before the
@@ -149,6 +171,35 @@ class TrainStep:
         self._join_side()          # flat_grads is complete for whatever the current stream does next (all-reduce, Adam, a reader)
         return logits
 
+    def _distill_loss(self, images, formulas, logits, targets, dlogits) -> None:
+        """The teacher's logits for this batch and i2l_ce_distill_fwd_bwd: sum and count where the plain loss puts them
+        (flat_grads[n], [n+1]), the two parts in ``loss_parts``."""
+        L = _lib.lib()
+        B, T, V = logits.shape
+        rows = self.teacher.logits(images, formulas)
+        records = (_lib.DistillTeacher * len(rows))()
+        for m, lg in enumerate(rows):
+            if tuple(lg.shape) != (B, T, V) or not lg.is_cuda:
+                raise RuntimeError(f"img2latex_amd: teacher member {m} gave logits {tuple(lg.shape)} on {lg.device}, the "
+                                   f"student's are {(B, T, V)} on {logits.device}")
+            records[m] = _lib.DistillTeacher(lg.data_ptr(), lg.stride(1), self.teacher.weights[m])
+        nbytes = L.i2l_ce_distill_workspace_bytes(B * T)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+        _lib.check(L.i2l_ce_distill_fwd_bwd(logits.data_ptr(), targets.data_ptr(), B * T, V, self.pad, self.smoothing,
+                                            records, len(rows), self.teacher.combine, self.distill_temperature,
+                                            self.distill_alpha, ws.data_ptr(), nbytes, dlogits.data_ptr(),
+                                            self.flat_grads.data_ptr() + 4 * self.n, self.loss_parts.data_ptr(),
+                                            _lib.stream_ptr()), "ce_distill_fwd_bwd")
+        self._parts_count = self.flat_grads[self.n + 1].clone()      # this rank's count: apply() all-reduces the slot
+        del rows, records, ws                                        # stream-ordered: the allocator reuses them after the launch
+
+    def _loss_parts(self) -> Dict[str, torch.Tensor]:
+        """{} without a teacher; else the last forward_backward's hard and soft loss per non-PAD token (device tensors)."""
+        if self.teacher is None:
+            return {}
+        per_token = self.loss_parts / self._parts_count.clamp(min=1.0)
+        return dict(hard_loss=per_token[0], soft_loss=per_token[1])
+
     def _join_side(self, clear: bool = True) -> None:
         """The current stream waits for the side lanes' weight gradients (no-op when none are pending)."""
         if self._side_keep:
@@ -175,7 +226,8 @@ class TrainStep:
             torch.autograd.graph.increment_version(p)
 
     def step(self, images: torch.Tensor, formulas: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """trainer.py:303-343 for one batch.  Returns device tensors (no sync): loss, total_norm, count, skipped.
+        """trainer.py:303-343 for one batch.  Returns device tensors (no sync): loss, total_norm, count, skipped -- and
+        with a teacher ``hard_loss`` / ``soft_loss``, the two unweighted parts of the loss per non-PAD token of this rank.
         ``skipped`` is 1.0 when the gradients were not finite (e.g. a grouped recurrence kernel timed out on a shared
         GPU and poisoned its outputs with NaN): the fused clip + Adam kernel then leaves parameters and moments
         untouched -- on every rank, since the all-reduce spreads the NaN -- and the caller may simply repeat the
@@ -185,7 +237,7 @@ class TrainStep:
         self.apply()
         count = self.flat_grads[self.n + 1]
         return dict(loss=self.flat_grads[self.n] / count.clamp(min=1.0), total_norm=self.stats[0], count=count,
-                    skipped=self.stats[3])
+                    skipped=self.stats[3], **self._loss_parts())
 
     def micro_step(self, images: torch.Tensor, formulas: torch.Tensor, accumulation_steps: int, update: bool) -> Dict[str, torch.Tensor]:
         """Gradient accumulation, trainer.py:345-383 (the shipped configuration: accumulation_steps 4): every micro-batch
@@ -214,7 +266,7 @@ class TrainStep:
             self._accum = torch.zeros(self.n, dtype=torch.float32, device=self.flat_grads.device)
         self._accum.addcmul_(self.flat_grads[:self.n], inv.expand(self.n))
         self._micro += 1
-        out = dict(loss=tail[0] / tail[1].clamp(min=1.0), count=tail[1])
+        out = dict(loss=tail[0] / tail[1].clamp(min=1.0), count=tail[1], **self._loss_parts())
         if update:
             world = dist.get_world_size(self.group) if self._reducer._active() else 1
             self.flat_grads[:self.n].copy_(self._accum)

@@ -774,6 +774,39 @@ int i2l_ce_label_smooth_fwd_bwd(const float* logits, const int32_t* targets, int
                                 float label_smoothing, void* workspace, size_t workspace_bytes,
                                 float* dlogits_out, float* loss_sum_and_count_out, i2l_stream_t stream);
 
+/* Word-level distillation (this package; the reference trains on the data set's tokens alone): the loss above plus the
+ * divergence of the student's token distribution from that of n teachers, at every kept row, in one fused launch and an
+ * ordered sum -- no (rows, vocab) intermediate.  csrc/distill_rules.inc.h states the rule; per row with target t != pad_id,
+ * student logits x, teacher rows z_m, weights w_m (normalised to sum 1 as in i2l_ensemble_decode):
+ *   hard = (1-eps)(lse(x) - x[t]) + eps(lse(x) - mean_v x[v])      exactly i2l_ce_label_smooth_fwd_bwd's row loss
+ *   y    = the ensemble's row under `combine` (I2L_ENSEMBLE_LOGPROB / _PROB, csrc/ensemble_rules.inc.h); n == 1: y = z_0
+ *   q = softmax(y / temperature), p = softmax(x / temperature)     the temperature is applied to y, not to the members
+ *   soft = temperature^2 sum_v q[v](log q[v] - log p[v])           a term with q[v] == 0 is 0
+ *   row loss = alpha hard + (1 - alpha) soft
+ *   dlogits[v] = alpha (softmax(x)[v] - (1-eps)[v == t] - eps/vocab) + (1 - alpha) temperature (p[v] - q[v])
+ * loss_sum_and_count_out[0] = SUM of the row losses (alpha parts[0] + (1 - alpha) parts[1] up to rounding), [1] = the
+ * number of non-pad rows, an exact integer; parts_out (2 floats or NULL) = SUM of hard, SUM of soft, unweighted;
+ * dlogits_out (rows, vocab) or NULL = gradient of the SUM, as above.  The three sums are fixed-order double sums:
+ * deterministic, and the same with and without dlogits_out / parts_out.
+ * A pad row adds exactly 0 to every sum and has exactly zero dlogits; it is selected, not multiplied: neither the
+ * student's nor the teachers' values at pad rows are read, so a NaN there reaches no output.  Teacher logits at kept rows
+ * must be finite (-inf or NaN there is outside the rule); a NaN in the student's row gives NaN sums, after which
+ * i2l_grad_clip_adam_step skips the update.  Teacher m's logits are (rows, ld) with ld >= vocab.
+ * Accepted: 1 <= n <= I2L_MAX_ENSEMBLE, combine one of the two rules, weights finite and > 0, temperature finite and > 0,
+ * 0 <= alpha <= 1, rows >= 1, every vocab >= 1 (a row longer than 512 columns is re-read, not refused).  Anything else is
+ * I2L_ERR_ARG, a short workspace I2L_ERR_WORKSPACE; both are answered by host code before the first HIP call and leave
+ * every output untouched. */
+typedef struct i2l_distill_teacher {
+    const float* logits;   /* (rows, ld) */
+    int ld;                /* >= vocab */
+    float weight;
+} i2l_distill_teacher;
+size_t i2l_ce_distill_workspace_bytes(int rows);
+int i2l_ce_distill_fwd_bwd(const float* logits, const int32_t* targets, int rows, int vocab, int pad_id,
+                           float label_smoothing, const i2l_distill_teacher* teachers, int n, int combine,
+                           float temperature, float alpha, void* workspace, size_t workspace_bytes,
+                           float* dlogits_out, float* loss_sum_and_count_out, float* parts_out, i2l_stream_t stream);
+
 /* clip_grad_norm_(max_norm) + Adam(lr, betas, eps, coupled L2 weight_decay) over flat fp32 buffers of
  * n elements (trainer.py:91-93,338-342).  grads hold the gradient of the SUM loss; count_ptr (device,
  * may be NULL = 1) is the number of non-pad target tokens the sum runs over (the GLOBAL count after the
