@@ -226,7 +226,24 @@ __global__ __launch_bounds__(MT) void sequence_metrics_bp_kernel(const int32_t* 
     if (tid < 2 && tla_out) tla_out[(size_t)pair * 2 + tid] = cnt[4 + tid];
 }
 
-// masked_accuracy (metrics.py:226-238): one wave per row: first-index arg max over V, compare, mask; integer counts.
+// torch.argmax order: NaN above everything, then the larger value, then the smaller index.  Started from
+// (-inf, INT_MAX), a row of -inf only ends at index 0.  masked_accuracy_kernel and tfe_rows_kernel both choose by it.
+__device__ __forceinline__ bool argmax_better(float x, int i, float bv, int bi) {
+    const bool xn = x != x, bn = bv != bv;
+    if (xn || bn) return xn && (!bn || i < bi);
+    return x > bv || (x == bv && i < bi);
+}
+
+__device__ __forceinline__ void wave_argmax(float& bv, int& bi) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        if (argmax_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+}
+
+// masked_accuracy (metrics.py:226-238): one wave per row: torch.argmax's arg max over V, compare, mask; integer counts.
 __global__ __launch_bounds__(MT) void masked_accuracy_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
                                                              long rows, int V, long pad_id,
                                                              unsigned long long* __restrict__ out) {
@@ -240,14 +257,9 @@ __global__ __launch_bounds__(MT) void masked_accuracy_kernel(const float* __rest
         int bi = 0x7fffffff;
         for (int v = lane; v < V; v += 64) {
             const float x = p[v];
-            if (x > bv) { bv = x; bi = v; }
+            if (argmax_better(x, v, bv, bi)) { bv = x; bi = v; }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ov = __shfl_xor(bv, off);
-            const int oi = __shfl_xor(bi, off);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
+        wave_argmax(bv, bi);
         if (lane == 0) {
             const int64_t t = targets[row];
             if (t != pad_id) {
@@ -305,22 +317,6 @@ __global__ __launch_bounds__(MT) void compact_ids_kernel(const int32_t* __restri
 constexpr int TFE_WAVES = 4;
 constexpr int TFE_REG_V = 2048;         // 64 lanes x 32 floats
 constexpr int TFE_FIN = 1024;           // threads of the finishing workgroup
-
-// torch.argmax order: NaN above everything, then the larger value, then the smaller index
-__device__ __forceinline__ bool tfe_better(float x, int i, float bv, int bi) {
-    const bool xn = x != x, bn = bv != bv;
-    if (xn || bn) return xn && (!bn || i < bi);
-    return x > bv || (x == bv && i < bi);
-}
-
-__device__ __forceinline__ void tfe_wave_argmax(float& bv, int& bi) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(bv, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        if (tfe_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-}
 
 __device__ __forceinline__ float tfe_wave_sum(float v) {
 #pragma unroll
@@ -382,7 +378,7 @@ __global__ __launch_bounds__(64 * TFE_WAVES) void tfe_rows_kernel(const float* _
 #define TFE_IDX(k) (VEC ? 4 * (lane + 64 * ((k) >> 2)) + ((k) & 3) : lane + 64 * (k))
 #pragma unroll
         for (int k = 0; k < NE; ++k)
-            if (TFE_IDX(k) < V && tfe_better(r[k], TFE_IDX(k), bv, bi)) { bv = r[k]; bi = TFE_IDX(k); }
+            if (TFE_IDX(k) < V && argmax_better(r[k], TFE_IDX(k), bv, bi)) { bv = r[k]; bi = TFE_IDX(k); }
 #pragma unroll
         for (int k = 0; k < NE; ++k) m = fmaxf(m, r[k]);
         m = tfe_wave_max(m);
@@ -398,7 +394,7 @@ __global__ __launch_bounds__(64 * TFE_WAVES) void tfe_rows_kernel(const float* _
                 const float e[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (tfe_better(e[j], v + j, bv, bi)) { bv = e[j]; bi = v + j; }
+                    if (argmax_better(e[j], v + j, bv, bi)) { bv = e[j]; bi = v + j; }
                     tfe_online(e[j], m, s);
                     sx += e[j];
                 }
@@ -406,7 +402,7 @@ __global__ __launch_bounds__(64 * TFE_WAVES) void tfe_rows_kernel(const float* _
         } else {
             for (int v = lane; v < V; v += 64) {
                 const float e = x[v];
-                if (tfe_better(e, v, bv, bi)) { bv = e; bi = v; }
+                if (argmax_better(e, v, bv, bi)) { bv = e; bi = v; }
                 tfe_online(e, m, s);
                 sx += e;
             }
@@ -418,7 +414,7 @@ __global__ __launch_bounds__(64 * TFE_WAVES) void tfe_rows_kernel(const float* _
         }
     }
     sx = tfe_wave_sum(sx);
-    tfe_wave_argmax(bv, bi);
+    wave_argmax(bv, bi);
     if (lane == 0) {
         const int tgt = targets[row];
         const bool keep = tgt != pad_id;
@@ -426,7 +422,8 @@ __global__ __launch_bounds__(64 * TFE_WAVES) void tfe_rows_kernel(const float* _
         const float lse = m + logf(s);
         const float nll = lse - x[tg];
         const float smooth = lse - sx / (float)V;
-        row_loss[row] = keep ? (1.f - eps) * nll + eps * smooth : 0.f;
+        // eps == 0: no smoothing term, as in torch -- a -inf logit makes it +inf, and 0 * inf is NaN
+        row_loss[row] = !keep ? 0.f : eps > 0.f ? (1.f - eps) * nll + eps * smooth : nll;
         row_arg[row] = bi;
     }
 }

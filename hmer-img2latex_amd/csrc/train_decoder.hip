@@ -403,7 +403,8 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     if (tid == 0) {
         const float nll = lse - x[tg];
         const float smooth = lse - sx / (float)V;
-        row_loss[row] = keep ? (1.f - eps) * nll + eps * smooth : 0.f;
+        // eps == 0: no smoothing term, as in torch -- a -inf logit makes it +inf, and 0 * inf is NaN
+        row_loss[row] = !keep ? 0.f : eps > 0.f ? (1.f - eps) * nll + eps * smooth : nll;
         row_keep[row] = keep ? 1.f : 0.f;
     }
 }

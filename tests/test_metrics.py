@@ -70,6 +70,7 @@ def test_kernel_statistics_and_scores_vs_reference():
     for i, (p, t) in enumerate(zip(preds, tgts)):
         assert int(st["lev"][i]) == MO.levenshtein_raw(p, t), i
         assert st["match"][i].tolist() == MO.ngram_matches(p, t, 4), i
+        assert st["tla"][i].tolist() == list(MO.token_list_accuracy([p], [t], PAD)), i
     cm = M.calculate_metrics(preds, tgts)
     assert cm["bleu"] == d["calc"][0] and cm["levenshtein"] == d["calc"][1] and cm["batch_size"] == int(d["calc"][2])
     assert M.token_list_accuracy(preds, tgts, PAD) == tuple(d["tla"].tolist())
@@ -112,6 +113,7 @@ def test_device_id_matrices_and_long_sequences():
         p, t = P[i, : pl[i]].tolist(), T[i, : tl[i]].tolist()
         assert int(st["lev"][i]) == MO.levenshtein_raw(p, t), i
         assert st["match"][i].tolist() == MO.ngram_matches(p, t, 4), i
+        assert st["tla"][i].tolist() == list(MO.token_list_accuracy([p], [t], PAD)), i
 
 
 @pytest.mark.gpu
@@ -131,6 +133,7 @@ def test_very_long_sequences():
         p, t = P[i, : pl[i]].tolist(), T[i, : tl[i]].tolist()
         assert int(st["lev"][i]) == MO.levenshtein_raw(p, t), i
         assert st["match"][i].tolist() == MO.ngram_matches(p, t, 4), i
+        assert st["tla"][i].tolist() == list(MO.token_list_accuracy([p], [t], PAD)), i
 
 
 @pytest.mark.gpu
@@ -160,12 +163,99 @@ def test_bit_vector_levenshtein_block_boundaries(width):
             p, t = P[i, : pl[i]].tolist(), T[i, : tl[i]].tolist()
             assert int(st["lev"][i]) == MO.levenshtein_raw(p, t), (width, alpha, i, pl[i], tl[i])
             assert st["match"][i].tolist() == MO.ngram_matches(p, t, 4), (width, alpha, i)
+            assert st["tla"][i].tolist() == list(MO.token_list_accuracy([p], [t], PAD)), (width, alpha, i)
         st2 = M.device_sequence_statistics(torch.from_numpy(P).to(dev), torch.from_numpy(pl).to(dev),
                                            torch.from_numpy(T).to(dev), torch.from_numpy(tl).to(dev), 2, PAD, _max_len=width)
         for i in range(B):                                       # max_n below 4: the higher orders stay 0
             p, t = P[i, : pl[i]].tolist(), T[i, : tl[i]].tolist()
             assert st2["match"][i].tolist()[:2] == MO.ngram_matches(p, t, 2), (width, alpha, i)
             assert st2["match"][i].tolist()[2:] in ([], [0, 0]), (width, alpha, i)
+
+
+ODD_IDS = np.array([0, 1, 2, -1, -5, 2 ** 31 - 1], np.int32)   # 0 is what the n-gram window holds past a sequence's end
+HANDOVER_WIDTHS = [1, 64, 65, 256, 257, 300]                  # 256: the bit-vector kernel's last width, 257: the table kernel's first
+
+
+def _odd_id_pairs(width, B, seed):
+    """Pairs over ODD_IDS with lengths on and around the width, and: a pair that differs only where the shorter sequence
+    ends; a prediction that is a prefix of a target which goes on with zeros (what the window holds past the prediction's
+    end); the same the other way round; two sequences of zeros of unequal length."""
+    rng = np.random.default_rng(seed)
+    P = ODD_IDS[rng.integers(0, len(ODD_IDS), size=(B, width))]
+    T = ODD_IDS[rng.integers(0, len(ODD_IDS), size=(B, width))]
+    lens = sorted(l for l in {0, 1, 2, 3, 4, width // 2, width - 1, width} if 0 <= l <= width)
+    pl = np.array([lens[i % len(lens)] for i in range(B)], np.int32)
+    tl = np.array([lens[(i * 5 + 3) % len(lens)] for i in range(B)], np.int32)
+    k = max(width - 3, 1)
+    T[0] = P[0]
+    T[0, k - 1] = -5 if P[0, k - 1] != -5 else 1              # equal up to the last token of the shorter one
+    pl[0], tl[0] = k, width
+    T[1] = P[1]
+    T[1, k:] = 0
+    pl[1], tl[1] = k, width
+    P[2] = T[2]
+    P[2, k:] = 0
+    pl[2], tl[2] = width, k
+    P[3] = T[3] = 0
+    pl[3], tl[3] = width, max(width - 2, 0)
+    T[4] = P[4]
+    pl[4] = tl[4] = width
+    return P, pl, T, tl
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", HANDOVER_WIDTHS)
+def test_sequence_metrics_odd_ids_and_pads_inside_sequences(width):
+    """Ids 0, negative and 2**31 - 1, pad ids 0, 2 and -1 with pad tokens inside targets and predictions, at the widths
+    on both sides of the hand-over between the two kernels: lev, match for max_n 1..4 and tla equal the oracle's."""
+    from img2latex_amd.training import metrics as M
+    dev = torch.device("cuda:0")
+    B = 12
+    P, pl, T, tl = _odd_id_pairs(width, B, seed=300 + width)
+    seqs = [(P[i, : pl[i]].tolist(), T[i, : tl[i]].tolist()) for i in range(B)]
+    lev = [MO.levenshtein_raw(p, t) for p, t in seqs]
+    match = [MO.ngram_matches(p, t, 4) for p, t in seqs]
+    dP, dpl, dT, dtl = (torch.from_numpy(a).to(dev) for a in (P, pl, T, tl))
+    for pad in (0, 2, -1):
+        for n in (1, 2, 3, 4):
+            st = M.device_sequence_statistics(dP, dpl, dT, dtl, n, pad, _max_len=width)
+            for i, (p, t) in enumerate(seqs):
+                assert int(st["lev"][i]) == lev[i], (width, pad, n, i)
+                assert st["match"][i].tolist() == match[i][:n] + [0] * (4 - n), (width, pad, n, i)
+                assert st["tla"][i].tolist() == list(MO.token_list_accuracy([p], [t], pad)), (width, pad, n, i)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", HANDOVER_WIDTHS)
+def test_sequence_metrics_clamps_lengths_through_the_c_abi(width):
+    """Lengths of max_len + 5 and -3 through the C ABI, rows wider than max_len with ids behind every length: the
+    statistics of the sequences cut to max_len, and of empty sequences for the negative lengths."""
+    from img2latex_amd import _lib
+    dev = torch.device("cuda:0")
+    B, stride_p, stride_t = 8, width + 9, width + 6
+    rng = np.random.default_rng(500 + width)
+    P = ODD_IDS[rng.integers(0, len(ODD_IDS), size=(B, stride_p))]
+    T = ODD_IDS[rng.integers(0, len(ODD_IDS), size=(B, stride_t))]
+    T[2, :width] = P[2, :width]
+    T[3, :width] = P[3, :width]
+    pl = np.array([width + 5, width + 5, width + 5, width // 2, -3, -3, width, -3], np.int32)
+    tl = np.array([width + 5, width // 2, width + 5, width + 5, width + 5, -3, -3, width // 2], np.int32)
+    dP, dpl, dT, dtl = (torch.from_numpy(a).to(dev) for a in (P, pl, T, tl))
+    seqs = [(P[i, : min(max(pl[i], 0), width)].tolist(), T[i, : min(max(tl[i], 0), width)].tolist()) for i in range(B)]
+    want = [(MO.levenshtein_raw(p, t), MO.ngram_matches(p, t, 4)) for p, t in seqs]
+    for pad in (0, 2, -1):
+        lev = torch.full((B,), -7, dtype=torch.int32, device=dev)
+        match = torch.full((B, 4), -7, dtype=torch.int32, device=dev)
+        tla = torch.full((B, 2), -7, dtype=torch.int32, device=dev)
+        rc = _lib.lib().i2l_sequence_metrics(dP.data_ptr(), dpl.data_ptr(), stride_p, dT.data_ptr(), dtl.data_ptr(),
+                                             stride_t, B, width, 4, pad, lev.data_ptr(), match.data_ptr(), tla.data_ptr(),
+                                             _lib.stream_ptr())
+        assert rc == 0, rc
+        torch.cuda.synchronize()
+        lev, match, tla = lev.cpu(), match.cpu(), tla.cpu()
+        for i, (p, t) in enumerate(seqs):
+            assert (int(lev[i]), match[i].tolist()) == want[i], (width, pad, i)
+            assert tla[i].tolist() == list(MO.token_list_accuracy([p], [t], pad)), (width, pad, i)
 
 
 def test_scores_host_helper_is_bit_identical_to_the_python_formulas():

@@ -457,6 +457,35 @@ def test_ce_extreme_logits(V):
 
 
 @gpu
+@pytest.mark.parametrize("V", [65, 513])
+def test_ce_minus_inf_logits(V):
+    """-inf logits (a masked vocabulary).  Smoothing 0 has no smoothing term, as in torch: with -inf in non-target
+    columns only, the loss sum and the gradient are finite and within the float64 bounds (the floor without the mean
+    logit, which the loss then does not contain); with -inf at a kept target the sum is +inf.  Smoothing 0.1: +inf."""
+    gen = torch.Generator().manual_seed(31 + V)
+    rows = 9
+    logits = torch.randn(rows, V, generator=gen) * 3
+    tgt = torch.randint(4, V - 1, (rows,), generator=gen)
+    tgt[tgt == V // 2 - 20] = 5
+    tgt[1::5] = 0
+    logits[:, 1], logits[::2, V // 2 - 20], logits[3, V - 1] = -math.inf, -math.inf, -math.inf
+    logits[1, 2:] = -math.inf                                           # a pad row, all but one logit masked
+    out, d = ce_call(logits, tgt, 0, 0.0)
+    keep = tgt != 0
+    loss64, d64 = ce_ref(logits, tgt, 0, 0.0, F64)
+    loss32, d32 = ce_ref(logits, tgt, 0, 0.0, F32)
+    assert math.isfinite(loss64) and float(out[1]) == float(keep.sum())
+    assert torch.isfinite(out).all() and torch.isfinite(d).all()
+    judge("ce -inf dlogits", (d.double() - d64).abs(), (d32.double() - d64).abs(), 2.0 ** -22, V, share="row")
+    x64 = logits.double()
+    mag = ((torch.logsumexp(x64, 1).abs() + x64.gather(1, tgt[:, None])[:, 0].abs()) * keep).sum()
+    judge("ce -inf loss sum", abs(float(out[0]) - loss64), abs(loss32 - loss64), 2.0 ** -21 * float(mag), V)
+    assert ce_ref(logits, tgt, 0, 0.1, F64)[0] == math.inf and float(ce_call(logits, tgt, 0, 0.1)[0][0]) == math.inf
+    logits[4, tgt[4]] = -math.inf                                       # -inf at a kept target
+    assert ce_ref(logits, tgt, 0, 0.0, F64)[0] == math.inf and float(ce_call(logits, tgt, 0, 0.0)[0][0]) == math.inf
+
+
+@gpu
 def test_ce_refusals():
     L = _lib.lib()
     rows, V = 9, 33
