@@ -28,6 +28,14 @@ PLAN_DTYPE = np.dtype([("src_offset", "<i8"), ("tmp_offset", "<i8"), ("bh_offset
                        ("kh_ksize", "<i4"), ("kv_ksize", "<i4")])
 assert PLAN_DTYPE.itemsize == 88
 
+# How far an axis may shrink.  Output sample x sums up to 2 * support * in / out source samples ("taps"), held in a table
+# row of ksize = 2 * ceil(support * in / out) + 1 weights (support 3 for LANCZOS, 2 for BICUBIC).  The host builder
+# (i2l_resample_coeffs) keeps one sample's weights in 512 doubles on its stack and returns I2L_ERR_UNSUPPORTED for more
+# (LANCZOS past ~85x, BICUBIC past ~128x); the device builder has no such buffer and is held to rows of 1024 weights
+# (LANCZOS ~170x, BICUBIC ~255x).  Between the two, ``tables="device"`` resamples and ``tables="host"`` refuses.
+HOST_MAX_TAPS = 512
+DEVICE_MAX_KSIZE = 1024
+
 
 class _TablePool:
     """Resampling tables resident on the device, one per (source size, target size, filter), shared by every image
@@ -67,8 +75,13 @@ class _TablePool:
             ins = np.array([missing[i][0] for i in sel], np.int32)
             outs = np.array([missing[i][1] for i in sel], np.int32)
             o = np.ascontiguousarray(offs[sel])
-            _lib.check(L.i2l_resample_coeffs_batch(flt, len(sel), ins.ctypes.data, outs.ctypes.data, o.ctypes.data,
-                                                   host.data_ptr(), min(16, os.cpu_count() or 1)), "resample_coeffs_batch")
+            rc = L.i2l_resample_coeffs_batch(flt, len(sel), ins.ctypes.data, outs.ctypes.data, o.ctypes.data,
+                                             host.data_ptr(), min(16, os.cpu_count() or 1))
+            if rc == _lib.ERR_UNSUPPORTED:                        # nothing of this request has entered the pool
+                raise ValueError(f"tables=\"host\" builds at most {HOST_MAX_TAPS} taps per output sample and an axis of "
+                                 f"this batch shrinks by more than that allows; tables=\"device\" takes table rows of "
+                                 f"up to {DEVICE_MAX_KSIZE} weights")
+            _lib.check(rc, "resample_coeffs_batch")
         hv = host.numpy()
         for (key, k, off) in zip(missing, ks, offs.tolist()):
             b = key[1]
@@ -176,8 +189,9 @@ def _plan_batch(shapes: np.ndarray, out_h: int, channels: int, keep_aspect: bool
         t_in = np.concatenate([w, h]).astype(np.int32)
         t_out = np.concatenate([new_w, np.full(n, out_h, np.int64)]).astype(np.int32)
         ks = _ksizes(flt, t_in, t_out)
-        if int(ks.max()) > 2 * 512:
-            raise ValueError("down-scaling by more than ~80x is not supported")
+        if int(ks.max()) > DEVICE_MAX_KSIZE:
+            raise ValueError(f"an axis of this batch shrinks by more than table rows of {DEVICE_MAX_KSIZE} weights allow "
+                             f"(it needs {int(ks.max())})")
         t_size = t_out.astype(np.int64) * (2 + ks)
         t_off = np.zeros(2 * n, np.int64)
         t_off[1:] = np.cumsum(t_size[:-1])

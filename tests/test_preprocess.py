@@ -137,7 +137,9 @@ def test_device_built_tables_equal_the_host_tables():
     i2l_resample_coeffs (host, libm = Pillow's arithmetic) for ~700 (source, target) sizes and both filters: every bound and
     every 22-bit weight.  The device's sin() is not libm's, so a weight MAY differ by one unit where the normalised value
     sits within ~1e-16 of a rounding boundary (odds ~1e-9 per weight): equality is asserted, and a ragged batch goes through
-    preprocess_batch with device-built and with host-built tables bit-identically."""
+    preprocess_batch with device-built and with host-built tables bit-identically.  The bicubic fixed-size batch at the end
+    compares the library with itself (the two table builders); that path against Pillow -- every pass, mode conversion
+    and channel count of it -- is tests/test_preprocess_paths.py's."""
     from img2latex_amd.data import preprocess_batch
     from img2latex_amd.data.preprocess import _ksizes
     L = _lib.lib()
