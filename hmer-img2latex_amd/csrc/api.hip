@@ -2,7 +2,7 @@
 #include "common.h"
 #include <new>
 
-extern "C" int i2l_version(void) { return 117; }
+extern "C" int i2l_version(void) { return 118; }
 
 extern "C" const char* i2l_error_string(int code) {
     switch (code) {

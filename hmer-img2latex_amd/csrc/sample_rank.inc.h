@@ -13,12 +13,10 @@
 // where a workgroup per image would walk its 256 distances on one.  d(i, j) and d(j, i) are both computed; that spares
 // an exchange between workgroups, and there is no poll, no atomic and no cooperative launch.
 //
-// The distance is Myers' bit-vector algorithm in blocks of 64 tokens, as metrics.hip's sequence_metrics_bp_kernel walks
-// it (J. ACM 46(3) 1999; global-distance boundary as in Hyyro 2003): sample i's tokens sit in registers, lane = place
-// within a block, W blocks; per token of sample j a ballot yields the match mask of a block and ~20 scalar bit
-// operations its new vertical deltas and the carry into the next block.  Sample j's tokens sit in registers too and are
-// read lane by lane, so the kernel touches no LDS but the 16 distances of its row.  Exact: integers throughout.  Every
-// loop is bounded by steps <= 64 W.
+// The distance is myers_wave.inc.h's wave_edit_distance (Myers' bit-vector algorithm in blocks of 64 tokens; the risk
+// objective's i2l_risk_rows calls the same function): both samples' tokens sit in registers, so the kernel touches no
+// LDS but the 16 distances of its row.  Exact: integers throughout.  Every loop is bounded by steps <= 64 W.
+#include "myers_wave.inc.h"
 
 constexpr int SRK_NT = 64 * SR_MAX_SAMPLES;
 
@@ -56,46 +54,7 @@ __global__ __launch_bounds__(SRK_NT) void sample_distance_kernel(RankParams p) {
     }
     const SrCut ca = sr_cut_at(fa, T);
     const int R = ca.n, C = sr_cut_at(fb, T).n;
-    int d = R;
-    if (R == 0) d = C;
-    else if (C > 0) {
-        bool ok[W];
-        u64 Pv[W], Mv[W];
-#pragma unroll
-        for (int w = 0; w < W; ++w) { ok[w] = 64 * w + lane < R; Pv[w] = ~0ull; Mv[w] = 0ull; }
-        const int last = (R - 1) >> 6;
-        const u64 high = 1ull << ((R - 1) & 63);
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            const int nk = min(64, C - 64 * k);          // tokens of sample j in its block k
-            for (int jj = 0; jj < nk; ++jj) {
-                const int t = __builtin_amdgcn_readlane(tb[k], jj);
-                int hin = 1;                             // D[0][j] - D[0][j-1] = +1: global distance
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    if (w <= last) {
-                        u64 Eq = __ballot(ok[w] && pa[w] == t);
-                        const u64 pv = Pv[w], mv = Mv[w];
-                        const u64 Xv = Eq | mv;
-                        if (hin < 0) Eq |= 1ull;
-                        const u64 Xh = (((Eq & pv) + pv) ^ pv) | Eq;
-                        u64 Ph = mv | ~(Xh | pv);
-                        u64 Mh = pv & Xh;
-                        const u64 hb = w == last ? high : (1ull << 63);
-                        const int hout = (Ph & hb) ? 1 : ((Mh & hb) ? -1 : 0);
-                        Ph <<= 1;
-                        Mh <<= 1;
-                        if (hin < 0) Mh |= 1ull;
-                        else if (hin > 0) Ph |= 1ull;
-                        Pv[w] = Mh | ~(Xv | Ph);
-                        Mv[w] = Ph & Xv;
-                        hin = hout;
-                    }
-                }
-                d += hin;                                // D[R][j+1] - D[R][j]
-            }
-        }
-    }
+    const int d = wave_edit_distance<W>(pa, R, tb, C, lane);
     if (lane == 0) {
         drow[j] = d;
         if (p.dist) p.dist[((size_t)img * S + i) * S + j] = d;

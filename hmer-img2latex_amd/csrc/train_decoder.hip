@@ -362,52 +362,7 @@ __global__ __launch_bounds__(NT) void lstm_train_bwd_kernel(BwdBuf p) {
 #include "train_batched.inc.h"
 
 // ------------------------------------------------------------------ cross entropy with label smoothing
-// One workgroup per (b,t) row.  row_loss = keep * ((1-eps)*nll + eps*(-mean_v logp));
-// dlogits = keep * (softmax - (1-eps)*onehot - eps/V)   [gradient of the SUM over rows; the mean's 1/count
-// is applied later so that data-parallel ranks can all-reduce un-normalised sums].
-__global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits,
-                                                      const int32_t* __restrict__ targets, float* __restrict__ dlogits,
-                                                      float* __restrict__ row_loss, float* __restrict__ row_keep, int V,
-                                                      int pad_id, float eps) {
-    __shared__ float red[8];
-    const size_t row = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* x = logits + row * V;
-    const int tgt = targets[row];
-    float m = -INFINITY;
-    for (int v = tid; v < V; v += 256) m = fmaxf(m, x[v]);
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    if (lane == 0) red[wave] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float s = 0.f, sx = 0.f;
-    for (int v = tid; v < V; v += 256) { s += expf(x[v] - m); sx += x[v]; }
-    for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off, 64); sx += __shfl_xor(sx, off, 64); }
-    if (lane == 0) { red[wave] = s; red[4 + wave] = sx; }
-    __syncthreads();
-    s = (red[0] + red[1]) + (red[2] + red[3]);
-    sx = (red[4] + red[5]) + (red[6] + red[7]);
-    const float lse = m + logf(s);
-    const bool keep = tgt != pad_id;
-    const int tg = min(max(tgt, 0), V - 1);
-    if (dlogits) {
-        float* d = dlogits + row * V;
-        const float base = eps / (float)V;
-        // softmax as exp(x - max) / sum, not exp(x - lse): lse is rounded to ulp(|lse|), which at |logits| ~ 1e4 is 1e-3
-        for (int v = tid; v < V; v += 256) {
-            float g = expf(x[v] - m) / s - base - (v == tg ? (1.f - eps) : 0.f);
-            d[v] = keep ? g : 0.f;
-        }
-    }
-    if (tid == 0) {
-        const float nll = lse - x[tg];
-        const float smooth = lse - sx / (float)V;
-        // eps == 0: no smoothing term, as in torch -- a -inf logit makes it +inf, and 0 * inf is NaN
-        row_loss[row] = !keep ? 0.f : eps > 0.f ? (1.f - eps) * nll + eps * smooth : nll;
-        row_keep[row] = keep ? 1.f : 0.f;
-    }
-}
+#include "ce_rows.inc.h"
 
 // out[0] = sum(row_loss), out[1] = sum(row_keep): one workgroup, fixed order -> deterministic.
 __global__ __launch_bounds__(256) void ordered_sum2_kernel(const float* __restrict__ a, const float* __restrict__ b,
@@ -799,8 +754,8 @@ extern "C" int i2l_ce_label_smooth_fwd_bwd(const float* logits, const int32_t* t
     float* row_loss = static_cast<float*>(workspace);
     float* row_keep = reinterpret_cast<float*>(static_cast<char*>(workspace) + i2l_align((size_t)rows * sizeof(float)));
     hipStream_t s = i2l_s(stream);
-    hipLaunchKernelGGL(ce_rows_kernel, dim3(rows), dim3(256), 0, s, logits, targets, dlogits_out, row_loss, row_keep,
-                       vocab, pad_id, label_smoothing);
+    hipLaunchKernelGGL(ce_rows_kernel<false>, dim3(rows), dim3(256), 0, s, logits, targets, dlogits_out, row_loss, row_keep,
+                       vocab, pad_id, label_smoothing, CeSeq{});
     I2L_CHECK_LAUNCH();
     hipLaunchKernelGGL(ordered_sum2_kernel, dim3(1), dim3(256), 0, s, (const float*)row_loss, (const float*)row_keep,
                        (size_t)rows, loss_sum_and_count_out);

@@ -26,7 +26,7 @@ ENSEMBLE_LOGPROB, ENSEMBLE_PROB = 0, 1            # I2L_ENSEMBLE_*: the combinat
 CONSTRAIN_NONE, CONSTRAIN_BRACKETS, CONSTRAIN_ARGUMENTS = 0, 1, 2   # I2L_CONSTRAIN_*: the kind of its class table
 RANK_CONSENSUS, RANK_LOGPROB = 0, 1               # I2L_RANK_*: the order of i2l_sample_decode_multi / i2l_sample_rank
 MAX_RANK_STEPS = 1024                             # I2L_MAX_RANK_STEPS
-ABI_VERSION = 117                                # the i2l_version() this binding was written against (csrc/api.hip)
+ABI_VERSION = 118                                # the i2l_version() this binding was written against (csrc/api.hip)
 # kernel-selection flags (include/img2latex_hip.h I2L_FLAG_*): explicit arguments, the library reads no environment
 FLAG_EXACT_FP32, FLAG_NO_GROUP, FLAG_RESNET_NO_RING, FLAG_RESNET_IM2COL_STEM = 0x1, 0x2, 0x4, 0x8
 FLAG_WEIGHTS_PACKED = 0x10          # conv forward: the workspace still holds the packed filters of these weights
@@ -200,6 +200,14 @@ _SIGNATURES = {
     "i2l_ce_distill_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, POINTER(DistillTeacher), c_int,
                                        c_int, c_float, c_float, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
+    # minimum-risk fine-tuning (csrc/train_risk.hip)
+    "i2l_risk_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "i2l_ce_weighted_workspace_bytes": (c_size_t, [c_int]),
+    "i2l_ce_weighted_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "i2l_rows_repeat": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "i2l_rows_fold": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _SIGNATURES.update({

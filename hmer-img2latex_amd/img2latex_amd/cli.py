@@ -15,6 +15,8 @@
                                   [--augment] [--data {auto,native,reference}] [--decode {host,device}]
                                   [--teacher CHECKPOINT ... --teacher-weights a,b,... --teacher-rule {logprob,prob}
                                    --distill-alpha A --distill-temperature T]  (this package: distillation)
+                                  [--risk-samples N --risk-alpha A --risk-temperature T --risk-top-k K --risk-top-p P]
+                                                                   (this package: minimum-risk fine-tuning)
     python -m img2latex_amd evaluate CHECKPOINT DATA_DIR [--split test] [--batch-size 32] [--num-samples N] [--errors]
                                                          [--beam-size 0] [--device cuda] [--output-dir outputs]
                                                          [--decode {host,device}]
@@ -226,12 +228,41 @@ def _synthetic_batches(config: Dict, steps: int, vocab_size: int, seed: int):
                "formulas": torch.from_numpy(synth.make_formulas(batch, length, vocab_size, seed=seed + s))}
 
 
+RISK_KEYS = ("samples", "alpha", "temperature", "top_k", "top_p")
+
+
+def _risk_objective(options: Optional[Dict], tcfg: Dict, tokenizer, has_teacher: bool):
+    """The RiskObjective of a ``train`` run, or None: ``options`` (the command line's, any of RISK_KEYS) over the config's
+    ``training.risk_<key>``.  It is on when ``samples`` is set in either place.  SystemExit for the other options without
+    it, for a teacher beside it and for values RiskObjective refuses."""
+    merged = {k: tcfg["risk_" + k] for k in RISK_KEYS if tcfg.get("risk_" + k) is not None}
+    merged.update({k: v for k, v in (options or {}).items() if v is not None})
+    unknown = sorted(set(merged) - set(RISK_KEYS))
+    if unknown:
+        raise SystemExit(f"img2latex_amd train: unknown risk option(s) {unknown}; expected {list(RISK_KEYS)}")
+    if not merged:
+        return None
+    if "samples" not in merged:
+        raise SystemExit(f"img2latex_amd train: risk option(s) {sorted(merged)} need --risk-samples (training.risk_samples)")
+    if has_teacher:
+        raise SystemExit("img2latex_amd train: --risk-samples with --teacher: the step takes a teacher or the risk "
+                         "objective, not both")
+    from .training import RiskObjective
+    try:
+        merged["samples"] = int(merged["samples"])
+        if "top_k" in merged:
+            merged["top_k"] = int(merged["top_k"])
+        return RiskObjective(int(tokenizer.start_token_id), int(tokenizer.end_token_id), **merged)
+    except (TypeError, ValueError) as exc:
+        raise SystemExit(f"img2latex_amd train: --risk-samples: {exc}")
+
+
 def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: str = "img2latex_v1",
           checkpoint_path: Optional[str] = None, data_dir: Optional[str] = None, device: Optional[str] = None,
           seed: int = 42, synthetic_steps: int = 0, synthetic_vocab: int = 512, output_dir: str = "outputs",
           synthetic_val_steps: int = 0, augment: bool = False, data: str = "auto", decode: Optional[str] = None,
           train_kernel: str = "auto", teacher=(), teacher_weights=None, teacher_rule: str = "logprob",
-          distill_alpha: float = 0.5, distill_temperature: float = 2.0) -> Dict:
+          distill_alpha: float = 0.5, distill_temperature: float = 2.0, risk: Optional[Dict] = None) -> Dict:
     """cli.py:104-250 reduced to the hot path: model from the config, optional resume, TrainStep over the batches, a
     checkpoint in the reference's layout (trainer.py:209-224) per epoch, and -- with validation batches -- the epoch-end
     validation / LR schedule / best checkpoint / early stop of trainer.py:713-766.  Returns {"loss", "steps",
@@ -244,7 +275,10 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
     of an ensemble (``teacher_weights`` one per path, ``teacher_rule`` "logprob" / "prob"); the student then trains on
     ``distill_alpha`` x the cross entropy + (1 - ``distill_alpha``) x the divergence from the teacher's token distribution
     at ``distill_temperature`` (training/distill.py).  Every teacher checkpoint's ``token_to_id`` must be the student's
-    tokenizer's (SystemExit naming the first differing token).  Validation is untouched: ``val_loss`` stays the hard loss."""
+    tokenizer's (SystemExit naming the first differing token).  Validation is untouched: ``val_loss`` stays the hard loss.
+    ``risk``: the options of minimum-risk fine-tuning (training/risk.py) given on the command line, a dict with any of
+    ``samples``, ``alpha``, ``temperature``, ``top_k``, ``top_p``; the config's ``training.risk_samples`` ... ``risk_top_p``
+    stand behind them.  The objective is on when ``samples`` is set in either place; it does not combine with a teacher."""
     import random
     from . import data as D
     from .training import EarlyStopping, PlateauSchedule, TokenTable, TrainStep, save_checkpoint, validate
@@ -305,6 +339,7 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
         except ValueError as exc:
             raise SystemExit(f"img2latex_amd train: --teacher: {exc}")
         _check_teacher_tokens(teacher, tables, tokenizer)
+    objective = _risk_objective(risk, tcfg, tokenizer, bool(teacher))
     model = build_model(config, tokenizer.vocab_size)
     if resume is not None:
         model.load_state_dict(resume["model_state_dict"])                   # trainer.py:253
@@ -314,7 +349,8 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
                    clip_grad_norm=float(tcfg.get("clip_grad_norm", 5.0)), pad_token_id=tokenizer.pad_token_id,
                    label_smoothing=0.1, seed=seed,                          # trainer.py:91-93,111-115
                    **(dict(teacher=distill, distill_alpha=distill_alpha, distill_temperature=distill_temperature)
-                      if distill is not None else {}))
+                      if distill is not None else {}),
+                   **(dict(risk=objective) if objective is not None else {}))
     if resume is not None and resume.get("optimizer_state_dict"):
         ts.load_optimizer_state_dict(resume["optimizer_state_dict"])        # trainer.py:255
     # trainer.py:257-258,697: a checkpoint's "epoch" is the number of COMPLETED epochs and "step" the global step; a resumed
@@ -346,6 +382,7 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
             batches.set_epoch(epoch - 1)                                    # the warp's key, as below
         it = iter(batches)
         batch, batch_idx, seen = next(it, None), 0, 0
+        reward_sum, reward_batches = 0.0, 0
         while batch is not None:
             nxt = next(it, None)                                            # one batch of look-ahead: "is this the last one?" (:374)
             images = batch["images"].to(dev)                                # data/utils.py:113-135 prepare_batch
@@ -357,11 +394,16 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
                 images = D.batch_convert_for_resnet(images)
             update = (batch_idx + 1) % accum == 0 or nxt is None
             last = ts.micro_step(images, batch["formulas"].to(dev), accum, update)
-            step += 1                                                       # the reference's global_step counts batches (:399)
+            if "reward" in last:                                            # summed on the device: no sync in the loop
+                reward_sum, reward_batches = reward_sum + last["reward"], reward_batches + 1
+            step += 1                                                      # the reference's global_step counts batches (:399)
             batch, batch_idx = nxt, batch_idx + 1
         loss = float(last["loss"]) if last is not None else float("nan")
         parts = ""
-        if last is not None and "hard_loss" in last:                       # distillation: the last batch's two parts
+        if last is not None and "reward" in last:                          # risk objective: the epoch's mean reward
+            parts = (f" (reward {reward_sum / max(1, reward_batches):.4f}, hard {float(last['hard_loss']):.4f}, "
+                     f"risk {float(last['risk_loss']):.4f})")
+        elif last is not None and "hard_loss" in last:                     # distillation: the last batch's two parts
             parts = f" (hard {float(last['hard_loss']):.4f}, soft {float(last['soft_loss']):.4f})"
         if val_batches is None:
             path = os.path.join(ck_dir, f"checkpoint_epoch_{epoch}_step_{step}.pt")
@@ -391,7 +433,10 @@ def train(config_path: str = "img2latex/configs/config.yaml", experiment_name: s
             break
     out = {"loss": float(last["loss"]) if last is not None else None, "steps": step - step0, "global_step": step,
            "checkpoint": path}
-    if last is not None and "hard_loss" in last:
+    if last is not None and "reward" in last:
+        out.update(reward=float(reward_sum) / max(1, reward_batches), hard_loss=float(last["hard_loss"]),
+                   risk_loss=float(last["risk_loss"]))
+    elif last is not None and "hard_loss" in last:
         out.update(hard_loss=float(last["hard_loss"]), soft_loss=float(last["soft_loss"]))
     if val_metrics is not None:
         out.update(best_val_loss=stopper.best_val_loss, val_metrics=val_metrics)
@@ -578,6 +623,18 @@ def main(argv: Optional[List[str]] = None) -> int:
                    help="(this package) with --teacher: weight of the data set's tokens in the loss, 0 .. 1 (default 0.5)")
     t.add_argument("--distill-temperature", type=float, default=None, metavar="T",
                    help="(this package) with --teacher: temperature of both distributions in the soft term (default 2.0)")
+    t.add_argument("--risk-samples", type=int, default=None, metavar="N",
+                   help="(this package) minimum-risk fine-tuning: draw N formulas per image from the model (2 .. 16) and "
+                        "train on them, weighted by their edit-distance reward, beside the gold formula; also the config "
+                        "key training.risk_samples.  Not with --teacher")
+    t.add_argument("--risk-alpha", type=float, default=None, metavar="A",
+                   help="(this package) with --risk-samples: weight of the gold formula's cross entropy, 0 .. 1 (default 0.5)")
+    t.add_argument("--risk-temperature", type=float, default=None, metavar="T",
+                   help="(this package) with --risk-samples: temperature of the draws (default 1.0)")
+    t.add_argument("--risk-top-k", type=int, default=None, metavar="K",
+                   help="(this package) with --risk-samples: draw from the K most likely tokens (default 0: no limit)")
+    t.add_argument("--risk-top-p", type=float, default=None, metavar="P",
+                   help="(this package) with --risk-samples: draw from the nucleus of mass P (default 0: no limit)")
     e = sub.add_parser("evaluate", help="Evaluate the model on a dataset.")
     e.add_argument("checkpoint_path", help="Path to trained model checkpoint")
     e.add_argument("data_dir", help="Path to data directory")
@@ -646,6 +703,19 @@ def main(argv: Optional[List[str]] = None) -> int:
                 ap.error(str(exc))
             distill_kw = dict(teacher=args.teacher, teacher_weights=weights, teacher_rule=args.teacher_rule or "logprob",
                               distill_alpha=alpha, distill_temperature=temperature)
+        risk = {k: getattr(args, "risk_" + k) for k in RISK_KEYS if getattr(args, "risk_" + k) is not None}
+        if risk:
+            # what needs neither the config nor the tokenizer is answered here, with the parser's exit; train() checks
+            # again once the config's keys are merged in
+            if args.teacher:
+                ap.error("--risk-samples with --teacher: the step takes a teacher or the risk objective, not both")
+            if "samples" in risk:
+                from .training.risk import RiskObjective
+                try:
+                    RiskObjective(1, 2, **risk)
+                except (TypeError, ValueError) as exc:
+                    ap.error(str(exc))
+            distill_kw = dict(distill_kw, risk=risk)
     if args.command == "evaluate" and not 1 <= args.errors_top <= 1024:
         ap.error("--errors-top must be 1 .. 1024")
     if args.command == "predict" and args.complete_arguments and args.beam_size > 0:

@@ -7,9 +7,10 @@ from .tokenizer import TokenizeTable, pack_texts, tokenize_image, tokenize_table
 from .vocab import VocabFit, fit_formulas_file, fit_vocabulary, split_lines
 from .train_step import TrainStep
 from .distill import Teacher
+from .risk import RiskObjective
 from .epoch_policy import EarlyStopping, PlateauSchedule
 from .validate import BleuSampler, ValidationTimeout, Validator, teacher_forced_eval, validate
 
-__all__ = ["TrainStep", "Teacher", "Predictor", "TokenTable", "DetokenizeTable", "detokenize_table", "token_image", "TokenizeTable", "tokenize_table", "tokenize_image", "pack_texts", "fit_vocabulary", "fit_formulas_file", "split_lines", "VocabFit", "save_checkpoint", "all_reduce_gradients", "shard_batch",
+__all__ = ["TrainStep", "Teacher", "RiskObjective", "Predictor", "TokenTable", "DetokenizeTable", "detokenize_table", "token_image", "TokenizeTable", "tokenize_table", "tokenize_image", "pack_texts", "fit_vocabulary", "fit_formulas_file", "split_lines", "VocabFit", "save_checkpoint", "all_reduce_gradients", "shard_batch",
            "calculate_metrics", "levenshtein_distance", "bleu_n_score", "masked_accuracy", "token_list_accuracy",
            "Validator", "BleuSampler", "validate", "teacher_forced_eval", "ValidationTimeout", "PlateauSchedule", "EarlyStopping", "BracketTable", "ArgumentTable"]

@@ -5,7 +5,8 @@
     loss = CrossEntropyLoss(ignore_index=PAD, label_smoothing=0.1)   :111-115,335-336
     loss.backward(); clip_grad_norm_(5.0); Adam(lr, weight_decay).step(); zero_grad   :337-343
 
-(with ``teacher=``: the distillation loss of training/distill.py in place of the plain cross entropy)
+(with ``teacher=``: the distillation loss of training/distill.py in place of the plain cross entropy; with ``risk=``: the
+minimum-risk objective of training/risk.py -- the decoder runs on the gold row and on N draws of every image)
 
 run entirely with the HIP kernels: training forward of encoder and decoder, fused CE, BPTT,
 conv/linear backward writing straight into ONE flat gradient buffer, one all-reduce of that
@@ -22,6 +23,7 @@ from .. import _lib
 from ..model._train_fn import (decoder_train_backward, decoder_train_forward, encoder_train_backward,
                                encoder_train_forward)
 from .dp import OverlappedAllReduce, broadcast_parameters, rank_of
+from .risk import RiskObjective, risk_seed, rows_fold, rows_repeat
 
 
 def step_seed(seed: int, step: int, rank: int, micro: int) -> int:
@@ -35,7 +37,7 @@ class TrainStep:
     def __init__(self, model, lr: float = 1e-3, weight_decay: float = 1e-4, clip_grad_norm: float = 5.0,
                  pad_token_id: int = 0, label_smoothing: float = 0.1, betas=(0.9, 0.999), eps: float = 1e-8,
                  process_group=None, seed: int = 0, overlap_all_reduce: bool = True, side_wgrad: bool = True,
-                 teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 2.0):
+                 teacher=None, distill_alpha: float = 0.5, distill_temperature: float = 2.0, risk=None):
         # teacher (training/distill.py: Teacher, or None): the loss becomes distill_alpha x today's cross entropy +
         # (1 - distill_alpha) x temperature^2 KL(teacher || student) at distill_temperature (i2l_ce_distill_fwd_bwd).  With
         # None nothing changes: the same entry is called with the same arguments.  Refused before anything else is looked at
@@ -47,6 +49,17 @@ class TrainStep:
                                 f"(wrap the model: Teacher(model)), got {type(teacher).__name__}")
             self.distill_alpha, self.distill_temperature = check_distill_arguments(distill_alpha, distill_temperature)
             teacher.check_vocab(model.vocab_size)
+        # risk (training/risk.py: RiskObjective, or None): the step draws risk.samples formulas per image from the model
+        # itself and trains on the gold row and on the draws, each draw weighted by its leave-one-out advantage in
+        # Levenshtein similarity.  With None nothing changes.  Refused, like a bad teacher, before a device is looked at
+        self.risk = risk
+        if risk is not None:
+            if not isinstance(risk, RiskObjective):
+                raise TypeError("img2latex_amd: TrainStep(risk=...) takes a training.risk.RiskObjective, got "
+                                f"{type(risk).__name__}")
+            if teacher is not None:
+                raise ValueError("img2latex_amd: TrainStep takes a teacher or a risk objective, not both")
+            risk.check_model(model)
         self.model = model
         self.lr, self.weight_decay, self.clip = lr, weight_decay, clip_grad_norm
         self.pad, self.smoothing, self.betas, self.eps = pad_token_id, label_smoothing, betas, eps
@@ -86,6 +99,10 @@ class TrainStep:
         # this rank's own rows (never all-reduced)
         self.loss_parts = torch.zeros(2, dtype=torch.float32, device=dev) if teacher is not None else None
         self._parts_count = None
+        # the risk objective only: [loss sum, non-PAD count] of the gold rows, then of the draws' rows, unweighted, and the
+        # mean reward of the last forward_backward's draws; this rank's own rows
+        self.risk_parts = torch.zeros(4, dtype=torch.float32, device=dev) if risk is not None else None
+        self.risk_batch = None        # what RiskObjective.assemble returned for the last forward_backward, plus "draws"
         self.grad_views: Dict[str, torch.Tensor] = {}
         with torch.no_grad():
             for name, p in named:
@@ -117,7 +134,9 @@ class TrainStep:
     def forward_backward(self, images: torch.Tensor, formulas: torch.Tensor) -> torch.Tensor:
         """Training forward + backward for this rank's shard; fills flat_grads (gradient of the SUM of the
         per-token losses), flat_grads[n] = loss sum, flat_grads[n+1] = non-PAD count.  Returns logits.  With a teacher
-        the loss is the distillation loss and ``loss_parts`` holds its two unweighted sums."""
+        the loss is the distillation loss and ``loss_parts`` holds its two unweighted sums.  With a risk objective the
+        decoder runs on ``B (samples + 1)`` sequences -- per image the gold row, then its draws (``risk_batch``) -- and the
+        logits returned are theirs; the count is the number of non-PAD targets of all of them."""
         model = self.model
         L = _lib.lib()
         formulas = formulas.to(torch.int32) if formulas.dtype != torch.int32 else formulas
@@ -126,10 +145,17 @@ class TrainStep:
         B, T = tokens_in.shape
         self.step_seed = step_seed(self.seed, self.step_count, self.rank, self._micro)
         enc, enc_state = encoder_train_forward(model.encoder, images)
+        if self.risk is not None:
+            # the draws come from the encoder rows of this very forward; the decoder then sees every row samples + 1 times
+            tokens_in, targets = self._risk_rows(enc, formulas, T)
+            times = self.risk.samples + 1
+            enc = rows_repeat(enc, times)
         logits, dec_state = decoder_train_forward(model.decoder, enc, tokens_in, self.step_seed)
         V = logits.shape[-1]
         dlogits = torch.empty_like(logits)
-        if self.teacher is None:
+        if self.risk is not None:
+            self._risk_loss(logits, targets, dlogits)
+        elif self.teacher is None:
             nbytes = L.i2l_ce_workspace_bytes(B * T)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
             _lib.check(L.i2l_ce_label_smooth_fwd_bwd(logits.data_ptr(), targets.data_ptr(), B * T, V, self.pad,
@@ -147,6 +173,10 @@ class TrainStep:
         denc = decoder_train_backward(model.decoder, dec_state, dlogits, dgr, lanes=side)
         if side:
             self._side_keep.extend((dec_state, dlogits, enc_state, images, tokens_in))
+        if self.risk is not None:
+            if side:
+                self._side_keep.append(enc)                          # the repeated rows the side lanes still read
+            denc = rows_fold(denc, times)                            # d(repeat): the rows of an image summed, in order
         egr = {n[len("encoder."):]: g for n, g in self.grad_views.items() if n.startswith("encoder.")}
 
         def after_linear():
@@ -193,8 +223,38 @@ class TrainStep:
         self._parts_count = self.flat_grads[self.n + 1].clone()      # this rank's count: apply() all-reduces the slot
         del rows, records, ws                                        # stream-ordered: the allocator reuses them after the launch
 
+    def _risk_rows(self, enc, formulas, T):
+        """The step's draws and i2l_risk_rows -> the decoder's (tokens_in, targets) of the B (samples + 1) sequences;
+        ``risk_batch`` keeps everything the kernel wrote."""
+        draws = self.risk.draw(self.model, enc, T, risk_seed(self.step_seed))
+        batch = self.risk.assemble(formulas, draws, self.pad, self.smoothing)
+        batch["draws"] = draws
+        self.risk_batch = batch
+        return batch["rows"][:, :-1].contiguous(), batch["rows"][:, 1:].contiguous()
+
+    def _risk_loss(self, logits, targets, dlogits) -> None:
+        """i2l_ce_weighted_fwd_bwd on the assembled sequences: the weighted sum and the count of ALL non-PAD targets where
+        the plain loss puts them (flat_grads[n], [n+1]), the two unweighted parts in ``risk_parts``."""
+        L = _lib.lib()
+        rows, T, V = logits.shape
+        batch = self.risk_batch
+        nbytes = L.i2l_ce_weighted_workspace_bytes(rows * T)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+        _lib.check(L.i2l_ce_weighted_fwd_bwd(logits.data_ptr(), targets.data_ptr(), rows, T, V, self.pad,
+                                             batch["coef"].data_ptr(), batch["smooth"].data_ptr(), batch["part"].data_ptr(),
+                                             ws.data_ptr(), nbytes, dlogits.data_ptr(),
+                                             self.flat_grads.data_ptr() + 4 * self.n, self.risk_parts.data_ptr(),
+                                             _lib.stream_ptr()), "ce_weighted_fwd_bwd")
+        del ws                                                       # stream-ordered: the allocator reuses it after the launch
+
     def _loss_parts(self) -> Dict[str, torch.Tensor]:
-        """{} without a teacher; else the last forward_backward's hard and soft loss per non-PAD token (device tensors)."""
+        """{} for the plain loss; with a teacher the last forward_backward's hard and soft loss per non-PAD token; with a
+        risk objective its mean reward and the unweighted cross entropy per non-PAD token of the gold rows (hard_loss) and
+        of the draws' rows (risk_loss).  Device tensors."""
+        if self.risk is not None:
+            parts = self.risk_parts
+            return dict(reward=self.risk_batch["reward"].mean(), hard_loss=parts[0] / parts[1].clamp(min=1.0),
+                        risk_loss=parts[2] / parts[3].clamp(min=1.0))
         if self.teacher is None:
             return {}
         per_token = self.loss_parts / self._parts_count.clamp(min=1.0)
@@ -227,7 +287,8 @@ class TrainStep:
 
     def step(self, images: torch.Tensor, formulas: torch.Tensor) -> Dict[str, torch.Tensor]:
         """trainer.py:303-343 for one batch.  Returns device tensors (no sync): loss, total_norm, count, skipped -- and
-        with a teacher ``hard_loss`` / ``soft_loss``, the two unweighted parts of the loss per non-PAD token of this rank.
+        with a teacher ``hard_loss`` / ``soft_loss``, the two unweighted parts of the loss per non-PAD token of this rank;
+        with a risk objective ``reward`` (the mean over this rank's draws), ``hard_loss`` and ``risk_loss``.
         ``skipped`` is 1.0 when the gradients were not finite (e.g. a grouped recurrence kernel timed out on a shared
         GPU and poisoned its outputs with NaN): the fused clip + Adam kernel then leaves parameters and moments
         untouched -- on every rank, since the all-reduce spreads the NaN -- and the caller may simply repeat the

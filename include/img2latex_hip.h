@@ -807,6 +807,58 @@ int i2l_ce_distill_fwd_bwd(const float* logits, const int32_t* targets, int rows
                            float temperature, float alpha, void* workspace, size_t workspace_bytes,
                            float* dlogits_out, float* loss_sum_and_count_out, float* parts_out, i2l_stream_t stream);
 
+/* Minimum-risk fine-tuning (this package; the reference trains on the gold prefix alone): train on the model's own draws,
+ * each weighted by how its Levenshtein similarity to the gold formula compares with the image's other draws.
+ * csrc/risk_rules.inc.h states the rules; the four entries below are the launches a training step adds.
+ *
+ * i2l_risk_rows: formulas (images, steps + 1) int32 = [START, tokens, END, PAD ...]; draws (images, samples, steps) int32
+ * as i2l_sample_decode_multi leaves them (-1 behind END).  Per image and draw n:
+ *   cut        draw: its ids before the first end_id (all `steps` without one); gold: formulas[1:] before the first
+ *              end_id or pad_id
+ *   dist_out   the exact Levenshtein distance d of the two;  len_out  the draw's number of tokens
+ *   reward_out r = 1 - d / max(len_draw, len_gold), 1 when both are empty, in double, rounded to fp32 once
+ *   advantage_out  A[n] = r[n] - (sum over m != n of r[m], in index order) / (samples - 1), in double from the double
+ *              rewards, rounded once
+ * and the batch of images (samples + 1) sequences, image-major, each steps + 1 tokens (rows_out), one value per sequence in
+ * coef_out / smooth_out / part_out:
+ *   sequence b (samples + 1)           the gold row as it stands; coef alpha, smooth label_smoothing, part 0
+ *   sequence b (samples + 1) + 1 + n   [START, draw n through its END, pad_id ...]; coef (float)((1 - (double)alpha) A[n])
+ *                                      from the double advantage, smooth 0, part 1
+ * A pad_id the model sampled before its END stays in the row (where the loss masks it like a gold PAD) and counts in the
+ * distance and the length.  One workgroup per image, one wave per draw; no atomics, no polls; every element of the eight
+ * outputs is written.
+ * Accepted: images, steps >= 1, steps <= I2L_MAX_RANK_STEPS, 2 <= samples <= I2L_MAX_NBEST, 0 <= alpha <= 1,
+ * 0 <= label_smoothing < 1.  A NULL pointer, a non-positive dimension, alpha or label_smoothing outside its range:
+ * I2L_ERR_ARG; samples < 2 or > I2L_MAX_NBEST, steps > I2L_MAX_RANK_STEPS: I2L_ERR_UNSUPPORTED.
+ *
+ * i2l_ce_weighted_fwd_bwd: i2l_ce_label_smooth_fwd_bwd whose token row i belongs to sequence i / steps (logits
+ * (seqs * steps, vocab), targets (seqs * steps)), each sequence with its own coefficient, smoothing and part:
+ *   dlogits[i][v] = keep coef (softmax(x)[v] - (1 - eps)[v == t] - eps / vocab),   eps = seq_smooth[seq]
+ *   loss_sum_and_count_out[0] = SUM_i coef row_loss_i (row_loss as in i2l_ce_label_smooth_fwd_bwd with the sequence's eps),
+ *   [1] = the UNWEIGHTED number of non-pad rows; parts_out (4 floats or NULL) = [loss sum, non-pad rows] of the sequences
+ *   with seq_part == 0, then of all the others, unweighted.  Fixed-order double sums.  With every coefficient 1 and one
+ *   smoothing value every output equals i2l_ce_label_smooth_fwd_bwd's bit for bit.  workspace:
+ *   i2l_ce_weighted_workspace_bytes(seqs * steps).  NULL pointers (dlogits_out and parts_out may be NULL), non-positive
+ *   dimensions: I2L_ERR_ARG; seqs * steps >= 2^31: I2L_ERR_UNSUPPORTED; a short workspace: I2L_ERR_WORKSPACE.
+ *
+ * i2l_rows_repeat: out[r * times + j][:] = in[r][:], in (rows, width), out (rows * times, width) fp32.
+ * i2l_rows_fold:   out[r][:] = sum_j in[r * times + j][:], an fp32 sum in the order j = 0 .. times - 1; in (rows * times,
+ * width), out (rows, width).  The gradient of i2l_rows_repeat.  NULL pointers, non-positive dimensions or more than 2^38
+ * elements: I2L_ERR_ARG.
+ *
+ * Every refusal of the four is host code before the first HIP call and leaves every output untouched. */
+int i2l_risk_rows(const int32_t* formulas, const int32_t* draws, int images, int samples, int steps, int start_id,
+                  int end_id, int pad_id, float alpha, float label_smoothing, int32_t* rows_out, float* coef_out,
+                  float* smooth_out, int32_t* part_out, int32_t* dist_out, int32_t* len_out, float* reward_out,
+                  float* advantage_out, i2l_stream_t stream);
+size_t i2l_ce_weighted_workspace_bytes(int rows);
+int i2l_ce_weighted_fwd_bwd(const float* logits, const int32_t* targets, int seqs, int steps, int vocab, int pad_id,
+                            const float* seq_coef, const float* seq_smooth, const int32_t* seq_part, void* workspace,
+                            size_t workspace_bytes, float* dlogits_out, float* loss_sum_and_count_out, float* parts_out,
+                            i2l_stream_t stream);
+int i2l_rows_repeat(const float* in, int rows, int width, int times, float* out, i2l_stream_t stream);
+int i2l_rows_fold(const float* in, int rows, int width, int times, float* out, i2l_stream_t stream);
+
 /* clip_grad_norm_(max_norm) + Adam(lr, betas, eps, coupled L2 weight_decay) over flat fp32 buffers of
  * n elements (trainer.py:91-93,338-342).  grads hold the gradient of the SUM loss; count_ptr (device,
  * may be NULL = 1) is the number of non-pad target tokens the sum runs over (the GLOBAL count after the
